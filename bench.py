@@ -22,6 +22,10 @@ each step with ONE all-gather of the scored nodes (pred_dist) over RCCL.
 
 Prints ONE JSON line (rank 0).  value = typed KG edges aggregated per second, whole job:
 N * B * E * L * K / t  (t = max over ranks of the barrier-bracketed wall time of K steps).
+
+A plain run only sets up, warms up, times the K steps and prints that line.  --full adds the side measurements
+(step-time spread, exact-fp32 loop, structure-build timings, roofline, CPU baseline with parity_in_run, other workloads,
+e2e, train_step).  --dump-outputs DIR writes what the last timed step returned as .npy files (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -169,6 +173,13 @@ def main():
                     help="steps of the additional exact-fp32 timed loop (ms_per_step_fp32); 0 = off")
     ap.add_argument("--math", choices=["default", "fp32", "bf16x3", "mixed"], default="default",
                     help="math mode of the dense projections (default = the library's default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: step-time spread, exact-fp32 loop, structure-build "
+                         "timings, roofline, CPU baseline and parity_in_run, other workloads, e2e and train_step legs.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (rank 0): pred_dist.npy, the answer "
+                         "distribution [B, N], and node_state.npy, the final node state (a fixed sample of its rows when large)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -324,6 +335,9 @@ def main():
     finally:
         if gc_was:
             gc.enable()
+    if args.dump_outputs and rank == 0:
+        # read before anything else runs on the layer: the node state is the one the last timed step left behind
+        dump_outputs(args.dump_outputs, cfg, last, graph.h[cfg.L - 1] if graph is not None else layer.local_entity_emb)
     if distributed:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -332,7 +346,7 @@ def main():
 
     # step-time spread: `spread_steps` further steps, each bracketed by its own HIP event pair (rank 0's device time)
     spread = None
-    if args.spread_steps > 0:
+    if args.full and args.spread_steps > 0:
         # a pool of 16 event pairs, read back every 16 steps: hundreds of timing events outstanding at once made the
         # HIP runtime grow its signal pool in the middle of the loop (one 30-60 ms host stall, seen as a "step")
         pool = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(16)]
@@ -373,7 +387,7 @@ def main():
     # must reproduce the timed loop's last result bit for bit - are kept and compared further down with the reference's
     # own ReasonGNNLayer run on the identical batch by the cpu_baseline leg
     gpu_results = {}
-    want_parity = rank == 0 and world == 1 and graph is None and not args.no_cpu_baseline
+    want_parity = args.full and rank == 0 and world == 1 and graph is None and not args.no_cpu_baseline
 
     def record_results(lay):
         with torch.no_grad():
@@ -390,7 +404,7 @@ def main():
     # the same step in EXACT fp32 (v_mfma_f32_16x16x4_f32 everywhere; the default 'mixed' mode runs the two large
     # products as bf16x3): a second, shorter timed loop on a layer object bound to that math mode
     ms_per_step_fp32 = None
-    if rank == 0 and graph is None and ops.get_dense_math() != ops.MATH_FP32 and args.fp32_steps > 0:
+    if args.full and rank == 0 and graph is None and ops.get_dense_math() != ops.MATH_FP32 and args.fp32_steps > 0:
         old_math = ops.set_dense_math(ops.MATH_FP32)
         try:
             layer32 = stack.build_layer(cfg, batch, params, dev)
@@ -418,21 +432,22 @@ def main():
     # ~45 ms pause inside the timed loop of the workloads with many launches per step (C3: 2.06 instead of 0.50 ms per step;
     # tools/c3_probe.sh) - round 6 found such pauses to be full collections of the interpreter's cyclic collector, which is
     # now off across the timed region (see above); the order is kept
-    et = batch.edge_tuple
-    t0 = time.perf_counter()
-    for _ in range(3):
-        ops.CsrPlan(et[0], et[1], et[2], cfg.B, cfg.N, cfg.R1, dev, validate=False)
-    torch.cuda.synchronize()
-    csr_build_ms = (time.perf_counter() - t0) * 1e3 / 3
-    csr_cached_ms, csr_concat_ms = (cached_structure_ms(batch, dev, ops)
-                                    if rank == 0 and not os.environ.get("BENCH_SKIP_STRUCTURE_TIMING") else (None, None))
-    overlapped = None
-    # (single process only: `step` enqueues the ranks' all-gather when a process group is up - rank 0 alone must not call it)
-    if rank == 0 and not distributed and graph is None and not strong and not os.environ.get("BENCH_SKIP_STRUCTURE_TIMING"):
-        try:
-            overlapped = build_plus_step_ms(batch, dev, step, 48)
-        except Exception as e:                       # never fail the bench on the side measurement
-            overlapped = {"error": repr(e)[:300]}
+    csr_build_ms = csr_cached_ms = csr_concat_ms = overlapped = None
+    if args.full:
+        et = batch.edge_tuple
+        t0 = time.perf_counter()
+        for _ in range(3):
+            ops.CsrPlan(et[0], et[1], et[2], cfg.B, cfg.N, cfg.R1, dev, validate=False)
+        torch.cuda.synchronize()
+        csr_build_ms = (time.perf_counter() - t0) * 1e3 / 3
+        csr_cached_ms, csr_concat_ms = (cached_structure_ms(batch, dev, ops)
+                                        if rank == 0 and not os.environ.get("BENCH_SKIP_STRUCTURE_TIMING") else (None, None))
+        # (single process only: `step` enqueues the ranks' all-gather when a process group is up - rank 0 alone must not call it)
+        if rank == 0 and not distributed and graph is None and not strong and not os.environ.get("BENCH_SKIP_STRUCTURE_TIMING"):
+            try:
+                overlapped = build_plus_step_ms(batch, dev, step, 48)
+            except Exception as e:                       # never fail the bench on the side measurement
+                overlapped = {"error": repr(e)[:300]}
 
     ms_per_step = elapsed * 1e3 / args.steps
     typed_edges = global_B * cfg.E * cfg.L * cfg.T
@@ -463,7 +478,8 @@ def main():
                                         if csr_concat_ms else None),
         # host-buffer boundary: int64 tuple -> int32 upload over PCIe + device structure build, once per batch,
         # amortised over ONE step (a ReaRev forward runs num_iter steps on the same structure); never `value`
-        "value_incl_upload_and_build": typed_edges / (elapsed / args.steps + csr_build_ms * 1e-3),
+        "value_incl_upload_and_build": (typed_edges / (elapsed / args.steps + csr_build_ms * 1e-3)
+                                        if csr_build_ms is not None else None),
         # a fresh structure every step, built in line from the device fact cache WITHOUT a stream wait (the cache knows the
         # relation counts): build + step in one loop
         "structure_build_in_line": overlapped,
@@ -480,7 +496,7 @@ def main():
                    if graph is not None else "eager: one gnnrag_reason_stack call per step"),
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         out.update(roofline_leg(cfg, layer, devin, ops, F_g, args.steps))
         if not args.no_cpu_baseline and world == 1:     # rank 0 at N = 1 only (the other ranks would idle)
             sample_b = args.cpu_sample_b
@@ -552,7 +568,7 @@ def other_workloads_leg(names, math):
     import subprocess
     out = {}
     for w in names:
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", "20", "--warmup", "10",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", w, "--steps", "20", "--warmup", "10",
                "--no-cpu-baseline", "--no-e2e", "--spread-steps", "0", "--fp32-steps", "0", "--clock-ramp-ms", "200",
                "--other-workloads", "", "--math", math]
         t0 = time.perf_counter()
@@ -581,6 +597,27 @@ def other_workloads_leg(names, math):
 def synth_T(name):
     from gnnrag_amd import synth
     return synth.CONFIGS[name].T
+
+
+DUMP_STATE_ROWS = 16384      # node-state rows kept by --dump-outputs: 16384 x D=200 fp32 = 13 MB (C2's whole state is 102 MB)
+
+
+def dump_outputs(out_dir, cfg, pred_dist, node_state):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files - the answer distribution of the
+    last layer call (``pred_dist.npy``, [B, N], whole) and the node state that call left in the layer
+    (``node_state.npy``): all B x N rows of D (zero padding of the hidden size cut off) when they fit
+    DUMP_STATE_ROWS, otherwise a fixed seeded sample of them in ascending order, whose flat row indices go to
+    ``node_state_rows.npy``.  The inputs are seeded: the same arguments give the same files on every build."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    d = pred_dist.detach().float().cpu().numpy()
+    np.save(os.path.join(out_dir, "pred_dist.npy"), d)
+    h = node_state.detach().reshape(cfg.B, cfg.N, -1)[..., :cfg.D].reshape(-1, cfg.D)      # (this rank's questions)
+    if h.shape[0] > DUMP_STATE_ROWS:
+        rows = np.sort(np.random.default_rng(0).choice(h.shape[0], DUMP_STATE_ROWS, replace=False))
+        np.save(os.path.join(out_dir, "node_state_rows.npy"), rows.astype(np.float64))
+        h = h[torch.from_numpy(rows).to(h.device)]
+    np.save(os.path.join(out_dir, "node_state.npy"), h.float().cpu().numpy())
 
 
 def cached_structure_ms(batch, dev, ops):

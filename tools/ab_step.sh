@@ -6,7 +6,7 @@ export BENCH_SKIP_STRUCTURE_TIMING=1
 for round in 1 2; do
   for v in default "$@"; do
     if [ "$v" = default ]; then unset GNNRAG_LIB; else export GNNRAG_LIB=$PWD/gnn-rag_amd/lib/exp_$v.so; fi
-    python bench.py --steps 200 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
+    python bench.py --full --steps 200 --warmup 30 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
