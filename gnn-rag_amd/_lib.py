@@ -42,6 +42,12 @@ class RelorderStruct(C.Structure):
                 ("chunk_ptr", C.c_void_p)]
 
 
+class UGraphStruct(C.Structure):
+    """Mirror of ``struct gnnrag_ugraph`` (include/gnnrag.h)."""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("F", C.c_int64), ("cap", C.c_int64),
+                ("u_ptr", C.c_void_p), ("u_adj", C.c_void_p)]
+
+
 class LayerParams(C.Structure):
     """Mirror of ``struct gnnrag_layer_params`` (include/gnnrag.h)."""
     _fields_ = [("W_rel", C.c_void_p), ("b_rel", C.c_void_p), ("pos_fwd", C.c_void_p), ("pos_inv", C.c_void_p),
@@ -124,6 +130,15 @@ SIGNATURES = {
                                                   C.c_int32, _VP]),
     "gnnrag_aggregate_fused_frontier": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gnnrag_frontier_read": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP]),
+    # reasoning paths (additive to ABI 16)
+    "gnnrag_ugraph_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnnrag_ugraph_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnnrag_ugraph_build": (C.c_int, [C.POINTER(CsrStruct), _VP, C.c_size_t, _VP, C.c_size_t, C.POINTER(UGraphStruct),
+                                      _VP]),
+    "gnnrag_paths_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gnnrag_paths_out_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "gnnrag_shortest_paths": (C.c_int, [C.POINTER(UGraphStruct), _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                        _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "gnnrag_stream_copy": (C.c_int, [_VP, _VP, C.c_int64, _VP]),
     "gnnrag_abi_version": (C.c_int, []),
     "gnnrag_error_string": (C.c_char_p, [C.c_int]),

@@ -1087,6 +1087,102 @@ def topp_candidates(pred_dist: torch.Tensor, eligible: torch.Tensor, ignore_prob
     return slots, cnt
 
 
+class UGraph:
+    """Simple undirected adjacency of a batch on the device (``gnnrag_ugraph_build``): per node its neighbours in
+    ascending order, each with the winning fact of the pair (the largest fact id among the facts that join the two
+    nodes).  What the reference's ``build_graph`` (``llm/src/utils/graph_utils.py:9-15``) makes with networkx, derived
+    from the structure that is already resident.  Owns its memory like :class:`CsrPlan`."""
+
+    def __init__(self, plan: "CsrPlan"):
+        lib = _lib.load()
+        self.B, self.N, self.F, self.device = plan.B, plan.N, plan.F, plan.device
+        with torch.cuda.device(self.device):
+            nbytes = lib.gnnrag_ugraph_bytes(self.F, self.B, self.N)
+            sbytes = lib.gnnrag_ugraph_scratch_bytes(self.F, self.B, self.N)
+            if nbytes == 0 or sbytes == 0:
+                raise ValueError("batch too large for the undirected adjacency (2 F and B * N must fit int32)")
+            self._mem = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            scratch = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+            self.c = _lib.UGraphStruct()
+            _lib.check(lib.gnnrag_ugraph_build(C.byref(plan.c), self._mem.data_ptr(), self._mem.numel(),
+                                               scratch.data_ptr(), scratch.numel(), C.byref(self.c), _stream()),
+                       "gnnrag_ugraph_build")
+            scratch.record_stream(torch.cuda.current_stream())      # nothing waited for the stream: keep the scratch
+        self._plan = plan                   # a concatenated structure's parts stay alive with it
+
+    @classmethod
+    def from_plan(cls, plan: "CsrPlan") -> "UGraph":
+        return cls(plan)
+
+    def _dev_view(self, addr: int, n: int) -> torch.Tensor:
+        off = int(addr) - self._mem.data_ptr()
+        return self._mem[off: off + 4 * n].view(torch.int32)
+
+    def to_host(self) -> dict:
+        """(u_ptr [B*N+1], u_adj [U, 2]) copied back (tests and tools; waits for the stream)."""
+        u_ptr = self._dev_view(self.c.u_ptr, self.B * self.N + 1).cpu().numpy()
+        U = int(u_ptr[-1])
+        u_adj = self._dev_view(self.c.u_adj, 2 * U).cpu().numpy().reshape(-1, 2) if U else np.zeros((0, 2), np.int32)
+        return {"u_ptr": u_ptr, "u_adj": u_adj}
+
+
+class PathBuffers:
+    """Worst-case output arrays and the workspace of ``gnnrag_shortest_paths`` for one ``(B, N, limits)``."""
+
+    def __init__(self, B, N, max_seeds, max_cands, max_paths, max_hops, device):
+        lib = _lib.load()
+        self.key = (int(B), int(N), int(max_seeds), int(max_cands), int(max_paths), int(max_hops), torch.device(device))
+        P = B * max_seeds * max_cands
+        if lib.gnnrag_paths_out_bytes(B, max_seeds, max_cands, max_paths, max_hops) == 0:
+            raise ValueError("path limits out of range (positive sizes, max_hops <= 254, pairs * max_paths < 2^31)")
+        nws = lib.gnnrag_paths_workspace_bytes(B, N, max_seeds, max_cands)
+        if nws == 0:
+            raise _lib.GnnragError("gnnrag_shortest_paths supports at most 65536 node slots per question (N = %d)" % N)
+        kw = dict(dtype=torch.int32, device=device)
+        self.q_info = torch.empty((B, 2), **kw)
+        self.pair_info = torch.empty((B, max_seeds, max_cands, 2), **kw)
+        self.path_off = torch.empty(P + 1, **kw)
+        self.path_nodes = torch.empty((P * max_paths, max_hops + 1), **kw)
+        self.path_facts = torch.empty((P * max_paths, max_hops), **kw)
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=device)
+
+
+_path_buffers = {}
+
+
+def shortest_paths(graph: "UGraph", seed_flag: torch.Tensor, cand_slot: torch.Tensor, cand_cnt: torch.Tensor,
+                   max_seeds: int = 4, max_cands: int = 16, max_paths: int = 64, max_hops: int = 8,
+                   buffers: Optional["PathBuffers"] = None) -> "PathBuffers":
+    """All shortest paths seed -> candidate per question (``gnnrag_shortest_paths``; the reference's ``get_truth_paths``,
+    ``llm/src/utils/graph_utils.py:37-60``).  ``cand_slot`` / ``cand_cnt`` are :func:`topp_candidates`' outputs.  Nothing
+    waits for the stream; the result is the :class:`PathBuffers` holding the device arrays (one set per shape and limits
+    is kept and reused when ``buffers`` is not given: copy what you keep before the next call)."""
+    lib = _lib.load()
+    B, N = graph.B, graph.N
+    seed_flag = _chk(seed_flag, "seed_flag", dtype=torch.uint8, shape=(B, N))
+    cand_slot = _chk(cand_slot, "cand_slot", dtype=torch.int32, shape=(B, N))
+    cand_cnt = _chk(cand_cnt, "cand_cnt", dtype=torch.int32, shape=(B, 2))
+    for name, t in (("seed_flag", seed_flag), ("cand_slot", cand_slot), ("cand_cnt", cand_cnt)):
+        if t.device != graph.device:
+            raise _lib.GnnragError("%s lives on %s but the graph was built on %s" % (name, t.device, graph.device))
+    key = (B, N, int(max_seeds), int(max_cands), int(max_paths), int(max_hops), graph.device)
+    with torch.cuda.device(graph.device):
+        if buffers is None:
+            buffers = _path_buffers.get(key)
+            if buffers is None:
+                _path_buffers.clear()               # one set at a time: the worst case is large
+                buffers = _path_buffers[key] = PathBuffers(*key)
+        elif buffers.key != key:
+            raise ValueError("buffers were made for %s, the call needs %s" % (buffers.key, key))
+        o = buffers
+        _lib.check(lib.gnnrag_shortest_paths(C.byref(graph.c), seed_flag.data_ptr(), cand_slot.data_ptr(),
+                                             cand_cnt.data_ptr(), max_seeds, max_cands, max_paths, max_hops,
+                                             o.q_info.data_ptr(), o.pair_info.data_ptr(), o.path_off.data_ptr(),
+                                             o.path_nodes.data_ptr(), o.path_facts.data_ptr(), o.ws.data_ptr(),
+                                             o.ws.numel(), _stream()), "gnnrag_shortest_paths")
+    return buffers
+
+
 def stream_copy(src: torch.Tensor, dst: torch.Tensor):
     lib = _lib.load()
     with torch.cuda.device(src.device):

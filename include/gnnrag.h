@@ -505,6 +505,62 @@ int gnnrag_lstm_forward(const float* x, const float* w_ih, const float* w_hh, co
                         const float* h0, const float* c0, float* out, float* h_n, float* c_n, int32_t B, int32_t T,
                         int32_t E, int32_t H, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* ---- Reasoning paths (additive to ABI 16: new entry points only, nothing above changes) ----------------------------------
+ * The retrieval step of GNN-RAG: all shortest paths between the question's entities and the retrieved candidates in the
+ * question's subgraph taken as a SIMPLE UNDIRECTED graph - what llm/src/utils/graph_utils.py builds with networkx
+ * (build_graph :9-15) and searches with nx.all_shortest_paths per pair (get_truth_paths :37-60), called from
+ * llm/src/qa_prediction/build_qa_input.py:114-127.
+ *
+ * Graph of a question: its facts with head != tail; all facts joining one unordered pair {u, v} (any relation, either
+ * orientation) are ONE edge whose relation is that of the fact with the largest fact id (G.add_edge overwrites the
+ * attribute): the pair's winning fact. */
+typedef struct gnnrag_ugraph {
+  int32_t B;        /* questions                                                                  */
+  int32_t N;        /* node slots per question                                                    */
+  int64_t F;        /* facts of the structure it was made from                                    */
+  int64_t cap;      /* records u_adj has room for (2 F); the count in use is u_ptr[B*N], on the device */
+  int32_t* u_ptr;   /* [B*N+1]  first neighbour record of each node                               */
+  int32_t* u_adj;   /* [cap][2] (neighbour node, winning fact id), neighbours of a node ascending */
+} gnnrag_ugraph;
+
+/* Caller-owned device memory of a gnnrag_ugraph / of its build (0 on negative or overflowing sizes). */
+size_t gnnrag_ugraph_bytes(int64_t F, int32_t B, int32_t N);
+size_t gnnrag_ugraph_scratch_bytes(int64_t F, int32_t B, int32_t N);
+/* Derives the adjacency from a structure made by gnnrag_csr_build, gnnrag_csr_build_counts or gnnrag_csr_concat (rows in
+ * any order, hub-sorted rows included; only row_ptr / edge / perm are read): a 64-bit-key radix sort of (node,
+ * neighbour), run heads flagged and scanned, the largest fact id of each run kept.  No wait for the stream.  Replaces
+ * build_graph (graph_utils.py:9-15). */
+int gnnrag_ugraph_build(const gnnrag_csr* csr, void* mem, size_t mem_bytes, void* scratch, size_t scratch_bytes,
+                        gnnrag_ugraph* out, gnnrag_stream_t stream);
+
+/* Device scratch of gnnrag_shortest_paths: levels (bytes) and path counts of every (question, seed).  0 on bad sizes
+ * and for N > 65536 (the levels of a question live in one CU's LDS; larger questions are GNNRAG_E_UNSUPPORTED). */
+size_t gnnrag_paths_workspace_bytes(int32_t B, int32_t N, int32_t max_seeds, int32_t max_cands);
+/* Worst-case bytes of the five output arrays of gnnrag_shortest_paths, each rounded up to 256 bytes, in the order
+ * q_info, pair_info, path_off, path_nodes, path_facts (a caller may carve one block that way).  With P = B * max_seeds *
+ * max_cands pairs: q_info [B,2], pair_info [P,2], path_off [P+1], path_nodes [P*max_paths, max_hops+1], path_facts
+ * [P*max_paths, max_hops].  0 on bad sizes, max_hops > 254 or P * max_paths >= 2^31. */
+size_t gnnrag_paths_out_bytes(int32_t B, int32_t max_seeds, int32_t max_cands, int32_t max_paths, int32_t max_hops);
+/* Pairs of question b = its seeds (slots with seed_flag != 0, ascending, the first max_seeds) x its candidates (the first
+ * min(cand_cnt[b,1], max_cands) entries of row b of cand_slot: exactly the outputs of gnnrag_topp_candidates, so
+ * selection -> paths runs on one stream without a host round trip).  Pair index = (b * max_seeds + seed index) *
+ * max_cands + candidate index.  Replaces get_truth_paths (graph_utils.py:37-60).
+ *   q_info[b]    = (seeds found, candidates offered): larger than max_seeds / max_cands means the question was cut
+ *   pair_info[p] = (n_paths, hops): the true number of shortest paths, saturating at INT32_MAX, and their length; (0, -1)
+ *                  when the candidate was not reached within max_hops, an endpoint has no edge, or the pair does not
+ *                  exist; seed == candidate with an edge: (1, 0)
+ *   path_off     = exclusive scan of min(n_paths, max_paths): the records of pair p are path_off[p] .. path_off[p+1]
+ *   path_nodes   = per record max_hops + 1 node ids (question * N + slot) from the seed to the candidate, then -1
+ *   path_facts   = per record max_hops winning fact ids (hop i joins nodes i and i + 1), then -1
+ * The records of a pair are its paths of rank 0 .. min(n_paths, max_paths) - 1 in rank order, paths ranked
+ * lexicographically by their node sequence read from the candidate back to the seed.  Records are written compactly:
+ * path_off[P] of them exist, the rest of the two arrays is not touched.  max_hops <= 254 and N <= 65536, else
+ * GNNRAG_E_UNSUPPORTED.  Nothing waits for the stream. */
+int gnnrag_shortest_paths(const gnnrag_ugraph* graph, const uint8_t* seed_flag, const int32_t* cand_slot,
+                          const int32_t* cand_cnt, int32_t max_seeds, int32_t max_cands, int32_t max_paths,
+                          int32_t max_hops, int32_t* q_info, int32_t* pair_info, int32_t* path_off, int32_t* path_nodes,
+                          int32_t* path_facts, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
 /* Plain HBM copy kernel (float4 per lane) used by bench.py to measure the achievable
  * streaming ceiling next to the 8 TB/s spec.  n = number of floats (multiple of 4). */
 int gnnrag_stream_copy(const float* src, float* dst, int64_t n, gnnrag_stream_t stream);
