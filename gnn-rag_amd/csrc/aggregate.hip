@@ -1788,6 +1788,8 @@ extern "C" int gnnrag_aggregate(const gnnrag_csr* csr, const float* dist, const 
                                 const float* T_fwd, const float* T_inv, float* agg, int32_t D, int32_t I,
                                 void* workspace, size_t workspace_bytes, gnnrag_stream_t stream) {
   if (!csr || !dist || !ins || !T_fwd || !T_inv || !agg || D <= 0 || I <= 0) return GNNRAG_E_BADARG;
+  // the stated size, whichever walk this call takes (the gather walk alone would get by with less)
+  if (!workspace || workspace_bytes < gnnrag_aggregate_workspace_bytes(csr, D, I)) return GNNRAG_E_WORKSPACE;
   WalkArgs a;
   memset(&a, 0, sizeof(a));
   int rc = fill_common(a, csr, D, workspace, workspace_bytes, I < 3 ? I : 3);
@@ -1821,6 +1823,7 @@ extern "C" int gnnrag_aggregate(const gnnrag_csr* csr, const float* dist, const 
 extern "C" int gnnrag_aggregate_fused(const gnnrag_csr* csr, const float* dist, const float* P, float* out,
                                       int32_t D, void* workspace, size_t workspace_bytes,
                                       gnnrag_stream_t stream_) {
+  if (csr && D > 0 && (!workspace || workspace_bytes < gnnrag_aggregate_workspace_bytes(csr, D, 1))) return GNNRAG_E_WORKSPACE;
   return gnnrag::aggregate_fused_dirs(csr, dist, P, out, D, 0, workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
@@ -1946,6 +1949,7 @@ extern "C" int gnnrag_typelayer(const gnnrag_csr* csr, const float* T, int use_w
                                 void* workspace, size_t workspace_bytes, gnnrag_stream_t stream) {
   if (!csr || !T || !h0 || D <= 0) return GNNRAG_E_BADARG;
   if (use_w_rel && (!csr->w_rel[0] || !csr->w_rel[1])) return GNNRAG_E_BADARG;
+  if (!workspace || workspace_bytes < gnnrag_aggregate_workspace_bytes(csr, D, 1)) return GNNRAG_E_WORKSPACE;
   WalkArgs a;
   memset(&a, 0, sizeof(a));
   const int rc = fill_common(a, csr, D, workspace, workspace_bytes, 1);

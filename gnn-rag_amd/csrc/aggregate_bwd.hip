@@ -780,6 +780,8 @@ extern "C" int gnnrag_aggregate_backward(const gnnrag_csr* csr, const gnnrag_rel
   const bool gather = gather_ok(relorder, D, I);
   if (relorder && (relorder->F != csr->F || relorder->rel_total != csr->rel_total)) return GNNRAG_E_BADARG;
   if (!gather && bwd_lds_bytes(2, csr->rel_max) > 160 * 1024 - 1024) return GNNRAG_E_UNSUPPORTED;
+  // the stated size, before anything is launched (the form this call takes may get by with less)
+  if (!workspace || workspace_bytes < gnnrag_backward_workspace_bytes(csr, relorder, D, I)) return GNNRAG_E_WORKSPACE;
   BwdArgs a;
   fill_bwd(a, csr, D, I);
   a.w[0] = csr->w_gnn[0];
@@ -845,6 +847,7 @@ extern "C" int gnnrag_aggregate_fused_backward(const gnnrag_csr* csr, const gnnr
   if (!csr || !relorder || !dist || !P || !g_nbr || !g_dist || !g_P || D <= 0 || csr->rel_total < 0) return GNNRAG_E_BADARG;
   if (relorder->F != csr->F || relorder->rel_total != csr->rel_total) return GNNRAG_E_BADARG;
   if (!gather_ok(relorder, D, 1) || ((((uintptr_t)P | (uintptr_t)g_nbr | (uintptr_t)g_P) & 15) != 0)) return GNNRAG_E_UNSUPPORTED;
+  if (!workspace || workspace_bytes < gnnrag_backward_workspace_bytes(csr, relorder, D, 1)) return GNNRAG_E_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   BwdArgs a;
   fill_bwd(a, csr, D, 1);
@@ -909,6 +912,7 @@ extern "C" int gnnrag_typelayer_backward(const gnnrag_csr* csr, const gnnrag_rel
                                          int32_t D, void* workspace, size_t workspace_bytes,
                                          gnnrag_stream_t stream_) {
   if (!csr || !g_pre || !g_T || D <= 0 || csr->rel_total < 0) return GNNRAG_E_BADARG;
+  if (!workspace || workspace_bytes < gnnrag_backward_workspace_bytes(csr, relorder, D, 1)) return GNNRAG_E_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   if (gather_ok(relorder, D, 1) && (!use_w_rel || w_rel_per_fact)) {
     if (relorder->F != csr->F || relorder->rel_total != csr->rel_total) return GNNRAG_E_BADARG;

@@ -62,6 +62,18 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32, shape=None) -> torch.T
     return t
 
 
+def _buf(shape, dtype, device, role: str, fill=None) -> torch.Tensor:
+    """Every device buffer this binding allocates for the library (outputs, workspaces, structure memory, scratch)
+    comes from here: ``fill=None`` leaves it uninitialised, a number fills it.  ``role`` names the buffer (entry point:
+    argument); nothing here reads it - the guarded allocator of the tests (tests/guarded.py) replaces this function and
+    reports a damaged guard under that name."""
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if fill == 0:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    return torch.full(shape, fill, dtype=dtype, device=device)
+
+
 _stage_buf = {"t": None}
 
 
@@ -124,7 +136,7 @@ class CsrPlan:
         if hrt_device is not None:
             if hrt_device.device != self.device and not (self.device.index is None):
                 raise _lib.GnnragError("hrt_device lives on %s, the plan on %s" % (hrt_device.device, self.device))
-            hrt = hrt_device if F else torch.zeros((3, 1), dtype=torch.int32, device=hrt_device.device)
+            hrt = hrt_device if F else _buf((3, 1), torch.int32, hrt_device.device, "csr_build: heads/rels/tails (no facts)", 0)
         elif (F and isinstance(base, np.ndarray) and heads.dtype == np.int32 and base is rels.base
                 and base is tails.base and base.dtype == np.int32 and base.shape == (3, F) and base.flags.c_contiguous
                 and heads.ctypes.data == base[0].ctypes.data and rels.ctypes.data == base[1].ctypes.data
@@ -158,8 +170,8 @@ class CsrPlan:
                 torch.cuda.current_stream().synchronize()                               # the block is reused next batch
             nbytes = lib.gnnrag_csr_bytes(F, B, N, R1, 0, 0)
             sbytes = lib.gnnrag_csr_scratch_bytes(F, B, N, R1)
-            self._mem = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
-            scratch = torch.empty(max(sbytes, 256), dtype=torch.uint8, device=self.device)
+            self._mem = _buf(max(nbytes, 256), torch.uint8, self.device, "csr_build: csr_mem")
+            scratch = _buf(max(sbytes, 256), torch.uint8, self.device, "csr_build: scratch")
             self.c = _lib.CsrStruct()
             row = self._hrt
             rt, rm = (-1, -1) if rel_counts is None else (int(rel_counts[0]), int(rel_counts[1]))
@@ -210,7 +222,7 @@ class CsrPlan:
         arr = (C.POINTER(_lib.CsrStruct) * B)(*[C.pointer(p.c) for p in parts])
         with torch.cuda.device(self.device):
             nbytes = lib.gnnrag_csr_bytes(self.F, B, self.N, self.R1, 0, 0)
-            self._mem = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            self._mem = _buf(max(nbytes, 256), torch.uint8, self.device, "csr_concat: csr_mem")
             self.c = _lib.CsrStruct()
             _lib.check(lib.gnnrag_csr_concat(arr, B, self.N, self.R1, self._mem.data_ptr(), self._mem.numel(),
                                              C.byref(self.c), _stream()), "gnnrag_csr_concat")
@@ -231,7 +243,8 @@ class CsrPlan:
                 h[0] += b * self.N
                 h[2] += b * self.N
                 blocks.append(h)
-            self._hrt_lazy = torch.cat(blocks, dim=1) if self.F else torch.zeros((3, 1), dtype=torch.int32, device=self.device)
+            self._hrt_lazy = (torch.cat(blocks, dim=1) if self.F else
+                              _buf((3, 1), torch.int32, self.device, "relorder_build: heads/rels/tails (no facts)", 0))
         return self._hrt_lazy
 
     @_hrt.setter
@@ -243,7 +256,7 @@ class CsrPlan:
         key = ("ws", D, min(I, 3))
         if key not in self._w:
             nbytes = _lib.load().gnnrag_aggregate_workspace_bytes(C.byref(self.c), D, I)
-            self._w[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            self._w[key] = _buf(max(nbytes, 256), torch.uint8, self.device, "aggregate / typelayer: workspace")
         return self._w[key]
 
     def relorder(self):
@@ -253,10 +266,10 @@ class CsrPlan:
             lib = _lib.load()
             w = self._w.get(("w_gnn_src",))
             with torch.cuda.device(self.device):
-                mem = torch.empty(max(lib.gnnrag_relorder_bytes(C.byref(self.c), int(w is not None)), 256),
-                                  dtype=torch.uint8, device=self.device)
-                scratch = torch.empty(max(lib.gnnrag_relorder_scratch_bytes(C.byref(self.c)), 256),
-                                      dtype=torch.uint8, device=self.device)
+                mem = _buf(max(lib.gnnrag_relorder_bytes(C.byref(self.c), int(w is not None)), 256),
+                           torch.uint8, self.device, "relorder_build: mem")
+                scratch = _buf(max(lib.gnnrag_relorder_scratch_bytes(C.byref(self.c)), 256),
+                               torch.uint8, self.device, "relorder_build: scratch")
                 ro = _lib.RelorderStruct()
                 row = self._hrt
                 _lib.check(lib.gnnrag_relorder_build(
@@ -272,7 +285,7 @@ class CsrPlan:
         if key not in self._w:
             nbytes = _lib.load().gnnrag_backward_workspace_bytes(C.byref(self.c), None if ro is None else C.byref(ro),
                                                                  D, I)
-            self._w[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=self.device)
+            self._w[key] = _buf(max(nbytes, 256), torch.uint8, self.device, "backward: workspace")
         return self._w[key]
 
     # -- lazily attached per-fact weights ----------------------------------------------------
@@ -284,8 +297,8 @@ class CsrPlan:
         if w.shape[0] != self.F:
             raise ValueError("%s has %d entries for %d facts" % (key, w.shape[0], self.F))
         with torch.cuda.device(self.device):
-            src = torch.from_numpy(w).to(self.device) if self.F else torch.zeros(1, device=self.device)
-            out = torch.empty((2, max(self.F, 1)), dtype=torch.float32, device=self.device)
+            src = torch.from_numpy(w).to(self.device) if self.F else _buf(1, torch.float32, self.device, "csr_permute_weight: w_per_fact (no facts)", 0)
+            out = _buf((2, max(self.F, 1)), torch.float32, self.device, "csr_permute_weight: out")
             _lib.check(lib.gnnrag_csr_permute_weight(C.byref(self.c), src.data_ptr(), int(square),
                                                      out[0].data_ptr(), out[1].data_ptr(), _stream()),
                        "gnnrag_csr_permute_weight")
@@ -377,7 +390,7 @@ def linear(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None
         if add.shape[1] != Nout:
             raise ValueError("add must have %d columns" % Nout)
         add_rows = add.shape[0]
-    out = torch.empty((M, Nout), dtype=torch.float32, device=A.device)
+    out = _buf((M, Nout), torch.float32, A.device, "linear: out")
     with torch.cuda.device(A.device):
         _lib.check(lib.gnnrag_linear(A.data_ptr(), M, K, W.data_ptr(), _ptr(bias), _ptr(add), add_rows,
                                      int(relu), out.data_ptr(), Nout, _math(math), _stream()), "gnnrag_linear")
@@ -410,13 +423,13 @@ def rel_transform(relfeat: torch.Tensor, relfeat_inv: torch.Tensor, layers, plan
             pos_rows = pos.shape[0]
             keep += [pos, pos_inv]
             params[j].pos_fwd, params[j].pos_inv = pos.data_ptr(), pos_inv.data_ptr()
-    out = torch.empty((L, 2, R1, D), dtype=torch.float32, device=relfeat.device)
+    out = _buf((L, 2, R1, D), torch.float32, relfeat.device, "rel_transform: out")
     pl = None
     if planes:
         nbytes = lib.gnnrag_rel_planes_bytes(R1, D, L)
         if nbytes == 0:
             raise _lib.GnnragError("relation planes need a hidden size <= 224")
-        pl = torch.empty((L, 2, 3, R1, nbytes // (L * 6 * R1 * 2)), dtype=torch.int16, device=relfeat.device)
+        pl = _buf((L, 2, 3, R1, nbytes // (L * 6 * R1 * 2)), torch.int16, relfeat.device, "rel_transform: planes")
     with torch.cuda.device(relfeat.device):
         _lib.check(lib.gnnrag_rel_transform(relfeat.data_ptr(), relfeat_inv.data_ptr(), R1, D, L, params, pos_rows,
                                             out.data_ptr(), _ptr(pl), _stream()), "gnnrag_rel_transform")
@@ -435,7 +448,7 @@ def relation_tables_planes(plan: "CsrPlan", planes: torch.Tensor, ins: torch.Ten
         raise ValueError("planes must be a contiguous [2, 3, R1, 448] int16 tensor of this plan's relation count")
     W_e2e = _chk(W_e2e, "e2e_linear.weight", shape=(D, (2 * I + 1) * D))
     _on_plan_device(plan, ins, "relational_ins")
-    P = torch.empty((2, max(plan.rel_total, 1), D), dtype=torch.float32, device=ins.device)
+    P = _buf((2, max(plan.rel_total, 1), D), torch.float32, ins.device, "relation_tables_planes: P")
     with torch.cuda.device(ins.device):
         _lib.check(lib.gnnrag_relation_tables_planes(C.byref(plan.c), planes.data_ptr(), ins.data_ptr(), W_e2e.data_ptr(),
                                                      P.data_ptr(), D, I, _stream()), "gnnrag_relation_tables_planes")
@@ -452,10 +465,10 @@ def gemm_tn(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
         raise ValueError("A is %s, B is %s" % (tuple(A.shape), tuple(B.shape)))
     M, N1 = A.shape
     N2 = B.shape[1]
-    out = torch.empty((N1, N2), dtype=torch.float32, device=A.device)
+    out = _buf((N1, N2), torch.float32, A.device, "gemm_tn: C")
     with torch.cuda.device(A.device):
         # the chunk count behind the workspace size depends on the CURRENT device's CU count: query it on A's device
-        ws = torch.empty(max(lib.gnnrag_gemm_tn_workspace_bytes(M, N1, N2), 16), dtype=torch.uint8, device=A.device)
+        ws = _buf(max(lib.gnnrag_gemm_tn_workspace_bytes(M, N1, N2), 16), torch.uint8, A.device, "gemm_tn: workspace")
         _lib.check(lib.gnnrag_gemm_tn(A.data_ptr(), B.data_ptr(), M, N1, N2, out.data_ptr(), ws.data_ptr(), ws.numel(),
                                       _stream()), "gnnrag_gemm_tn")
     return out
@@ -473,7 +486,7 @@ def aggregate(plan: CsrPlan, dist: torch.Tensor, ins: torch.Tensor, T_fwd: torch
         raise ValueError("dist/ins do not match the plan (B=%d, N=%d)" % (B, N))
     T_fwd = _chk(T_fwd, "T_fwd", shape=(plan.R1, D))
     T_inv = _chk(T_inv, "T_inv", shape=(plan.R1, D))
-    agg = torch.empty((B * N, 2 * I * D), dtype=torch.float32, device=dist.device)
+    agg = _buf((B * N, 2 * I * D), torch.float32, dist.device, "aggregate: agg")
     ws = plan.walk_workspace(D, I)
     with torch.cuda.device(dist.device):
         _lib.check(lib.gnnrag_aggregate(C.byref(plan.c), dist.data_ptr(), ins.data_ptr(), T_fwd.data_ptr(),
@@ -494,7 +507,7 @@ def relation_tables(plan: CsrPlan, T_fwd: torch.Tensor, T_inv: torch.Tensor, ins
     T_fwd = _chk(T_fwd, "T_fwd", shape=(plan.R1, D))
     T_inv = _chk(T_inv, "T_inv", shape=(plan.R1, D))
     W_e2e = _chk(W_e2e, "e2e_linear.weight", shape=(D, (2 * I + 1) * D))
-    P = torch.empty((2, plan.rel_total, D), dtype=torch.float32, device=ins.device)
+    P = _buf((2, plan.rel_total, D), torch.float32, ins.device, "relation_tables: P")
     with torch.cuda.device(ins.device):
         _lib.check(lib.gnnrag_relation_tables(C.byref(plan.c), T_fwd.data_ptr(), T_inv.data_ptr(), ins.data_ptr(),
                                               W_e2e.data_ptr(), P.data_ptr(), D, I, _math(math), _stream()),
@@ -525,7 +538,7 @@ def aggregate_fused_hub_form(plan: CsrPlan, D: int, I: int = 1) -> dict:
     (``gnnrag_aggregate_workspace_bytes(csr, D, I)``, softmax_layer.hip layer_ws)."""
     lib = _lib.load()
     ws = plan.walk_workspace(D, I)
-    form = torch.zeros(4, dtype=torch.int32, device=ws.device)
+    form = _buf(4, torch.int32, ws.device, "aggregate_fused_hub_form: form", 0)
     with torch.cuda.device(ws.device):
         _lib.check(lib.gnnrag_aggregate_fused_hub_form(C.byref(plan.c), int(D), ws.data_ptr(), ws.numel(), form.data_ptr(),
                                                        _stream()), "gnnrag_aggregate_fused_hub_form")
@@ -542,7 +555,7 @@ def aggregate_fused(plan: CsrPlan, dist: torch.Tensor, P: torch.Tensor) -> torch
         raise ValueError("P must be [2, plan.rel_total, D]")
     dist = _chk(dist, "dist").reshape(-1)
     _on_plan_device(plan, dist, "dist")
-    out = torch.empty((B * N, D), dtype=torch.float32, device=dist.device)
+    out = _buf((B * N, D), torch.float32, dist.device, "aggregate_fused: out")
     ws = plan.walk_workspace(D, 1)
     with torch.cuda.device(dist.device):
         _lib.check(lib.gnnrag_aggregate_fused(C.byref(plan.c), dist.data_ptr(), P.data_ptr(), out.data_ptr(), D,
@@ -564,7 +577,7 @@ class Frontier:
             raise ValueError("dist does not match the plan")
         self.dist = dist
         nbytes = max(lib.gnnrag_frontier_workspace_bytes(C.byref(plan.c)), 256)
-        self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dist.device)
+        self.ws = _buf(nbytes, torch.uint8, dist.device, "frontier_build: fws")
         with torch.cuda.device(dist.device):
             _lib.check(lib.gnnrag_frontier_build(C.byref(plan.c), dist.data_ptr(), self.ws.data_ptr(), self.ws.numel(),
                                                  _stream()), "gnnrag_frontier_build")
@@ -586,7 +599,7 @@ class Frontier:
         T_inv = _chk(T_inv, "T_inv", shape=(self.plan.R1, D))
         W_e2e = _chk(W_e2e, "e2e_linear.weight", shape=(D, (2 * I + 1) * D))
         if P is None:
-            P = torch.full((2, max(self.plan.rel_total, 1), D), float("nan"), dtype=torch.float32, device=ins.device)
+            P = _buf((2, max(self.plan.rel_total, 1), D), torch.float32, ins.device, "relation_tables_frontier: P", float("nan"))
         with torch.cuda.device(ins.device):
             _lib.check(_lib.load().gnnrag_relation_tables_frontier(
                 C.byref(self.plan.c), self.ws.data_ptr(), T_fwd.data_ptr(), T_inv.data_ptr(), ins.data_ptr(),
@@ -598,7 +611,7 @@ class Frontier:
         P = _chk(P, "P")
         D = P.shape[-1]
         if out is None:
-            out = torch.zeros((self.plan.B * self.plan.N, D), dtype=torch.float32, device=P.device)
+            out = _buf((self.plan.B * self.plan.N, D), torch.float32, P.device, "aggregate_fused_frontier: out", 0)
         with torch.cuda.device(P.device):
             _lib.check(_lib.load().gnnrag_aggregate_fused_frontier(
                 C.byref(self.plan.c), self.ws.data_ptr(), self.dist.data_ptr(), P.data_ptr(), out.data_ptr(), D,
@@ -616,8 +629,8 @@ def update_score_fused(h, nbr, W, b, w_s, b_s, mask, I: int, math: Optional[int]
     w_s = _chk(w_s, "w_s").reshape(-1)
     b_s = _chk(b_s, "b_s").reshape(-1)
     mask = _chk(mask, "mask").reshape(-1)
-    h_out = torch.empty_like(h)
-    score = torch.empty(BN, dtype=torch.float32, device=h.device)
+    h_out = _buf(h.shape, torch.float32, h.device, "update_score_fused: h_out")
+    score = _buf(BN, torch.float32, h.device, "update_score_fused: score")
     with torch.cuda.device(h.device):
         _lib.check(lib.gnnrag_update_score_fused(h.data_ptr(), nbr.data_ptr(), W.data_ptr(), b.data_ptr(),
                                                  w_s.data_ptr(), b_s.data_ptr(), mask.data_ptr(), h_out.data_ptr(),
@@ -638,8 +651,8 @@ def update_score(h, agg, W, b, w_s, b_s, mask, I: int, math: Optional[int] = Non
     mask = _chk(mask, "mask").reshape(-1)
     if w_s.numel() != D or b_s.numel() != 1 or mask.numel() != BN:
         raise ValueError("score_func / mask shapes do not match")
-    h_out = torch.empty_like(h)
-    score = torch.empty(BN, dtype=torch.float32, device=h.device)
+    h_out = _buf(h.shape, torch.float32, h.device, "update_score: h_out")
+    score = _buf(BN, torch.float32, h.device, "update_score: score")
     with torch.cuda.device(h.device):
         _lib.check(lib.gnnrag_update_score(h.data_ptr(), agg.data_ptr(), W.data_ptr(), b.data_ptr(),
                                            w_s.data_ptr(), b_s.data_ptr(), mask.data_ptr(), h_out.data_ptr(),
@@ -652,7 +665,7 @@ def masked_softmax(score: torch.Tensor, B: int, N: int) -> torch.Tensor:
     score = _chk(score, "score")
     if score.numel() != B * N:
         raise ValueError("score has %d entries, expected %d" % (score.numel(), B * N))
-    dist = torch.empty((B, N), dtype=torch.float32, device=score.device)
+    dist = _buf((B, N), torch.float32, score.device, "masked_softmax: dist")
     with torch.cuda.device(score.device):
         _lib.check(lib.gnnrag_masked_softmax(score.data_ptr(), dist.data_ptr(), B, N, _stream()),
                    "gnnrag_masked_softmax")
@@ -666,7 +679,7 @@ def typelayer(plan: CsrPlan, T: torch.Tensor, use_w_rel: bool) -> torch.Tensor:
     D = T.shape[1]
     if T.shape[0] != plan.R1:
         raise ValueError("T has %d rows, plan has R1=%d" % (T.shape[0], plan.R1))
-    h0 = torch.empty((plan.B * plan.N, D), dtype=torch.float32, device=T.device)
+    h0 = _buf((plan.B * plan.N, D), torch.float32, T.device, "typelayer: h0")
     ws = plan.walk_workspace(D, 1)
     with torch.cuda.device(T.device):
         _lib.check(lib.gnnrag_typelayer(C.byref(plan.c), T.data_ptr(), int(use_w_rel), h0.data_ptr(), D,
@@ -686,10 +699,10 @@ def aggregate_backward(plan: CsrPlan, dist, ins, T_fwd, T_inv, g_agg, gather: bo
     T_fwd = _chk(T_fwd, "T_fwd", shape=(plan.R1, D))
     T_inv = _chk(T_inv, "T_inv", shape=(plan.R1, D))
     g_agg = _chk(g_agg, "g_agg", shape=(B * N, 2 * I * D))
-    g_dist = torch.empty(B * N, dtype=torch.float32, device=dist.device)
-    g_ins = torch.empty_like(ins)
-    g_Tf = torch.empty_like(T_fwd)
-    g_Ti = torch.empty_like(T_inv)
+    g_dist = _buf(B * N, torch.float32, dist.device, "aggregate_backward: g_dist")
+    g_ins = _buf(ins.shape, torch.float32, ins.device, "aggregate_backward: g_ins")
+    g_Tf = _buf(T_fwd.shape, torch.float32, T_fwd.device, "aggregate_backward: g_T_fwd")
+    g_Ti = _buf(T_inv.shape, torch.float32, T_inv.device, "aggregate_backward: g_T_inv")
     ro = plan.relorder() if (gather and D % 4 == 0 and I <= 4) else None
     ws = plan.backward_workspace(D, I, ro)
     with torch.cuda.device(dist.device):
@@ -710,8 +723,8 @@ def aggregate_fused_backward(plan: CsrPlan, dist, P, g_nbr):
         raise ValueError("P must be [2, plan.rel_total, D] with D % 4 == 0")
     dist = _chk(dist, "dist").reshape(-1)
     g_nbr = _chk(g_nbr, "g_nbr", shape=(plan.B * plan.N, D))
-    g_dist = torch.empty(plan.B * plan.N, dtype=torch.float32, device=dist.device)
-    g_P = torch.zeros_like(P) if plan.rel_total == 0 else torch.empty_like(P)
+    g_dist = _buf(plan.B * plan.N, torch.float32, dist.device, "aggregate_fused_backward: g_dist")
+    g_P = _buf(P.shape, torch.float32, P.device, "aggregate_fused_backward: g_P", 0 if plan.rel_total == 0 else None)
     ro = plan.relorder()
     ws = plan.backward_workspace(D, 1, ro)
     with torch.cuda.device(dist.device):
@@ -729,7 +742,7 @@ def typelayer_backward(plan: CsrPlan, g_pre: torch.Tensor, use_w_rel: bool, gath
     D = g_pre.shape[1]
     if g_pre.shape[0] != plan.B * plan.N:
         raise ValueError("g_pre has %d rows, the plan %d nodes" % (g_pre.shape[0], plan.B * plan.N))
-    g_T = torch.empty((plan.R1, D), dtype=torch.float32, device=g_pre.device)
+    g_T = _buf((plan.R1, D), torch.float32, g_pre.device, "typelayer_backward: g_T")
     ro = plan.relorder() if (gather and D % 4 == 0) else None
     w_src = plan._w.get(("w_rel_src",)) if use_w_rel else None
     if use_w_rel and w_src is None:
@@ -753,7 +766,7 @@ class LayerWorkspace:
         nbytes = max(_lib.load().gnnrag_layer_workspace_bytes(C.byref(plan.c), D, I), 256)
         if self.key != str(device) or self.buf is None or self.buf.numel() < nbytes:
             self.buf = None                      # release the old buffer before taking the new one
-            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self.buf = _buf(nbytes, torch.uint8, device, "reason_layer: workspace")
             self.key = str(device)
         return self.buf
 
@@ -790,9 +803,9 @@ def reason_layer(plan: CsrPlan, h, dist, ins, relfeat, relfeat_inv, W_rel, b_rel
             raise ValueError("pos_emb must be [<=R1, D]")
     ws = ws or LayerWorkspace()
     wbuf = ws.get(plan, D, I, h.device)
-    h_out = torch.empty((B, N, D), dtype=torch.float32, device=h.device)
-    score = torch.empty((B, N), dtype=torch.float32, device=h.device)
-    dist_out = torch.empty((B, N), dtype=torch.float32, device=h.device)
+    h_out = _buf((B, N, D), torch.float32, h.device, "reason_layer: h_out")
+    score = _buf((B, N), torch.float32, h.device, "reason_layer: score")
+    dist_out = _buf((B, N), torch.float32, h.device, "reason_layer: dist_out")
     with torch.cuda.device(h.device):
         _lib.check(lib.gnnrag_reason_layer(
             C.byref(plan.c), h.data_ptr(), dist.data_ptr(), ins.data_ptr(), relfeat.data_ptr(),
@@ -849,7 +862,7 @@ class LayerStack:
         self.device = relfeat.device
         # the stack-sized workspace: relation projections of all L layers up front in one launch
         nbytes = max(lib.gnnrag_stack_workspace_bytes(C.byref(plan.c), self.L, D, self.I), 256)
-        self._ws_buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._ws_buf = _buf(nbytes, torch.uint8, self.device, "reason_stack: workspace")
         self._graph = self._graph_rest = None
         self.h = self.score = self.dist = None                   # graph mode: the fixed buffers of the captured sequence
         # the relation projections of the L layers depend on the parameters and the relation features only: the first
@@ -864,8 +877,8 @@ class LayerStack:
 
     def _new_outputs(self):
         f32, dev, L, B, N, D = torch.float32, self.device, self.L, self.B, self.N, self.D
-        return (torch.empty((L, B, N, D), dtype=f32, device=dev), torch.empty((L, B, N), dtype=f32, device=dev),
-                torch.empty((L, B, N), dtype=f32, device=dev))
+        return (_buf((L, B, N, D), f32, dev, "reason_stack: h_out"), _buf((L, B, N), f32, dev, "reason_stack: score"),
+                _buf((L, B, N), f32, dev, "reason_stack: dist_out"))
 
     def _args(self, h0, dist0, ins, out, reuse=False):
         h, score, dist = out
@@ -936,7 +949,7 @@ class LayerStack:
             raise RuntimeError("capture_rest() needs the projections of an eager run() in the workspace")
         self.release_graph()
         self.h, self.score, self.dist = self._new_outputs()
-        self._ins_buf = torch.empty((self.B, self.I, self.D), dtype=torch.float32, device=self.device)
+        self._ins_buf = _buf((self.B, self.I, self.D), torch.float32, self.device, "reason_stack_capture: ins")
         self.h[self.L - 1].copy_(h_prev.reshape(self.B, self.N, self.D))
         self._ins_buf.copy_(ins)
         h0g, dist0, insb = self._inputs(self.h[self.L - 1], dist0, self._ins_buf)
@@ -1008,16 +1021,16 @@ def lstm_forward(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, workspac
     h0 = None if h0 is None else _chk(h0, "h0", shape=(B, H))
     c0 = None if c0 is None else _chk(c0, "c0", shape=(B, H))
     dev = x.device
-    out = torch.empty((B, T, H), dtype=torch.float32, device=dev)
-    h_n = torch.empty((B, H), dtype=torch.float32, device=dev)
-    c_n = torch.empty((B, H), dtype=torch.float32, device=dev)
+    out = _buf((B, T, H), torch.float32, dev, "lstm_forward: out")
+    h_n = _buf((B, H), torch.float32, dev, "lstm_forward: h_n")
+    c_n = _buf((B, H), torch.float32, dev, "lstm_forward: c_n")
     need = lib.gnnrag_lstm_workspace_bytes(E, H)
     # one workspace per (device, stream): two calls on different streams of one device must not share the transposed-weight
     # scratch (calls on one stream are ordered)
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     ws = workspaces.get(key) if workspaces is not None else None
     if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _buf(need, torch.uint8, dev, "lstm_forward: workspace")
         if workspaces is not None:
             workspaces[key] = ws
     with torch.cuda.device(dev):
@@ -1036,7 +1049,7 @@ def seed_retrieve(seed_info: torch.Tensor, ent_emb: torch.Tensor) -> torch.Tenso
     if ent_emb.dim() != 3 or ent_emb.shape[0] != B or ent_emb.shape[1] != N:
         raise ValueError("ent_emb must be [B,N,D] matching seed_info [B,N]")
     D = ent_emb.shape[2]
-    out = torch.empty((B, D), dtype=torch.float32, device=ent_emb.device)
+    out = _buf((B, D), torch.float32, ent_emb.device, "seed_retrieve: out")
     with torch.cuda.device(ent_emb.device):
         _lib.check(lib.gnnrag_seed_retrieve(seed_info.data_ptr(), ent_emb.data_ptr(), out.data_ptr(), B, N, D,
                                             _stream()), "gnnrag_seed_retrieve")
@@ -1061,7 +1074,7 @@ def query_reform(q_node: torch.Tensor, seed_info: torch.Tensor, ent_emb: torch.T
         raise ValueError("query_reform: q_node [B,D], seed_info [B,N], ent_emb [B,N,>=D]")
     if tuple(W_r.shape) != (D, 3 * D) or tuple(W_g.shape) != (D, 3 * D):
         raise ValueError("query_reform: fusion weights must be [D, 3D]")
-    out = torch.empty((B, D), dtype=torch.float32, device=q_node.device)
+    out = _buf((B, D), torch.float32, q_node.device, "query_reform: out")
     with torch.cuda.device(q_node.device):
         _lib.check(lib.gnnrag_query_reform(q_node.data_ptr(), seed_info.data_ptr(), ent_emb.data_ptr(), ent_emb.shape[2],
                                            W_r.data_ptr(), W_g.data_ptr(), out.data_ptr(), B, N, D, _stream()),
@@ -1076,11 +1089,11 @@ def topp_candidates(pred_dist: torch.Tensor, eligible: torch.Tensor, ignore_prob
     pred_dist = _chk(pred_dist, "pred_dist")
     B, N = pred_dist.shape
     eligible = _chk(eligible, "eligible", dtype=torch.uint8, shape=(B, N))
-    slots = torch.empty((B, N), dtype=torch.int32, device=pred_dist.device)
-    cnt = torch.empty((B, 2), dtype=torch.int32, device=pred_dist.device)
+    slots = _buf((B, N), torch.int32, pred_dist.device, "topp_candidates_ws: slots")
+    cnt = _buf((B, 2), torch.int32, pred_dist.device, "topp_candidates_ws: counts")
     with torch.cuda.device(pred_dist.device):
         nws = lib.gnnrag_topp_workspace_bytes(B, N)          # > 0 for N > 16384: the survivors are sorted outside LDS
-        ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=pred_dist.device)
+        ws = _buf(max(nws, 16), torch.uint8, pred_dist.device, "topp_candidates_ws: workspace")
         _lib.check(lib.gnnrag_topp_candidates_ws(pred_dist.data_ptr(), eligible.data_ptr(), B, N, float(ignore_prob),
                                                  float(eps), slots.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(),
                                                  _stream()), "gnnrag_topp_candidates_ws")
@@ -1101,8 +1114,8 @@ class UGraph:
             sbytes = lib.gnnrag_ugraph_scratch_bytes(self.F, self.B, self.N)
             if nbytes == 0 or sbytes == 0:
                 raise ValueError("batch too large for the undirected adjacency (2 F and B * N must fit int32)")
-            self._mem = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            scratch = torch.empty(sbytes, dtype=torch.uint8, device=self.device)
+            self._mem = _buf(nbytes, torch.uint8, self.device, "ugraph_build: mem")
+            scratch = _buf(sbytes, torch.uint8, self.device, "ugraph_build: scratch")
             self.c = _lib.UGraphStruct()
             _lib.check(lib.gnnrag_ugraph_build(C.byref(plan.c), self._mem.data_ptr(), self._mem.numel(),
                                                scratch.data_ptr(), scratch.numel(), C.byref(self.c), _stream()),
@@ -1138,13 +1151,13 @@ class PathBuffers:
         nws = lib.gnnrag_paths_workspace_bytes(B, N, max_seeds, max_cands)
         if nws == 0:
             raise _lib.GnnragError("gnnrag_shortest_paths supports at most 65536 node slots per question (N = %d)" % N)
-        kw = dict(dtype=torch.int32, device=device)
-        self.q_info = torch.empty((B, 2), **kw)
-        self.pair_info = torch.empty((B, max_seeds, max_cands, 2), **kw)
-        self.path_off = torch.empty(P + 1, **kw)
-        self.path_nodes = torch.empty((P * max_paths, max_hops + 1), **kw)
-        self.path_facts = torch.empty((P * max_paths, max_hops), **kw)
-        self.ws = torch.empty(nws, dtype=torch.uint8, device=device)
+        i32 = torch.int32
+        self.q_info = _buf((B, 2), i32, device, "shortest_paths: q_info")
+        self.pair_info = _buf((B, max_seeds, max_cands, 2), i32, device, "shortest_paths: pair_info")
+        self.path_off = _buf(P + 1, i32, device, "shortest_paths: path_off")
+        self.path_nodes = _buf((P * max_paths, max_hops + 1), i32, device, "shortest_paths: path_nodes")
+        self.path_facts = _buf((P * max_paths, max_hops), i32, device, "shortest_paths: path_facts")
+        self.ws = _buf(nws, torch.uint8, device, "shortest_paths: workspace")
 
 
 _path_buffers = {}

@@ -17,6 +17,12 @@
  *    the only process-wide data are idempotent per-device caches of launch attributes (raised
  *    dynamic-LDS caps, CU counts), keyed by the device current at the call, so one process may
  *    drive several GPUs.
+ *  - buffers: every output is written at exactly the stated shape and every workspace / structure memory / scratch
+ *    block within the bytes its gnnrag_*_bytes function states - nothing in front of or behind them is read into a
+ *    result or written, and no result depends on what an output or a workspace held before the call (outputs are
+ *    fully written unless an entry point says that it updates listed rows only).  A byte count below the stated size
+ *    is refused with GNNRAG_E_WORKSPACE before anything is launched, also where the kernel form a particular call
+ *    takes would get by with less.  tests/test_gpu_guarded.py holds every entry point to this.
  *  - fp32 values, int32 indices, row-major contiguous.
  *  - return value: 0 = success; > 0 = hipError_t of a failed runtime call / launch;
  *    < 0 = GNNRAG_E_* argument error.  gnnrag_error_string() renders either.
@@ -217,7 +223,9 @@ int gnnrag_aggregate_fused_variant(const gnnrag_csr* csr, int32_t D);
  * workspace (the sizes of the hub-by-relation weight blocks live on the device, so the kernels decide; this entry runs
  * the same predicate on the same kernel arguments in a one-thread launch).  form_dev: 4 device int32 -
  * [0] GNNRAG_HUB_FORM_*, [1] / [2] hub rows of direction 0 / 1, [3] relation ranges per question.  Diagnostics for
- * tests and bench.py ("which kernel ran"); nothing on the product path calls it. */
+ * tests and bench.py ("which kernel ran"); nothing on the product path calls it.  No size is stated for `workspace`:
+ * pass what the gnnrag_aggregate_fused call in question gets (the answer depends on it); less than the walk's partial
+ * sums need is GNNRAG_E_WORKSPACE. */
 #define GNNRAG_HUB_FORM_NONE    0  /* the call has no dense hub kernels (LDS walk, or the form is switched off)   */
 #define GNNRAG_HUB_FORM_DENSE   1  /* k_hub_weights / k_hub_dense / k_hub_finish                                   */
 #define GNNRAG_HUB_FORM_CHUNKED 2  /* weight blocks do not fit the workspace: k_heavy_partial / k_heavy_reduce     */
@@ -288,7 +296,9 @@ int gnnrag_aggregate_backward(const gnnrag_csr* csr, const gnnrag_relorder* relo
  *   g_dist[s]        = sum_d sum_{f: src_d(f)=s} w_f * < g_nbr[dst_d(f), :], P[d, row(b, rel_f), :] >
  *   g_P[d, row, :]   = sum_{f in row} w_f * dist[src_d(f)] * g_nbr[dst_d(f), :]
  * both fully written; the relation tables P themselves are a differentiable dense expression of a few ten thousand
- * rows on the caller's side (gnn-rag_amd/autograd.py: relation_tables_dense).  Needs the (question, relation) ordering
+ * rows on the caller's side (gnn-rag_amd/autograd.py: relation_tables_dense).  P and g_P must be real pointers also for
+ * a batch without facts (rel_total == 0: nothing is read or written there; NULL is GNNRAG_E_BADARG, as for
+ * gnnrag_aggregate_fused).  Needs the (question, relation) ordering
  * (gnnrag_relorder) and D % 4 == 0; gather kernels, chunk partials summed in a fixed order, no atomics.
  * workspace: gnnrag_backward_workspace_bytes(csr, relorder, D, 1). */
 int gnnrag_aggregate_fused_backward(const gnnrag_csr* csr, const gnnrag_relorder* relorder, const float* dist,
