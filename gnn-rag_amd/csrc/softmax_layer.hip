@@ -2,16 +2,6 @@
 #include "gnnrag_common.h"
 #include "dense_internal.h"
 
-#include <map>
-#include <vector>
-
-#ifndef GNNRAG_OVERLAP_TABLES_DEFAULT
-#define GNNRAG_OVERLAP_TABLES_DEFAULT 0
-#endif
-#ifndef GNNRAG_OVERLAP_PROJ_DEFAULT
-#define GNNRAG_OVERLAP_PROJ_DEFAULT 0
-#endif
-
 namespace gnnrag {
 
 // dist[g,:] = softmax(score[g,:])  (reasongnn.py:169).  One 1024-thread workgroup per question.
@@ -234,52 +224,12 @@ static LayerWs layer_ws(const gnnrag_csr* csr, int32_t D, int32_t I) {
   return w;
 }
 
-// ---- the stack driver's side stream (relation tables of layers 1.. under the layers in front of them) ---------------
-// P of layer j >= 1 depends on the relation planes, the instructions and e2e_linear{j}.weight only - on nothing the
-// layers 0 .. j-1 compute.  With GNNRAG_OVERLAP_TABLES (default: see overlap_enabled) the whole-iteration call forks a
-// side stream behind its relation projections, runs the L - 1 table launches there into L - 1 table buffers of their
-// own, and the caller's stream waits for layer j's tables right before layer j's walk: the MFMA-bound table kernel runs
-// beside the issue-bound walk / the latency-bound frontier launches of the layers in front of it.  Same kernels'
-// arithmetic in the same order per output element: results are bit-identical to the serial sequence.
-// Stream and events are cached per host thread and device (an event shared by two host threads could hand one thread's
-// wait the other thread's record).
-struct OverlapRes {
-  hipStream_t side = nullptr;
-  hipEvent_t fork = nullptr;
-  std::vector<hipEvent_t> done;
-};
-
-static int overlap_res(int n_done, OverlapRes** out) {
-  static thread_local std::map<int, OverlapRes> per_device;
-  int dev = 0;
-  GNNRAG_HIP(hipGetDevice(&dev));
-  OverlapRes& r = per_device[dev];
-  if (!r.side) {
-    GNNRAG_HIP(hipStreamCreateWithFlags(&r.side, hipStreamNonBlocking));
-    GNNRAG_HIP(hipEventCreateWithFlags(&r.fork, hipEventDisableTiming));
-  }
-  while ((int)r.done.size() < n_done) {
-    hipEvent_t e = nullptr;
-    GNNRAG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    r.done.push_back(e);
-  }
-  *out = &r;
-  return 0;
-}
-
-static bool overlap_enabled() {
-  const char* env = getenv("GNNRAG_OVERLAP_TABLES");      // read per call: tests compare both forms in one process
-  return env ? env[0] != '0' : GNNRAG_OVERLAP_TABLES_DEFAULT != 0;
-}
-
-// shapes for which the side-stream form exists: the V-form table kernel's (planes) and the LDS walk behind it
-static bool overlap_shape_ok(const gnnrag_csr* csr, int32_t L, int32_t D, int32_t I) {
-  return L > 1 && tables_vq_shape_ok(D, I) && csr->rel_total >= 1024 &&
-         gnnrag_aggregate_fused_variant(csr, D) != GNNRAG_WALK_L2_GATHER;
-}
-
-static size_t overlap_p_bytes(const gnnrag_csr* csr, int32_t D) {
-  return align_up((size_t)2 * (csr->rel_total > 0 ? csr->rel_total : 1) * D * sizeof(float), 256);
+// whether a layer call should have the relation projections written as bf16 planes too: they are only worth writing when
+// the fused path (asked for, or chosen by GNNRAG_PATH_AUTO) with a bf16x3 product will read them in the V-form table kernel
+static bool planes_wanted(const gnnrag_csr* csr, int32_t D, int32_t I, int32_t path, int32_t math) {
+  const bool fused = (path & 0xf) == GNNRAG_PATH_FUSED ||
+                     ((path & 0xf) == GNNRAG_PATH_AUTO && fused_is_cheaper(csr->B, csr->N, csr->rel_total, D, I));
+  return fused && math != GNNRAG_MATH_FP32 && tables_vq_shape_ok(D, I) && csr->rel_total >= 1024;
 }
 
 }  // namespace gnnrag
@@ -346,13 +296,7 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
                       const float* ins, const float* T_fwd, const float* T_inv, const void* planes, const float* W_e2e,
                       const float* b_e2e, const float* w_score, const float* b_score, const float* mask,
                       float* h_out, float* score_out, float* dist_out, int32_t D, int32_t I, int32_t path,
-                      int32_t math, gnnrag_stream_t stream, bool pairs_ready = false, bool* pairs_for_next = nullptr,
-                      float* P_done = nullptr, hipEvent_t t_ready = nullptr) {
-  // t_ready != nullptr: the relation projections (T, planes) are being computed on the stack driver's side stream; the
-  // caller's stream waits for them in front of the first launch that reads them - behind the frontier build in the
-  // seed-prior form (which reads only the prior and the structure), at the top otherwise
-  // P_done != nullptr: this layer's relation tables were already computed into P_done (and its score buffer zeroed) by
-  // the stack driver's side stream, and the caller's stream has waited for them - the table launch is skipped
+                      int32_t math, gnnrag_stream_t stream, bool pairs_ready = false, bool* pairs_for_next = nullptr) {
   // pairs_ready: the previous layer's softmax launch left this layer's (prior, relation) pairs in the workspace;
   // pairs_for_next != nullptr: the caller will run another layer on dist_out - *pairs_for_next reports whether this
   // layer's last launch wrote that layer's pairs
@@ -368,7 +312,7 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
   if (path == GNNRAG_PATH_AUTO)
     path = fused_is_cheaper(csr->B, csr->N, csr->rel_total, D, I) ? GNNRAG_PATH_FUSED : GNNRAG_PATH_UNFUSED;
   if (path == GNNRAG_PATH_FUSED) {
-    float* P = P_done ? P_done : (float*)(base + w.P);
+    float* P = (float*)(base + w.P);
     float* nbr = (float*)(base + w.nbr);
     const bool one_dir = only >= 0 && gnnrag_aggregate_fused_variant(csr, D) != GNNRAG_WALK_L2_GATHER;
     // the frontier kernels issue 16-byte loads / stores on ins, W, T, P (workspace) and the node rows: a misaligned view
@@ -376,7 +320,6 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     const bool fr_aligned = ((((uintptr_t)ins | (uintptr_t)W_e2e | (uintptr_t)T_fwd | (uintptr_t)T_inv | (uintptr_t)P |
                                (uintptr_t)nbr | (uintptr_t)dist) & 15) == 0) && csr->N > 0;
     const bool frontier_form = seed_prior && only < 0 && fr_aligned && gnnrag_frontier_supported(csr, D) && csr->rel_total > 0;
-    if (t_ready && !frontier_form) GNNRAG_HIP(hipStreamWaitEvent((hipStream_t)stream, t_ready, 0));
     if (frontier_form) {
       // The caller says `dist` is a seed distribution (first layer of a ReaRev iteration, rearev.py:208): only the
       // seeds' facts have a prior, so only the relation-table rows those facts use and the neighbour sums of the nodes
@@ -386,7 +329,6 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
       const bool gated = update_rows_supported(h, nbr, W_e2e, h_out, BN, D, I, math);
       if (!gated) GNNRAG_HIP(hipMemsetAsync(nbr, 0, (size_t)BN * D * sizeof(float), (hipStream_t)stream));
       rc = frontier_build_z(csr, dist, fws, w.fws_bytes, score_out, BN, nbr + (size_t)BN * D, D, (hipStream_t)stream);
-      if (t_ready) GNNRAG_HIP(hipStreamWaitEvent((hipStream_t)stream, t_ready, 0));     // (also joins after an error)
       if (rc) return rc;
       rc = gnnrag_relation_tables_frontier(csr, fws, T_fwd, T_inv, ins, W_e2e, P, D, I, stream);
       if (rc) return rc;
@@ -399,13 +341,8 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     }
     rc = GNNRAG_E_UNSUPPORTED;
     bool score_zeroed = false;    // the V-form table kernel also zeroes the score the update accumulates onto
-    if (P_done) {
-      rc = 0;
-      score_zeroed = true;
-    } else if (planes && math != GNNRAG_MATH_FP32 && csr->rel_total > 0) {
-      const char* menv = getenv("GNNRAG_TABLES_LITE_MAIN");      // experiment knob: the side-stream kernel in the serial sequence
-      rc = ((menv && menv[0] == '1') ? tables_vq_lite_launch_z : tables_vq_launch_z)(
-          csr, planes, ins, W_e2e, P, D, I, one_dir ? only : -1, score_out, BN, (hipStream_t)stream);
+    if (planes && math != GNNRAG_MATH_FP32 && csr->rel_total > 0) {
+      rc = tables_vq_launch_z(csr, planes, ins, W_e2e, P, D, I, one_dir ? only : -1, score_out, BN, (hipStream_t)stream);
       score_zeroed = rc == 0;
     }
     if (rc == GNNRAG_E_UNSUPPORTED) rc = gnnrag_relation_tables(csr, T_fwd, T_inv, ins, W_e2e, P, D, I, math, stream);
@@ -418,7 +355,6 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     if (rc) return rc;
     return finish_softmax(csr, w, base, score_out, dist_out, D, only < 0, pairs_for_next, stream);
   } else {
-    if (t_ready) GNNRAG_HIP(hipStreamWaitEvent((hipStream_t)stream, t_ready, 0));
     float* agg = (float*)(base + w.agg);
     rc = gnnrag_aggregate(csr, dist, ins, T_fwd, T_inv, agg, D, I, base + w.partial, w.partial_bytes, stream);
     if (rc) return rc;
@@ -456,11 +392,8 @@ extern "C" size_t gnnrag_stack_workspace_bytes(const gnnrag_csr* csr, int32_t L,
   if (!csr || L <= 0 || D <= 0 || I <= 0) return 0;
   // one layer's workspace + the relation projections of all L layers (one contiguous block, computed up front)
   // + their bf16 planes where the V-form tables kernel applies
-  // + L - 1 relation-table buffers where the side-stream form applies (layer j's tables are computed while layer j - 1
-  // still reads its own)
   return layer_ws(csr, D, I).total + align_up((size_t)L * 2 * csr->R1 * D * sizeof(float), 256) +
-         align_up(tables_vq_shape_ok(D, I) ? (size_t)L * tables_vq_planes_bytes(csr->R1) : 0, 256) +
-         (overlap_shape_ok(csr, L, D, I) ? (size_t)(L - 1) * overlap_p_bytes(csr, D) : 0);
+         align_up(tables_vq_shape_ok(D, I) ? (size_t)L * tables_vq_planes_bytes(csr->R1) : 0, 256);
 }
 
 extern "C" int gnnrag_reason_layer(const gnnrag_csr* csr, const float* h, const float* dist, const float* ins,
@@ -481,11 +414,7 @@ extern "C" int gnnrag_reason_layer(const gnnrag_csr* csr, const float* h, const 
   float* T_fwd = (float*)(base + w.T_fwd);
   float* T_inv = (float*)(base + w.T_inv);
   const gnnrag_layer_params p = {W_rel, b_rel, pos_fwd, pos_inv, W_e2e, b_e2e};
-  // the planes are only worth writing when the fused path with a bf16x3 product will read them
-  const bool fused = (path & 0xf) == GNNRAG_PATH_FUSED ||
-                     ((path & 0xf) == GNNRAG_PATH_AUTO && fused_is_cheaper(csr->B, csr->N, csr->rel_total, D, I));
-  void* planes = fused && math != GNNRAG_MATH_FP32 && tables_vq_shape_ok(D, I) && csr->rel_total >= 1024
-                     ? (void*)(base + w.planes) : nullptr;
+  void* planes = planes_wanted(csr, D, I, path, math) ? (void*)(base + w.planes) : nullptr;
   bool planes_written = false;
   const int rc = rel_projections(csr, 1, &p, relfeat_fwd, relfeat_inv, pos_rows, T_fwd, planes, &planes_written, D, math,
                                  stream);
@@ -495,6 +424,10 @@ extern "C" int gnnrag_reason_layer(const gnnrag_csr* csr, const float* h, const 
                     dist_out, D, I, path, math, stream);
 }
 
+// Argument checks, the relation projections of all layers up front where the workspace has room for them, then the
+// layers in order.  Everything is enqueued on `stream` and nothing else: no stream or event is created, recorded or
+// waited for here or below, so gnnrag_reason_stack_capture captures a single-stream sequence and every early error
+// return leaves a capture in a state that can be ended.
 extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnrag_layer_params* layers,
                                    const float* h0, const float* dist0, const float* ins,
                                    const float* relfeat_fwd, const float* relfeat_inv, int32_t pos_rows,
@@ -518,13 +451,10 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
   const bool upfront = L > 1 && workspace_bytes >= gnnrag_stack_workspace_bytes(csr, L, D, I);
   float* T0 = (float*)(base + w.T_fwd);
   float* Tall = (float*)(base + w.total);
-  const bool fused = (path & 0xf) == GNNRAG_PATH_FUSED ||
-                     ((path & 0xf) == GNNRAG_PATH_AUTO && fused_is_cheaper(csr->B, csr->N, csr->rel_total, D, I));
-  const bool want_planes = fused && math != GNNRAG_MATH_FP32 && tables_vq_shape_ok(D, I) && csr->rel_total >= 1024;
+  const bool want_planes = planes_wanted(csr, D, I, path, math);
   const size_t plane_bytes = tables_vq_planes_bytes(csr->R1);
   char* planes_all = base + w.total + align_up((size_t)L * 2 * RD * sizeof(float), 256);
   bool planes_written = false;
-  hipEvent_t t_ready = nullptr;      // set while the relation projections run on the side stream (layer 0 joins them)
   const bool reuse = upfront && (path & GNNRAG_PATH_REUSE_PROJ) != 0;
   path &= ~GNNRAG_PATH_REUSE_PROJ;
   if (reuse) {
@@ -533,68 +463,9 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
     planes_written = want_planes && rel_transform_accepts(relfeat_fwd, relfeat_inv, csr->R1, D, L, layers, pos_rows, Tall,
                                                           planes_all);
   } else if (upfront) {
-    // GNNRAG_OVERLAP_PROJ (default: GNNRAG_OVERLAP_PROJ_DEFAULT): the projections on the side stream, so that layer 0's
-    // frontier build - which reads only the prior and the structure - runs beside them instead of behind them
-    const char* penv = getenv("GNNRAG_OVERLAP_PROJ");
-    const bool proj_side = fused && (path & GNNRAG_PATH_SEED_PRIOR) && (penv ? penv[0] != '0' : GNNRAG_OVERLAP_PROJ_DEFAULT != 0);
-    OverlapRes* pr = nullptr;
-    if (proj_side) {
-      const int rc0 = overlap_res(L, &pr);
-      if (rc0) return rc0;
-      GNNRAG_HIP(hipEventRecord(pr->fork, (hipStream_t)stream));
-      GNNRAG_HIP(hipStreamWaitEvent(pr->side, pr->fork, 0));
-    }
     const int rc = rel_projections(csr, L, layers, relfeat_fwd, relfeat_inv, pos_rows, Tall,
-                                   want_planes ? planes_all : nullptr, &planes_written, D, math,
-                                   proj_side ? (gnnrag_stream_t)pr->side : stream);
-    if (proj_side) {
-      GNNRAG_HIP(hipEventRecord(pr->done[0], pr->side));
-      if (rc) (void)hipStreamWaitEvent((hipStream_t)stream, pr->done[0], 0);
-      else t_ready = pr->done[0];
-    }
+                                   want_planes ? planes_all : nullptr, &planes_written, D, math, stream);
     if (rc) return rc;
-  }
-  // side-stream tables (see OverlapRes): only in the full-workspace form with the planes in place, both directions
-  const bool overlap = upfront && want_planes && planes_written && fused && (path & ~0xf & ~GNNRAG_PATH_SEED_PRIOR) == 0 &&
-                       overlap_shape_ok(csr, L, D, I) && overlap_enabled() &&
-                       ((((uintptr_t)ins | (uintptr_t)planes_all) & 15) == 0);
-  OverlapRes* ov = nullptr;
-  char* P_extra = planes_all + align_up(tables_vq_shape_ok(D, I) ? (size_t)L * plane_bytes : 0, 256);
-  const size_t p_bytes = overlap_p_bytes(csr, D);
-  bool side_ok[64] = {false};
-  // gate (GNNRAG_OVERLAP_GATE, default on): layer j + 1's tables are not enqueued at the fork but right in front of layer
-  // j's walk, so that they run BESIDE that walk (complementary pipes) instead of competing with layer j - 1's update for CUs
-  const char* genv = getenv("GNNRAG_OVERLAP_GATE");
-  const bool gate = !(genv && genv[0] == '0');
-  const char* lenv = getenv("GNNRAG_TABLES_LITE");           // 0: the side stream launches k_tables_vq itself (A/B)
-  const bool lite = !(lenv && lenv[0] == '0');
-  auto side_tables = [&](int j) -> int {                     // layer j's tables on the side stream
-    if (j >= 64 || (((uintptr_t)layers[j].W_e2e) & 15) != 0) return 0;
-    const int rc = (lite ? tables_vq_lite_launch_z : tables_vq_launch_z)(
-        csr, planes_all + (size_t)j * plane_bytes, ins, layers[j].W_e2e, (float*)(P_extra + (size_t)(j - 1) * p_bytes), D, I, -1,
-        score_out + (size_t)j * BN, (int64_t)BN, ov->side);
-    if (rc == GNNRAG_E_UNSUPPORTED) return 0;
-    if (rc) return rc;
-    side_ok[j] = true;
-    GNNRAG_HIP(hipEventRecord(ov->done[j], ov->side));
-    return 0;
-  };
-  auto side_join_all = [&](int from) {       // whatever happened: a forked side stream is joined again (captures!)
-    if (!ov) return;
-    (void)hipEventRecord(ov->done[0], ov->side);
-    (void)hipStreamWaitEvent((hipStream_t)stream, ov->done[0], 0);
-    (void)from;
-  };
-  if (overlap && L <= 64) {
-    { const int rc = overlap_res(L, &ov); if (rc) return rc; }
-    GNNRAG_HIP(hipEventRecord(ov->fork, (hipStream_t)stream));
-    GNNRAG_HIP(hipStreamWaitEvent(ov->side, ov->fork, 0));
-    int rc_side = 0;
-    for (int j = 1; j < (gate ? 2 : L) && !rc_side; ++j) rc_side = side_tables(j);
-    if (rc_side) {
-      side_join_all(0);
-      return rc_side;
-    }
   }
   const float* h = h0;
   const float* dist = dist0;
@@ -614,29 +485,10 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
     if (!planes_written) planes = nullptr;
     // GNNRAG_PATH_SEED_PRIOR describes dist0, i.e. layer 0 only (every later layer starts from a softmax output)
     bool pairs_next = false;
-    float* P_done = nullptr;
-    if (ov && j < 64 && side_ok[j]) {
-      GNNRAG_HIP(hipStreamWaitEvent((hipStream_t)stream, ov->done[j], 0));     // joins the side stream up to layer j's tables
-      P_done = (float*)(P_extra + (size_t)(j - 1) * p_bytes);
-    }
-    if (ov && gate && j >= 1 && j + 1 < L) {
-      // layer j + 1's tables start where layer j's walk starts
-      GNNRAG_HIP(hipEventRecord(ov->fork, (hipStream_t)stream));
-      GNNRAG_HIP(hipStreamWaitEvent(ov->side, ov->fork, 0));
-      const int rc_side = side_tables(j + 1);
-      if (rc_side) {
-        side_join_all(j);
-        return rc_side;
-      }
-    }
     const int rc = layer_body(csr, w, base, h, dist, ins, T, T + RD, planes, p.W_e2e, p.b_e2e, w_score, b_score, mask, hj, sj,
                               dj, D, I, j == 0 ? path : (path & ~GNNRAG_PATH_SEED_PRIOR), math, stream, pairs_ready,
-                              j + 1 < L ? &pairs_next : nullptr, P_done, j == 0 ? t_ready : nullptr);
-    if (rc) {
-      if (j == 0 && t_ready) (void)hipStreamWaitEvent((hipStream_t)stream, t_ready, 0);
-      side_join_all(j);       // join what is still outstanding on the side stream before reporting the error
-      return rc;
-    }
+                              j + 1 < L ? &pairs_next : nullptr);
+    if (rc) return rc;
     pairs_ready = pairs_next;
     h = hj;
     dist = dj;

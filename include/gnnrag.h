@@ -399,8 +399,10 @@ typedef struct gnnrag_layer_params {
   const float* b_e2e;    /* e2e_linear{j}.bias [D]                           */
 } gnnrag_layer_params;
 /* Workspace of gnnrag_reason_stack that lets it compute the relation projections of all L layers up front in ONE
- * launch (gnnrag_layer_workspace_bytes + an [L][2][R1][D] block).  With only gnnrag_layer_workspace_bytes the stack
- * call still works and projects per layer (same results bit for bit). */
+ * launch.  The size is gnnrag_layer_workspace_bytes + an [L][2][R1][D] fp32 block for the projections + L layers' bf16
+ * planes of them where the V-form relation-table kernel applies to (D, I), the two additions each rounded up to 256
+ * bytes - and nothing else.  A larger workspace is accepted.  With only gnnrag_layer_workspace_bytes the stack call
+ * still works and projects per layer (same results bit for bit). */
 size_t gnnrag_stack_workspace_bytes(const gnnrag_csr* csr, int32_t L, int32_t D, int32_t I);
 
 /* T_out[j][d][r, :] = rel_linear{j}(rel_features_d[r, :]) (+ pos_emb{j}_d[r, :] for r < pos_rows), j < L, d = 0

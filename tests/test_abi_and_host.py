@@ -62,6 +62,9 @@ def test_size_queries_and_struct_layout(lib):
     assert planes == 3 * 2 * 3 * 602 * 448 * 2
     assert lib.gnnrag_stack_workspace_bytes(ctypes.byref(c), 3, 200, 2) >= ws + 3 * 2 * 602 * 200 * 4 + planes
     assert lib.gnnrag_stack_workspace_bytes(ctypes.byref(c), 3, 64, 2) >= lib.gnnrag_layer_workspace_bytes(ctypes.byref(c), 64, 2) + 3 * 2 * 602 * 64 * 4
+    # ... and nothing else: each of the two blocks is rounded up to 256 bytes, hence at most 512 bytes above their sum
+    assert lib.gnnrag_stack_workspace_bytes(ctypes.byref(c), 3, 200, 2) <= ws + 3 * 2 * 602 * 200 * 4 + planes + 512
+    assert lib.gnnrag_stack_workspace_bytes(ctypes.byref(c), 3, 64, 2) <= lib.gnnrag_layer_workspace_bytes(ctypes.byref(c), 64, 2) + 3 * 2 * 602 * 64 * 4 + 512
     assert lib.gnnrag_rel_planes_bytes(602, 300, 3) == 0 and lib.gnnrag_stack_workspace_bytes(None, 3, 200, 2) == 0
     # weight-gradient GEMM: partial blocks of [N1, N2] per row chunk
     tn = lib.gnnrag_gemm_tn_workspace_bytes(128000, 200, 200)

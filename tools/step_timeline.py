@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Kernel timeline of bench steps from a rocprofv3 rocpd database (``--kernel-trace``): start / end / duration of every
 launch of one step in the middle of the timed loop, relative to the step's first launch, with the hardware queue it ran
-on - what overlaps what when the whole-iteration call forks its side stream.
+on - what overlaps what whenever work is enqueued on more than one stream (as in the experiment of DESIGN.md section 5.7).
 Usage: python tools/step_timeline.py results.db [step index, default: the middle one] [steps to print, default 1]"""
 import re
 import sqlite3
