@@ -139,6 +139,10 @@ SIGNATURES = {
     "gnnrag_paths_out_bytes": (C.c_size_t, [C.c_int32] * 5),
     "gnnrag_shortest_paths": (C.c_int, [C.POINTER(UGraphStruct), _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_rule_paths_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
+    "gnnrag_rule_paths_out_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "gnnrag_rule_paths": (C.c_int, [C.POINTER(UGraphStruct), _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
     "gnnrag_stream_copy": (C.c_int, [_VP, _VP, C.c_int64, _VP]),
     "gnnrag_abi_version": (C.c_int, []),
     "gnnrag_error_string": (C.c_char_p, [C.c_int]),

@@ -1196,6 +1196,67 @@ def shortest_paths(graph: "UGraph", seed_flag: torch.Tensor, cand_slot: torch.Te
     return buffers
 
 
+class RulePathBuffers:
+    """Worst-case output arrays and the workspace of ``gnnrag_rule_paths`` for one ``(F, B, N, limits)``."""
+
+    def __init__(self, F, B, N, max_seeds, max_rules, max_paths, max_hops, device):
+        lib = _lib.load()
+        self.key = (int(F), int(B), int(N), int(max_seeds), int(max_rules), int(max_paths), int(max_hops),
+                    torch.device(device))
+        P = B * max_seeds * max_rules
+        if lib.gnnrag_rule_paths_out_bytes(B, max_seeds, max_rules, max_paths, max_hops) == 0:
+            raise ValueError("rule path limits out of range (positive sizes, max_hops <= 254, pairs * max_paths < 2^31)")
+        nws = lib.gnnrag_rule_paths_workspace_bytes(F, B, N, max_rules, max_hops)
+        if nws == 0:
+            raise _lib.GnnragError("gnnrag_rule_paths supports at most 65536 node slots per question (N = %d)" % N)
+        i32 = torch.int32
+        self.q_info = _buf((B, 2), i32, device, "rule_paths: q_info")
+        self.pair_info = _buf((B, max_seeds, max_rules, 2), i32, device, "rule_paths: pair_info")
+        self.path_off = _buf(P + 1, i32, device, "rule_paths: path_off")
+        self.path_nodes = _buf((P * max_paths, max_hops + 1), i32, device, "rule_paths: path_nodes")
+        self.path_facts = _buf((P * max_paths, max_hops), i32, device, "rule_paths: path_facts")
+        self.ws = _buf(nws, torch.uint8, device, "rule_paths: workspace")
+
+
+_rule_path_buffers = {}
+
+
+def rule_paths(graph: "UGraph", fact_rel: torch.Tensor, seed_flag: torch.Tensor, rule_rel: torch.Tensor,
+               rule_len: torch.Tensor, max_seeds: int = 4, max_rules: int = 8, max_paths: int = 64, max_hops: int = 4,
+               buffers: Optional["RulePathBuffers"] = None) -> "RulePathBuffers":
+    """Every walk from a seed that follows a rule hop by hop (``gnnrag_rule_paths``; the reference's ``bfs_with_rule``,
+    ``llm/src/utils/graph_utils.py:24-47``).  ``fact_rel`` [F] int32: the relation id of every fact of the batch tuple;
+    ``rule_rel`` [B, max_rules, max_hops] / ``rule_len`` [B, max_rules] int32: the rules of every question (a length
+    outside ``[1, max_hops]`` is an empty slot).  Nothing waits for the stream; the result is the
+    :class:`RulePathBuffers` holding the device arrays (one set per shape and limits is kept and reused when ``buffers``
+    is not given: copy what you keep before the next call)."""
+    lib = _lib.load()
+    B, N, F = graph.B, graph.N, graph.F
+    fact_rel = _chk(fact_rel, "fact_rel", dtype=torch.int32, shape=(F,))
+    seed_flag = _chk(seed_flag, "seed_flag", dtype=torch.uint8, shape=(B, N))
+    rule_rel = _chk(rule_rel, "rule_rel", dtype=torch.int32, shape=(B, max_rules, max_hops))
+    rule_len = _chk(rule_len, "rule_len", dtype=torch.int32, shape=(B, max_rules))
+    for name, t in (("fact_rel", fact_rel), ("seed_flag", seed_flag), ("rule_rel", rule_rel), ("rule_len", rule_len)):
+        if t.device != graph.device:
+            raise _lib.GnnragError("%s lives on %s but the graph was built on %s" % (name, t.device, graph.device))
+    key = (F, B, N, int(max_seeds), int(max_rules), int(max_paths), int(max_hops), graph.device)
+    with torch.cuda.device(graph.device):
+        if buffers is None:
+            buffers = _rule_path_buffers.get(key)
+            if buffers is None:
+                _rule_path_buffers.clear()          # one set at a time: the worst case is large
+                buffers = _rule_path_buffers[key] = RulePathBuffers(*key)
+        elif buffers.key != key:
+            raise ValueError("buffers were made for %s, the call needs %s" % (buffers.key, key))
+        o = buffers
+        _lib.check(lib.gnnrag_rule_paths(C.byref(graph.c), fact_rel.data_ptr(), seed_flag.data_ptr(), rule_rel.data_ptr(),
+                                         rule_len.data_ptr(), max_seeds, max_rules, max_paths, max_hops,
+                                         o.q_info.data_ptr(), o.pair_info.data_ptr(), o.path_off.data_ptr(),
+                                         o.path_nodes.data_ptr(), o.path_facts.data_ptr(), o.ws.data_ptr(),
+                                         o.ws.numel(), _stream()), "gnnrag_rule_paths")
+    return buffers
+
+
 def stream_copy(src: torch.Tensor, dst: torch.Tensor):
     lib = _lib.load()
     with torch.cuda.device(src.device):

@@ -13,6 +13,10 @@ enqueued on one stream, and ONE synchronising readback brings back the paths tha
     for pair in per_question[0]:
         for path in pair["paths"]:
             print(path_to_string(path))
+
+The reference's other path set, the walks that follow a predicted relation path ("rule") from a question entity
+(``bfs_with_rule``, called by ``apply_rules`` of ``build_qa_input.py``), comes from :func:`retrieve_rule_paths` on the
+same adjacency, and :func:`reasoning_context` joins the two the way ``PromptBuilder.process_input`` does (GNN-RAG+RA).
 """
 from __future__ import annotations
 
@@ -24,6 +28,8 @@ from . import _lib, ops
 # what the last retrieve_paths call copied back (tests assert the readback is O(paths written)): bytes of the two
 # small fixed blocks and of the record prefix, and the number of records
 LAST_READBACK = {"fixed_bytes": 0, "record_bytes": 0, "records": 0}
+# the same for the last retrieve_rule_paths call
+LAST_RULE_READBACK = {"fixed_bytes": 0, "record_bytes": 0, "records": 0}
 
 
 def path_to_string(path) -> str:
@@ -109,3 +115,92 @@ def retrieve_paths(plan_or_ugraph, rels, pred_dist: torch.Tensor, local_entity, 
                               "n_paths": int(pair_info[b, si, ci, 0]), "hops": h, "paths": paths})
         result.append(pairs)
     return (result, q_info.copy()) if return_info else result
+
+
+def _pack_rules(rules, B, relation2id, max_rules, max_hops):
+    """rules[b] = list of relation-id lists (or name lists through ``relation2id``) -> (rule_rel [B,R,H], rule_len [B,R])."""
+    if len(rules) != B:
+        raise ValueError("rules must hold one list per question (%d), got %d" % (B, len(rules)))
+    rule_rel = np.full((B, max_rules, max_hops), -1, dtype=np.int32)
+    rule_len = np.zeros((B, max_rules), dtype=np.int32)
+    for b, rs in enumerate(rules):
+        if len(rs) > max_rules:
+            raise ValueError("question %d has %d rules, max_rules is %d" % (b, len(rs), max_rules))
+        for k, rule in enumerate(rs):
+            if len(rule) > max_hops:
+                raise ValueError("rule %d of question %d has %d hops, max_hops is %d" % (k, b, len(rule), max_hops))
+            ids = [int(relation2id.get(x, -1)) if relation2id is not None else int(x) for x in rule]
+            rule_rel[b, k, : len(ids)] = ids
+            rule_len[b, k] = len(ids)
+    return rule_rel, rule_len
+
+
+def retrieve_rule_paths(plan_or_ugraph, rels, local_entity, query_entities, rules, relation2id=None, max_seeds: int = 4,
+                        max_rules: int = 8, max_paths: int = 64, max_hops: int = 4, id2entity=None, id2relation=None,
+                        return_info: bool = False):
+    """Per question the list ``[{"seed", "seed_slot", "rule", "n_paths", "hops", "paths": [[(u, rel, v), ...], ...]},
+    ...]`` over its (question entity, rule) pairs, seeds outermost, rules in the given order - the loops of
+    ``apply_rules``.  A path is a walk from the seed whose hop ``i`` is an edge of relation ``rule[i]`` (nodes may
+    repeat), every triple in walk direction, in ascending order of the walk's node sequence.
+
+    ``rules[b]``: the question's rules, each a list of relation ids, or of relation names mapped through ``relation2id``
+    (an unknown name becomes -1 and matches nothing, as an unknown string does in the reference).  More than
+    ``max_rules`` rules or a rule longer than ``max_hops`` raise ``ValueError``; an empty rule yields ``n_paths == 0``
+    (the reference's single empty path carries no triple).  ``n_paths`` is the true number of walks;
+    ``len(paths) == min(n_paths, max_paths)``.  The other arguments and ``return_info`` are those of
+    :func:`retrieve_paths`; ``info[b] = (seeds found, rules of 1 .. max_hops hops)``."""
+    B, N = plan_or_ugraph.B, plan_or_ugraph.N
+    rule_rel, rule_len = _pack_rules(rules, B, relation2id, max_rules, max_hops)      # raises before any device work
+    graph = plan_or_ugraph if isinstance(plan_or_ugraph, ops.UGraph) else ops.UGraph.from_plan(plan_or_ugraph)
+    dev = graph.device
+    local_entity = np.asarray(local_entity)
+    qe = np.asarray(query_entities)
+    if local_entity.shape != (B, N) or qe.shape != (B, N):
+        raise ValueError("local_entity and query_entities must be [%d, %d]" % (B, N))
+    rels = np.asarray(rels)
+    seeds = qe.astype(np.int64) == 1
+    with torch.cuda.device(dev):
+        sf = torch.from_numpy(seeds.astype(np.uint8)).to(dev)
+        fr = torch.from_numpy(np.ascontiguousarray(rels, dtype=np.int32)).to(dev)
+        out = ops.rule_paths(graph, fr, sf, torch.from_numpy(rule_rel).to(dev), torch.from_numpy(rule_len).to(dev),
+                             max_seeds, max_rules, max_paths, max_hops)
+        # the one synchronising readback: the small fixed blocks, then the records that exist
+        fixed = torch.cat([out.q_info.reshape(-1), out.pair_info.reshape(-1), out.path_off]).cpu().numpy()
+        P = B * max_seeds * max_rules
+        q_info = fixed[: 2 * B].reshape(B, 2)
+        pair_info = fixed[2 * B: 2 * B + 2 * P].reshape(B, max_seeds, max_rules, 2)
+        path_off = fixed[2 * B + 2 * P:]
+        total = int(path_off[-1])
+        nodes = out.path_nodes[:total].cpu().numpy()
+        facts = out.path_facts[:total].cpu().numpy()
+    LAST_RULE_READBACK.update(fixed_bytes=int(fixed.nbytes), record_bytes=int(nodes.nbytes + facts.nbytes),
+                              records=total)
+    result = []
+    for b in range(B):
+        pairs = []
+        for si, s in enumerate(np.flatnonzero(seeds[b])[:max_seeds]):
+            for k, rule in enumerate(rules[b]):
+                p = (b * max_seeds + si) * max_rules + k
+                h = int(pair_info[b, si, k, 1])
+                paths = []
+                for r in range(int(path_off[p]), int(path_off[p + 1])):
+                    ent = [_name(id2entity, int(local_entity[b, v - b * N])) for v in nodes[r, : h + 1]]
+                    paths.append([(ent[i], _name(id2relation, int(rels[facts[r, i]])), ent[i + 1]) for i in range(h)])
+                pairs.append({"seed": _name(id2entity, int(local_entity[b, s])), "seed_slot": int(s), "rule": list(rule),
+                              "n_paths": int(pair_info[b, si, k, 0]), "hops": h, "paths": paths})
+        result.append(pairs)
+    return (result, q_info.copy()) if return_info else result
+
+
+def reasoning_context(rule_result_b, shortest_result_b):
+    """The ordered list of path strings of one question as ``PromptBuilder.process_input`` assembles it
+    (``llm/src/qa_prediction/build_qa_input.py:105-123``, the GNN-RAG+RA union): every rule path in result order, then
+    each shortest path whose string is not in the list yet.  ``rule_result_b`` / ``shortest_result_b``: one question's
+    entry of :func:`retrieve_rule_paths` / :func:`retrieve_paths` (either may be ``None`` or empty).  Host code."""
+    out = [path_to_string(p) for pair in (rule_result_b or ()) for p in pair["paths"]]
+    for pair in (shortest_result_b or ()):
+        for p in pair["paths"]:
+            s = path_to_string(p)
+            if s not in out:
+                out.append(s)
+    return out

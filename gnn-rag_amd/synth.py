@@ -210,3 +210,39 @@ def make_layer_params(cfg: GraphConfig, seed: Optional[int] = None) -> dict:
     # TypeLayer (layer_init.py:19)
     p["type_layer.kb_self_linear.weight"], p["type_layer.kb_self_linear.bias"] = lin(D, D)
     return p
+
+
+def sample_rules(heads, rels, tails, B: int, N: int, seed_flag, n_rules: int, max_len: int, rng: np.random.Generator,
+                 n_rel: Optional[int] = None):
+    """Relation paths ("rules") per question for the rule-walk retrieval, the way a path predictor's output looks on a
+    question's subgraph: rule ``i`` is the relation sequence of a random walk of 1 .. ``max_len`` hops from one of the
+    question's seeds (taken in turn) over the question's simple undirected graph (an edge's relation = that of its
+    largest fact id), every fourth rule random relation ids instead (most of those match nothing).  Returns
+    ``rules[b] = [[relation id, ...], ...]``."""
+    heads, rels, tails = (np.asarray(x).tolist() for x in (heads, rels, tails))
+    n_rel = (max(rels) + 1 if rels else 1) if n_rel is None else n_rel
+    win = {}
+    for f, (a, b) in enumerate(zip(heads, tails)):
+        if a != b:
+            win[(a, b) if a < b else (b, a)] = f
+    adj = {}
+    for (a, b), f in sorted(win.items()):
+        adj.setdefault(a, []).append((b, rels[f]))
+        adj.setdefault(b, []).append((a, rels[f]))
+    rules = []
+    for q in range(B):
+        seeds = (np.flatnonzero(np.asarray(seed_flag[q]) != 0) + q * N).tolist()
+        out = []
+        for i in range(n_rules):
+            length = int(rng.integers(1, max_len + 1))
+            v = seeds[i % len(seeds)] if seeds else None
+            rule = []
+            if i % 4 != 3 and v in adj:
+                for _ in range(length):
+                    v, r = adj[v][int(rng.integers(len(adj[v])))]
+                    rule.append(int(r))
+            else:
+                rule = [int(x) for x in rng.integers(0, n_rel, length)]
+            out.append(rule)
+        rules.append(out)
+    return rules

@@ -573,6 +573,44 @@ int gnnrag_shortest_paths(const gnnrag_ugraph* graph, const uint8_t* seed_flag, 
                           int32_t max_hops, int32_t* q_info, int32_t* pair_info, int32_t* path_off, int32_t* path_nodes,
                           int32_t* path_facts, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* Rule-guided walks: the other path set the reference hands to the LLM.  bfs_with_rule (graph_utils.py:24-47, called for
+ * every question entity and every predicted relation path by apply_rules, build_qa_input.py:56-64) returns every WALK
+ * seed = v0, v1 .. vL of the question's graph (the gnnrag_ugraph above) whose hop i is an edge of relation rule[i], L =
+ * the rule's length.  Walks are not simple paths: nodes repeat, a walk may go back over the edge it just took.  The
+ * relation of an edge is that of its winning fact: fact_rel[u_adj[e][1]], fact_rel [F] = the relation id of every fact of
+ * the caller's tuple, on the device.
+ *
+ * Device scratch: the relation of every adjacency record, staged once per call (2 max(F, 1) int32), then the counts
+ * down[B][max_rules][max_hops][N] uint32 (walks from a node that complete the rule from hop l on; they do not depend on
+ * the seed), each part rounded up to 256 bytes.  0 on bad or overflowing sizes, max_hops > 254 and N > 65536. */
+size_t gnnrag_rule_paths_workspace_bytes(int64_t F, int32_t B, int32_t N, int32_t max_rules, int32_t max_hops);
+/* Worst-case bytes of the five output arrays, laid out as gnnrag_paths_out_bytes lays them out, with P = B * max_seeds *
+ * max_rules pairs.  0 on bad sizes, max_hops > 254 or P * max_paths >= 2^31. */
+size_t gnnrag_rule_paths_out_bytes(int32_t B, int32_t max_seeds, int32_t max_rules, int32_t max_paths, int32_t max_hops);
+/* Pairs of question b = its seeds (slots with seed_flag != 0, ascending, the first max_seeds) x its rules: rule k of
+ * question b is rule_rel[b,k,0 .. rule_len[b,k]) (rules are per question, as predicted_paths is).  Pair index = (b *
+ * max_seeds + seed index) * max_rules + rule index.  A rule_len outside [1, max_hops] marks an empty or rejected slot -
+ * the one deliberate difference: the reference answers an empty rule with one empty path, which carries no triple.  A
+ * relation id that no winning fact carries (negative ids included) never matches.
+ *   q_info[b]    = (seeds found, rules with rule_len in [1, max_hops]): a first value above max_seeds means the question
+ *                  was cut
+ *   pair_info[p] = (n_paths, hops): the true number of walks, saturating at INT32_MAX, and hops = rule_len (also when
+ *                  n_paths == 0); (0, -1) where the seed index or the rule does not exist
+ *   path_off     = exclusive scan of min(n_paths, max_paths): the records of pair p are path_off[p] .. path_off[p+1]
+ *   path_nodes   = per record max_hops + 1 node ids (question * N + slot) from the seed outwards, then -1
+ *   path_facts   = per record max_hops winning fact ids (hop i joins nodes i and i + 1), then -1
+ * The records of a pair are its walks of rank 0 .. min(n_paths, max_paths) - 1 in rank order, walks ranked
+ * lexicographically by their node sequence read from the seed outwards (ascending node id): deterministic, independent
+ * of the question's place in the batch; the reference's own order (networkx insertion order) is not reproduced.  Records
+ * are written compactly: path_off[P] of them exist, the rest of the two arrays is not touched.  max_hops <= 254 and N <=
+ * 65536, else GNNRAG_E_UNSUPPORTED; a workspace below the stated size is GNNRAG_E_WORKSPACE before anything is
+ * launched.  Nothing waits for the stream, no atomics, no result depends on what an output or the workspace held. */
+int gnnrag_rule_paths(const gnnrag_ugraph* graph, const int32_t* fact_rel, const uint8_t* seed_flag,
+                      const int32_t* rule_rel, const int32_t* rule_len, int32_t max_seeds, int32_t max_rules,
+                      int32_t max_paths, int32_t max_hops, int32_t* q_info, int32_t* pair_info, int32_t* path_off,
+                      int32_t* path_nodes, int32_t* path_facts, void* workspace, size_t workspace_bytes,
+                      gnnrag_stream_t stream);
+
 /* Plain HBM copy kernel (float4 per lane) used by bench.py to measure the achievable
  * streaming ceiling next to the 8 TB/s spec.  n = number of floats (multiple of 4). */
 int gnnrag_stream_copy(const float* src, float* dst, int64_t n, gnnrag_stream_t stream);
