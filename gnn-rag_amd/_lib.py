@@ -92,6 +92,11 @@ SIGNATURES = {
                                             C.c_int32, _VP, C.c_size_t, _VP]),
     "gnnrag_lstm_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gnnrag_lstm_forward": (C.c_int, [_VP] * 10 + [C.c_int32] * 4 + [_VP, C.c_size_t, _VP]),
+    # training form of the LSTM (additive to ABI 16)
+    "gnnrag_lstm_reserve_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_lstm_forward_train": (C.c_int, [_VP] * 10 + [C.c_int32] * 4 + [_VP, C.c_size_t, _VP, C.c_size_t, _VP]),
+    "gnnrag_lstm_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_lstm_backward": (C.c_int, [_VP] * 7 + [C.c_size_t] + [_VP] * 9 + [C.c_int32] * 4 + [_VP, C.c_size_t, _VP]),
     "gnnrag_seed_retrieve": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP]),
     "gnnrag_query_reform": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP]),
     "gnnrag_topp_candidates": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, _VP, _VP, _VP]),

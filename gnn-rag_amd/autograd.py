@@ -5,10 +5,13 @@ through ``reason_layer`` / ``reason_layer_inv`` (``reasongnn.py:61-116``) and ``
 (``layer_init.py:25-62``).  Here the typed-edge aggregation and its backward are HIP kernels
 (``gnnrag_aggregate`` / ``gnnrag_aggregate_backward``, ``gnnrag_typelayer`` /
 ``gnnrag_typelayer_backward``); the dense projections around them run on the library's matrix-core kernels in
-both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gemm_tn`` for dW)."""
+both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gemm_tn`` for dW).  The question
+encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``)."""
 from __future__ import annotations
 
 import torch
+
+from torch.autograd.function import once_differentiable
 
 from . import ops
 
@@ -122,3 +125,34 @@ def linear(x: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False) -> torc
     shp = x.shape
     y = LinearFn.apply(x.reshape(-1, shp[-1]), W, b, relu)
     return y.view(*shp[:-1], W.shape[0])
+
+
+class LstmFn(torch.autograd.Function):
+    """``out, h_n, c_n = LSTM(x, (h0, c0))`` (one layer, one direction, batch_first; ``nn.LSTM`` semantics) on
+    ``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``.  h0 / c0: [B, H] or None (zeros).  The reserve (activated
+    gates and cell states) is saved in the context of THIS call - a module called twice inside one graph has two;
+    ``workspaces`` is the caller's dict for the transposed-weight scratch (see :func:`ops.lstm_forward`)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh, h0, c0, workspaces):
+        x = x.detach().float()
+        h0 = None if h0 is None else h0.detach().float()
+        c0 = None if c0 is None else c0.detach().float()
+        out, h_n, c_n, reserve = ops.lstm_forward_train(x, w_ih, w_hh, b_ih, b_hh, h0, c0, workspaces=workspaces)
+        ctx.set_materialize_grads(False)            # an unused output arrives as None and goes to the library as NULL
+        ctx.save_for_backward(x, w_ih.detach(), w_hh.detach(), h0, c0, out, reserve)
+        return out, h_n, c_n
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, g_hn, g_cn):
+        x, w_ih, w_hh, h0, c0, out, reserve = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as out.sum().backward() delivers
+        g_out, g_hn, g_cn = (None if g is None else g.float() for g in (g_out, g_hn, g_cn))
+        dx, dw_ih, dw_hh, db, dh0, dc0 = ops.lstm_backward(x, w_ih, w_hh, h0, c0, out, reserve, g_out, g_hn, g_cn,
+                                                           need_dx=need[0], need_db=need[3] or need[4],
+                                                           need_dh0=need[5], need_dc0=need[6])
+        # b_ih and b_hh get the same values in two tensors (their .grad must not share memory)
+        return (dx, dw_ih if need[1] else None, dw_hh if need[2] else None, db if need[3] else None,
+                (db.clone() if need[3] else db) if need[4] else None, dh0, dc0, None)

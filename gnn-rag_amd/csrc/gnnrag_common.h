@@ -158,4 +158,7 @@ int update_b3_launch(const float* h, const float* nbr, const float* W, const flo
                      const float* mask, float* h_out, float* score, int64_t BN, int32_t D, int32_t ldw,
                      hipStream_t stream);
 
+// dst [cols, rows] = src [rows, cols]^T (lstm.hip: the transposed weight copies of the LSTM forward and backward)
+int lstm_transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t stream);
+
 }  // namespace gnnrag

@@ -12,6 +12,10 @@
 // weights are read transposed ([k][4H]: coalesced 16 H-byte rows, L2-resident - 1.6 MB at H = 200, E = 300), a weight
 // element is used for the R sequences and (input part) for TC consecutive tokens at once; h lives in LDS, c in the
 // registers of the first H threads.  Sums run over k in ascending order: one fixed order, fp32 throughout.
+//
+// Training form (gnnrag_lstm_forward_train): the same kernel with SAVE = true also writes the four activated gates and
+// the cell state of every step into the caller's reserve - the arithmetic and its order are those of the inference
+// form, so out / h_n / c_n are the same bits.  The backward lives in lstm_bwd.hip.
 #include "gnnrag_common.h"
 
 namespace gnnrag {
@@ -27,6 +31,8 @@ struct LstmArgs {
   float* out;            // [B, T, H]
   float* hn;             // [B, H]
   float* cn;             // [B, H]
+  float* act;            // [B, T, 4H] activated gates i, f, g, o   (SAVE only)
+  float* cs;             // [B, T, H]  cell state after every step  (SAVE only)
   int32_t B, T, E, H;
 };
 
@@ -47,11 +53,17 @@ __global__ __launch_bounds__(256) void k_lstm_transpose(const float* __restrict_
   }
 }
 
+int lstm_transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t stream) {
+  hipLaunchKernelGGL(k_lstm_transpose, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, stream, src, dst, rows, cols);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
 constexpr int kLstmTC = 4;      // tokens whose input projections share one pass over W_ih
 
-template <int R>
+template <int R, bool SAVE>
 __global__ __launch_bounds__(1024) void k_lstm(const LstmArgs a) {
   extern __shared__ float smem[];
   const int H = a.H, E = a.E, T = a.T, G = 4 * H;
@@ -119,7 +131,15 @@ __global__ __launch_bounds__(1024) void k_lstm(const LstmArgs a) {
           c[r] = fmaf(fg, c[r], ig * gg);
           const float h = og * tanhf(c[r]);
           s_h[r * H + j] = h;
-          if (b0 + r < a.B) a.out[((size_t)(b0 + r) * T + t) * H + j] = h;
+          if (b0 + r < a.B) {
+            const size_t row = (size_t)(b0 + r) * T + t;
+            a.out[row * H + j] = h;
+            if (SAVE) {
+              float* ar = a.act + row * G;
+              ar[j] = ig; ar[H + j] = fg; ar[2 * H + j] = gg; ar[3 * H + j] = og;
+              a.cs[row * H + j] = c[r];
+            }
+          }
         }
       }
       __syncthreads();
@@ -144,31 +164,56 @@ extern "C" size_t gnnrag_lstm_workspace_bytes(int32_t E, int32_t H) {
   return align_up((size_t)(E + H) * 4 * (size_t)H * sizeof(float), 256);
 }
 
-extern "C" int gnnrag_lstm_forward(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
-                                   const float* b_hh, const float* h0, const float* c0, float* out, float* h_n,
-                                   float* c_n, int32_t B, int32_t T, int32_t E, int32_t H, void* workspace,
-                                   size_t workspace_bytes, gnnrag_stream_t stream_) {
+extern "C" size_t gnnrag_lstm_reserve_bytes(int32_t B, int32_t T, int32_t H) {
+  if (B <= 0 || T <= 0 || H <= 0) return 0;
+  return (size_t)B * T * 5 * (size_t)H * sizeof(float);          // act [B,T,4H] then cs [B,T,H]
+}
+
+template <bool SAVE>
+static int lstm_launch(const float* x, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       const float* h0, const float* c0, float* out, float* h_n, float* c_n, int32_t B, int32_t T,
+                       int32_t E, int32_t H, void* reserve, size_t reserve_bytes, void* workspace,
+                       size_t workspace_bytes, gnnrag_stream_t stream_) {
   if (!x || !w_ih || !w_hh || !out || !h_n || !c_n || B <= 0 || T <= 0 || E <= 0 || H <= 0) return GNNRAG_E_BADARG;
   if (4 * H > 1024) return GNNRAG_E_UNSUPPORTED;            // one thread per gate row
   if (!workspace || workspace_bytes < gnnrag_lstm_workspace_bytes(E, H)) return GNNRAG_E_WORKSPACE;
+  if (SAVE && (!reserve || reserve_bytes < gnnrag_lstm_reserve_bytes(B, T, H))) return GNNRAG_E_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const int G = 4 * H;
   float* wih_t = (float*)workspace;
   float* whh_t = wih_t + (size_t)E * G;
-  hipLaunchKernelGGL(k_lstm_transpose, dim3((E + 31) / 32, (G + 31) / 32), dim3(256), 0, stream, w_ih, wih_t, G, E);
-  GNNRAG_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_lstm_transpose, dim3((H + 31) / 32, (G + 31) / 32), dim3(256), 0, stream, w_hh, whh_t, G, H);
-  GNNRAG_LAUNCH_CHECK();
+  GNNRAG_RC(lstm_transpose_launch(w_ih, wih_t, G, E, stream));
+  GNNRAG_RC(lstm_transpose_launch(w_hh, whh_t, G, H, stream));
   LstmArgs a;
   a.x = x; a.wih_t = wih_t; a.whh_t = whh_t; a.b_ih = b_ih; a.b_hh = b_hh; a.h0 = h0; a.c0 = c0;
   a.out = out; a.hn = h_n; a.cn = c_n; a.B = B; a.T = T; a.E = E; a.H = H;
+  a.act = SAVE ? (float*)reserve : nullptr;
+  a.cs = SAVE ? (float*)reserve + (size_t)B * T * G : nullptr;
   const int threads = (G + 63) / 64 * 64;
   if (B > 512) {            // many sequences (a relation vocabulary): four per workgroup share every weight element
     constexpr int R = 4;
-    hipLaunchKernelGGL((k_lstm<R>), dim3((B + R - 1) / R), dim3(threads), (size_t)R * 5 * H * sizeof(float), stream, a);
+    hipLaunchKernelGGL((k_lstm<R, SAVE>), dim3((B + R - 1) / R), dim3(threads), (size_t)R * 5 * H * sizeof(float), stream,
+                       a);
   } else {
-    hipLaunchKernelGGL((k_lstm<1>), dim3(B), dim3(threads), (size_t)5 * H * sizeof(float), stream, a);
+    hipLaunchKernelGGL((k_lstm<1, SAVE>), dim3(B), dim3(threads), (size_t)5 * H * sizeof(float), stream, a);
   }
   GNNRAG_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int gnnrag_lstm_forward(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                                   const float* b_hh, const float* h0, const float* c0, float* out, float* h_n,
+                                   float* c_n, int32_t B, int32_t T, int32_t E, int32_t H, void* workspace,
+                                   size_t workspace_bytes, gnnrag_stream_t stream) {
+  return lstm_launch<false>(x, w_ih, w_hh, b_ih, b_hh, h0, c0, out, h_n, c_n, B, T, E, H, nullptr, 0, workspace,
+                            workspace_bytes, stream);
+}
+
+extern "C" int gnnrag_lstm_forward_train(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                                         const float* b_hh, const float* h0, const float* c0, float* out, float* h_n,
+                                         float* c_n, int32_t B, int32_t T, int32_t E, int32_t H, void* reserve,
+                                         size_t reserve_bytes, void* workspace, size_t workspace_bytes,
+                                         gnnrag_stream_t stream) {
+  return lstm_launch<true>(x, w_ih, w_hh, b_ih, b_hh, h0, c0, out, h_n, c_n, B, T, E, H, reserve, reserve_bytes,
+                           workspace, workspace_bytes, stream);
 }

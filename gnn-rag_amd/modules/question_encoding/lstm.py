@@ -7,16 +7,27 @@ the instruction module's own ``forward``).  ``torch.lstm`` on ROCm goes to MIOpe
 shapes: two thirds of an evaluation batch's wall time at BASELINE config 2's hidden size.
 
 ``HipLSTM`` IS an ``nn.LSTM`` (same constructor, parameter names, ``state_dict``): without autograd its forward is one
-``gnnrag_lstm_forward`` launch; with autograd enabled (training), or for a shape the kernel does not take, it is the parent
-class.  ``swap_lstm(model)`` replaces every eligible ``nn.LSTM`` of a constructed model and shares - not copies - the
-parameters, so a checkpoint loaded before or after lands in the same tensors.
+``gnnrag_lstm_forward`` launch; with autograd enabled (training) and ``GNNRAG_HIP_LSTM_TRAIN=1`` it goes through
+``autograd.LstmFn`` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``), with ``=0`` - the default until the
+training form is measured - training is the parent class; for anything the kernels do not take it is the parent class.  ``swap_lstm(model)`` replaces every eligible
+``nn.LSTM`` of a constructed model and shares - not copies - the parameters, so a checkpoint loaded before or after lands in
+the same tensors.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
 
-from ... import ops
+from ... import autograd, ops
+
+TRAIN_DEFAULT = "0"        # GNNRAG_HIP_LSTM_TRAIN when unset: off until measured (DESIGN.md section 8 f-4)
+
+
+def train_on_hip() -> bool:
+    """Whether a forward under autograd runs on the library (read at every call: the switch can change in-process)."""
+    return os.environ.get("GNNRAG_HIP_LSTM_TRAIN", TRAIN_DEFAULT) != "0"
 
 
 def _eligible(m: nn.LSTM) -> bool:
@@ -25,14 +36,19 @@ def _eligible(m: nn.LSTM) -> bool:
 
 
 class HipLSTM(nn.LSTM):
-    """One-layer, one-direction, batch_first LSTM; inference forward through ``gnnrag_lstm_forward``."""
+    """One-layer, one-direction, batch_first LSTM; inference forward through ``gnnrag_lstm_forward``, training through
+    ``autograd.LstmFn``."""
 
     def forward(self, input, hx=None):  # noqa: A002  (torch's own argument name)
         fast = (_eligible(self) and isinstance(input, torch.Tensor) and input.is_cuda and input.dim() == 3 and
                 input.dtype == torch.float32 and input.shape[0] > 0 and input.shape[1] > 0 and
                 all(p.dtype == torch.float32 and p.is_cuda for p in self.parameters()) and
-                (hx is None or all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda for t in hx)) and
-                not (torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self.parameters()))))
+                (hx is None or all(isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda for t in hx)))
+        train = fast and torch.is_grad_enabled() and (
+            input.requires_grad or any(p.requires_grad for p in self.parameters()) or
+            (hx is not None and any(t.requires_grad for t in hx)))
+        if train and not (train_on_hip() and input.shape[2] % 4 == 0):       # the weight gradient's kernel: E % 4 == 0
+            fast = False
         if not fast:
             return super().forward(input, hx)
         h0 = c0 = None
@@ -43,7 +59,14 @@ class HipLSTM(nn.LSTM):
                 return super().forward(input, hx)       # torch raises its own shape error
             h0, c0 = h0[0], c0[0]
         bias = self.bias
-        ws = self.__dict__.setdefault("_gnnrag_ws", {})       # the module's own scratch (not a parameter / buffer)
+        # the module's own scratch (not a parameter / buffer): the transposed weights only, refilled by every call - what
+        # a backward needs from its forward is held by that call's autograd context
+        ws = self.__dict__.setdefault("_gnnrag_ws", {})
+        if train:
+            out, h_n, c_n = autograd.LstmFn.apply(input, self.weight_ih_l0, self.weight_hh_l0,
+                                                  self.bias_ih_l0 if bias else None, self.bias_hh_l0 if bias else None,
+                                                  h0, c0, ws)
+            return out, (h_n.unsqueeze(0), c_n.unsqueeze(0))
         out, h_n, c_n = ops.lstm_forward(input, self.weight_ih_l0, self.weight_hh_l0,
                                          self.bias_ih_l0 if bias else None, self.bias_hh_l0 if bias else None, h0, c0,
                                          workspaces=ws)

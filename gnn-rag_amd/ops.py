@@ -1040,6 +1040,82 @@ def lstm_forward(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, workspac
     return out, h_n, c_n
 
 
+def _lstm_args(x, w_ih, w_hh, b_ih, b_hh, h0, c0):
+    x = _chk(x, "x")
+    if x.dim() != 3:
+        raise ValueError("x must be [B,T,E]")
+    B, T, E = x.shape
+    w_ih = _chk(w_ih.detach(), "w_ih")
+    H = w_ih.shape[0] // 4
+    w_ih = _chk(w_ih, "w_ih", shape=(4 * H, E))
+    w_hh = _chk(w_hh.detach(), "w_hh", shape=(4 * H, H))
+    b_ih = None if b_ih is None else _chk(b_ih.detach(), "b_ih", shape=(4 * H,))
+    b_hh = None if b_hh is None else _chk(b_hh.detach(), "b_hh", shape=(4 * H,))
+    h0 = None if h0 is None else _chk(h0, "h0", shape=(B, H))
+    c0 = None if c0 is None else _chk(c0, "c0", shape=(B, H))
+    return x, w_ih, w_hh, b_ih, b_hh, h0, c0, (B, T, E, H)
+
+
+def lstm_forward_train(x, w_ih, w_hh, b_ih=None, b_hh=None, h0=None, c0=None, workspaces=None):
+    """:func:`lstm_forward` for training (``gnnrag_lstm_forward_train``): the same kernel and the same bits in out / h_n /
+    c_n, plus the reserve (activated gates and cell states of every step, a uint8 tensor of
+    ``gnnrag_lstm_reserve_bytes``) that :func:`lstm_backward` reads.  The reserve is allocated per call and returned: it
+    belongs to this forward, not to ``workspaces`` (which, as in :func:`lstm_forward`, only keeps the transposed-weight
+    scratch and is refilled by every call).  Returns (out, h_n, c_n, reserve)."""
+    lib = _lib.load()
+    x, w_ih, w_hh, b_ih, b_hh, h0, c0, (B, T, E, H) = _lstm_args(x, w_ih, w_hh, b_ih, b_hh, h0, c0)
+    dev = x.device
+    out = _buf((B, T, H), torch.float32, dev, "lstm_forward_train: out")
+    h_n = _buf((B, H), torch.float32, dev, "lstm_forward_train: h_n")
+    c_n = _buf((B, H), torch.float32, dev, "lstm_forward_train: c_n")
+    reserve = _buf(lib.gnnrag_lstm_reserve_bytes(B, T, H), torch.uint8, dev, "lstm_forward_train: reserve")
+    need = lib.gnnrag_lstm_workspace_bytes(E, H)
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream)
+    ws = workspaces.get(key) if workspaces is not None else None
+    if ws is None or ws.numel() < need:
+        ws = _buf(need, torch.uint8, dev, "lstm_forward_train: workspace")
+        if workspaces is not None:
+            workspaces[key] = ws
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_lstm_forward_train(x.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), _ptr(b_ih), _ptr(b_hh),
+                                                 _ptr(h0), _ptr(c0), out.data_ptr(), h_n.data_ptr(), c_n.data_ptr(), B, T, E,
+                                                 H, reserve.data_ptr(), reserve.numel(), ws.data_ptr(), ws.numel(),
+                                                 _stream()), "gnnrag_lstm_forward_train")
+    return out, h_n, c_n, reserve
+
+
+def lstm_backward(x, w_ih, w_hh, h0, c0, out, reserve, g_out=None, g_hn=None, g_cn=None, need_dx=True, need_db=True,
+                  need_dh0=False, need_dc0=False):
+    """Backward of :func:`lstm_forward_train` (``gnnrag_lstm_backward``): x, the weights and h0 / c0 (None = zeros) as
+    given to the forward, ``out`` and ``reserve`` as it returned them; g_out [B,T,H], g_hn / g_cn [B,H] the incoming
+    gradients (None = zeros).  Returns (dx, dw_ih, dw_hh, db, dh0, dc0); an output that is not wanted is None and is
+    not computed.  db is the gradient of b_ih and of b_hh alike.  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    x, w_ih, w_hh, _, _, h0, c0, (B, T, E, H) = _lstm_args(x, w_ih, w_hh, None, None, h0, c0)
+    out = _chk(out, "out", shape=(B, T, H))
+    reserve = _chk(reserve, "reserve", dtype=torch.uint8)
+    g_out = None if g_out is None else _chk(g_out, "g_out", shape=(B, T, H))
+    g_hn = None if g_hn is None else _chk(g_hn, "g_hn", shape=(B, H))
+    g_cn = None if g_cn is None else _chk(g_cn, "g_cn", shape=(B, H))
+    dev = x.device
+    dx = _buf((B, T, E), torch.float32, dev, "lstm_backward: dx") if need_dx else None
+    dw_ih = _buf((4 * H, E), torch.float32, dev, "lstm_backward: dw_ih")
+    dw_hh = _buf((4 * H, H), torch.float32, dev, "lstm_backward: dw_hh")
+    db = _buf((4 * H,), torch.float32, dev, "lstm_backward: db") if need_db else None
+    dh0 = _buf((B, H), torch.float32, dev, "lstm_backward: dh0") if need_dh0 else None
+    dc0 = _buf((B, H), torch.float32, dev, "lstm_backward: dc0") if need_dc0 else None
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn inside): query it on x's device
+        ws = _buf(max(lib.gnnrag_lstm_backward_workspace_bytes(B, T, E, H), 16), torch.uint8, dev,
+                  "lstm_backward: workspace")
+        _lib.check(lib.gnnrag_lstm_backward(x.data_ptr(), w_ih.data_ptr(), w_hh.data_ptr(), _ptr(h0), _ptr(c0),
+                                            out.data_ptr(), reserve.data_ptr(), reserve.numel(), _ptr(g_out), _ptr(g_hn),
+                                            _ptr(g_cn), _ptr(dx), dw_ih.data_ptr(), dw_hh.data_ptr(), _ptr(db), _ptr(dh0),
+                                            _ptr(dc0), B, T, E, H, ws.data_ptr(), ws.numel(), _stream()),
+                   "gnnrag_lstm_backward")
+    return dx, dw_ih, dw_hh, db, dh0, dc0
+
+
 def seed_retrieve(seed_info: torch.Tensor, ent_emb: torch.Tensor) -> torch.Tensor:
     """sum_n seed_info[b,n] * ent_emb[b,n,:]  ->  [B,D] (query_update.py:40), reading only flagged rows."""
     lib = _lib.load()

@@ -517,6 +517,39 @@ int gnnrag_lstm_forward(const float* x, const float* w_ih, const float* w_hh, co
                         const float* h0, const float* c0, float* out, float* h_n, float* c_n, int32_t B, int32_t T,
                         int32_t E, int32_t H, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* ---- Training form of the LSTM (additive to ABI 16; SURVEY.md section 8 f-4, the instruction side) ---------------------
+ * gnnrag_lstm_forward_train is gnnrag_lstm_forward - same arguments, same kernel, same arithmetic in the same order:
+ * out, h_n and c_n are the same bits - that also fills the caller-owned `reserve` the backward reads:
+ *   act [B,T,4H]  the four activated gates of every step (sigmoid i, sigmoid f, tanh g, sigmoid o), then
+ *   cs  [B,T,H]   the cell state after every step;
+ * gnnrag_lstm_reserve_bytes(B, T, H) bytes, fully written.  The reserve belongs to ONE forward call: a module that is
+ * called twice before its backward passes run (base_encoder.py:74-80) needs two. */
+size_t gnnrag_lstm_reserve_bytes(int32_t B, int32_t T, int32_t H);
+int gnnrag_lstm_forward_train(const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
+                              const float* b_hh, const float* h0, const float* c0, float* out, float* h_n, float* c_n,
+                              int32_t B, int32_t T, int32_t E, int32_t H, void* reserve, size_t reserve_bytes,
+                              void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
+/* Backward of the call above: what autograd derives for nn.LSTM in Trainer_KBQA.train_epoch (train_model.py:209-233).
+ * x, w_ih, w_hh, h0, c0 (NULL = zeros) as given to the forward, `out` and `reserve` as it left them; g_out [B,T,H],
+ * g_hn / g_cn [B,H]: the incoming gradients of out, h_n, c_n - each may be NULL (zeros).
+ * dw_ih [4H,E] and dw_hh [4H,H] are required; dx [B,T,E], db [4H] (the gradient of b_ih AND of b_hh: the same values),
+ * dh0 / dc0 [B,H] may be NULL: not wanted, not computed.  Every requested output is fully written.
+ * One workgroup per sequence walks t = T-1 .. 0 with dc in registers and leaves the pre-activation gate gradients
+ * dG [B,T,4H] in the workspace; dh_{t-1} = W_hh^T dG_t is four per-gate-block partial sums (ascending gate row) added
+ * in block order; dx = dG W_ih (the exact-fp32 gnnrag_linear), dw_ih = dG^T x and dw_hh = dG^T h_prev
+ * (gnnrag_gemm_tn), db = column sums of dG (rows in 8 slices, slices added in order): one fixed summation order, no
+ * atomics, fp32 throughout, nothing waits for the stream.
+ * 4 H <= 1024, E % 4 == 0, x / dw_ih / workspace 16-byte aligned, else GNNRAG_E_UNSUPPORTED.  A reserve below
+ * gnnrag_lstm_reserve_bytes or a workspace below gnnrag_lstm_backward_workspace_bytes(B, T, E, H) (which, like
+ * gnnrag_gemm_tn_workspace_bytes, depends on the current device) is GNNRAG_E_WORKSPACE before anything is launched. */
+size_t gnnrag_lstm_backward_workspace_bytes(int32_t B, int32_t T, int32_t E, int32_t H);
+int gnnrag_lstm_backward(const float* x, const float* w_ih, const float* w_hh, const float* h0, const float* c0,
+                         const float* out, const void* reserve, size_t reserve_bytes, const float* g_out,
+                         const float* g_hn, const float* g_cn, float* dx, float* dw_ih, float* dw_hh, float* db,
+                         float* dh0, float* dc0, int32_t B, int32_t T, int32_t E, int32_t H, void* workspace,
+                         size_t workspace_bytes, gnnrag_stream_t stream);
+
 /* ---- Reasoning paths (additive to ABI 16: new entry points only, nothing above changes) ----------------------------------
  * The retrieval step of GNN-RAG: all shortest paths between the question's entities and the retrieved candidates in the
  * question's subgraph taken as a SIMPLE UNDIRECTED graph - what llm/src/utils/graph_utils.py builds with networkx

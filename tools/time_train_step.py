@@ -86,6 +86,10 @@ def main():
     if not a.pure:
         from gnnrag_amd.data.fact_mat import patch_loader
         patch_loader(tr.train_data, cache=False, keep_rng_stream=True)
+        if os.environ.get("GNNRAG_HIP_LSTM", "1") != "0":
+            # the question encoder's nn.LSTM -> HipLSTM: under autograd it trains on the library unless
+            # GNNRAG_HIP_LSTM_TRAIN=0 hands the call back to the parent class (MIOpen's RNN)
+            install.swap_lstm(tr.model)
     sync = (lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
     tr.model.train()
@@ -123,7 +127,9 @@ def main():
            "entity_dim": int(tr.args["entity_dim"]), "num_iter": int(tr.args["num_iter"]), "num_gnn": int(tr.args["num_gnn"]),
            "num_ins": int(tr.args["num_ins"]), "train_questions": int(tr.train_data.num_data),
            "padded_nodes_per_question": int(tr.train_data.max_local_entity), "native_library": native,
-           "layer_class": type(tr.model.reasoning).__module__}
+           "layer_class": type(tr.model.reasoning).__module__,
+           "lstm_class": sorted({type(m).__name__ for m in tr.model.modules() if isinstance(m, torch.nn.LSTM)}),
+           "hip_lstm_train": None if a.pure else os.environ.get("GNNRAG_HIP_LSTM_TRAIN", "default")}
     import shutil
     shutil.rmtree(ck, ignore_errors=True)
     print("GNNRAG_TRAIN " + json.dumps(out))
