@@ -135,6 +135,8 @@ SIGNATURES = {
                                                   C.c_int32, _VP]),
     "gnnrag_aggregate_fused_frontier": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gnnrag_frontier_read": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP]),
+    # instruction generation (additive to ABI 16)
+    "gnnrag_instructions": (C.c_int, [_VP] * 4 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP] * 3),
     # reasoning paths (additive to ABI 16)
     "gnnrag_ugraph_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gnnrag_ugraph_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),

@@ -175,6 +175,7 @@ def swap(model, args: dict):
             tl.load_state_dict(tl_old.state_dict(), strict=True)
             tl.to(next(tl_old.parameters()).device)
             model.type_layer = tl
+        patch_instruction(model)
         return model
     # old.num_relation is overwritten by init_reason (reasongnn.py:55); the constructor value,
     # which sizes pos_emb, is kept by BaseModel (base_model.py:21)
@@ -204,6 +205,17 @@ def swap(model, args: dict):
     if hasattr(model, "get_rel_feature"):
         cache_rel_features(model)
     swap_lstm(model)
+    patch_instruction(model)
+    return model
+
+
+def patch_instruction(model):
+    """``model.instruction`` (rearev.py:124-127, nsm.py alike): all steps of ``get_instruction`` in one launch, the second
+    pass of a forward from the first (modules/question_encoding/instruction.py; ``GNNRAG_HIP_INSTRUCTION=0`` leaves the
+    reference's own methods in charge)."""
+    if getattr(model, "instruction", None) is not None:
+        from .modules.question_encoding.instruction import patch_instruction as _patch
+        _patch(model.instruction)
     return model
 
 

@@ -1158,6 +1158,50 @@ def query_reform(q_node: torch.Tensor, seed_info: torch.Tensor, ent_emb: torch.T
     return out
 
 
+MAX_INS = 8                                     # GNNRAG_MAX_INS (include/gnnrag.h)
+
+
+def instructions_supported(T: int, D: int, n_steps: int) -> bool:
+    """Whether ``gnnrag_instructions`` takes the shape (the header's LDS budget: one question's working set in 160 KB)."""
+    return (T > 0 and D > 0 and 0 < n_steps <= MAX_INS and
+            4 * ((T * D + 3) // 4 * 4 + (n_steps + 2) * D + T) <= 160 * 1024)
+
+
+def instructions(hidden, node, mask, W_q, b_q, W_cq, b_cq, w_ca, b_ca, r_in=None):
+    """``BaseInstruction.get_instruction`` (base_encoder.py:82-101) for ``len(W_q)`` chained steps in one launch
+    (``gnnrag_instructions``): hidden [B,T,D], node [B,D], mask [B,T], ``W_q`` / ``b_q`` LISTS of the steps'
+    ``question_linear`` weights [D,D] and biases [D], W_cq [D,4D], b_cq [D], w_ca [D] (or ``ca_linear.weight`` [1,D]),
+    b_ca [1], r_in [B,D] or None (zeros).  Returns (ins [n,B,D], attn [n,B,T]).  A shape outside the library's budget
+    raises ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    hidden = _chk(hidden, "hidden")
+    if hidden.dim() != 3:
+        raise ValueError("hidden must be [B,T,D]")
+    B, T, D = hidden.shape
+    n = len(W_q)
+    if len(b_q) != n:
+        raise ValueError("instructions: W_q and b_q must be lists of the same length")
+    node = _chk(node, "node", shape=(B, D))
+    mask = _chk(mask, "mask", shape=(B, T))
+    W_q = [_chk(w.detach(), "W_q[%d]" % i, shape=(D, D)) for i, w in enumerate(W_q)]
+    b_q = [_chk(v.detach(), "b_q[%d]" % i, shape=(D,)) for i, v in enumerate(b_q)]
+    W_cq = _chk(W_cq.detach(), "W_cq", shape=(D, 4 * D))
+    b_cq = _chk(b_cq.detach(), "b_cq", shape=(D,))
+    w_ca = _chk(w_ca.detach().reshape(-1), "w_ca", shape=(D,))
+    b_ca = _chk(b_ca.detach().reshape(-1), "b_ca", shape=(1,))
+    r_in = None if r_in is None else _chk(r_in, "r_in", shape=(B, D))
+    dev = hidden.device
+    ins = _buf((max(n, 1), B, D), torch.float32, dev, "instructions: ins_out")
+    attn = _buf((max(n, 1), B, T), torch.float32, dev, "instructions: attn_out")
+    Wp = (C.c_void_p * max(n, 1))(*[w.data_ptr() for w in W_q])
+    bp = (C.c_void_p * max(n, 1))(*[v.data_ptr() for v in b_q])
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_instructions(hidden.data_ptr(), node.data_ptr(), mask.data_ptr(), _ptr(r_in), Wp, bp,
+                                           W_cq.data_ptr(), b_cq.data_ptr(), w_ca.data_ptr(), b_ca.data_ptr(), B, T, D, n,
+                                           ins.data_ptr(), attn.data_ptr(), _stream()), "gnnrag_instructions")
+    return ins, attn
+
+
 def topp_candidates(pred_dist: torch.Tensor, eligible: torch.Tensor, ignore_prob: float, eps: float):
     """Per question: slots kept by the Evaluator's filter, sorted by probability (descending, stable), and
     how many of them the top-p cut retrieves.  Returns (slots int32 [B,N] (-1 padded), counts int32 [B,2])."""

@@ -550,6 +550,29 @@ int gnnrag_lstm_backward(const float* x, const float* w_ih, const float* w_hh, c
                          float* dh0, float* dc0, int32_t B, int32_t T, int32_t E, int32_t H, void* workspace,
                          size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* ---- Instruction generation (additive to ABI 16; SURVEY.md section 8 f-3, the instruction path) -------------------------
+ * BaseInstruction.get_instruction (gnn/modules/question_encoding/base_encoder.py:82-101) for n_steps chained steps in ONE
+ * launch.  Per question b, starting from r = r_in[b] (NULL = zeros), for step s:
+ *   q_s  = W_q[s] node[b] + b_q[s]                               (:92)
+ *   cq   = W_cq [r, q_s, q_s - r, q_s * r] + b_cq                (:93)
+ *   ca_t = sum_d w_ca[d] cq[d] hidden[b,t,d] + b_ca              (:95)
+ *   a    = softmax_t(ca_t + (1 - mask[b,t]) * -1e11)             (:98; the fp32 sum as written, row maximum subtracted)
+ *   r    = sum_t a_t hidden[b,t,:]                               (:100)   ins_out[s,b,:] = r, attn_out[s,b,:] = a
+ * hidden [B,T,D] (the encoder's token states), node [B,D], mask [B,T] (1 = token, 0 = padding; a question of padding only
+ * gets the uniform 1/T, as in the reference), W_cq [D,4D], b_cq [D], w_ca [D], b_ca [1] - all device memory, b_ca is
+ * read by the kernel.  W_q / b_q: HOST arrays of n_steps device pointers ([D,D] and [D] each; question_linear{s} are
+ * separate parameters) - read during the call and carried in the kernel's arguments, nothing is packed or copied.
+ * ins_out [n_steps,B,D], attn_out [n_steps,B,T], both fully written.  One workgroup per question, its token states in
+ * LDS; one fixed summation order (no atomics: the same bits on every call, and a chain cut into several calls gives the
+ * bits of one call); no allocation, no workspace, nothing waits for the stream; safe under stream capture.
+ * n_steps > GNNRAG_MAX_INS, or a working set of 4 * (ceil4(T D) + (n_steps + 2) D + T) bytes above 160 KB, is
+ * GNNRAG_E_UNSUPPORTED (every T D <= 16384 with D <= 2048 fits); any D >= 1 inside that is taken. */
+#define GNNRAG_MAX_INS 8
+int gnnrag_instructions(const float* hidden, const float* node, const float* mask, const float* r_in,
+                        const float* const* W_q, const float* const* b_q, const float* W_cq, const float* b_cq,
+                        const float* w_ca, const float* b_ca, int32_t B, int32_t T, int32_t D, int32_t n_steps,
+                        float* ins_out, float* attn_out, gnnrag_stream_t stream);
+
 /* ---- Reasoning paths (additive to ABI 16: new entry points only, nothing above changes) ----------------------------------
  * The retrieval step of GNN-RAG: all shortest paths between the question's entities and the retrieved candidates in the
  * question's subgraph taken as a SIMPLE UNDIRECTED graph - what llm/src/utils/graph_utils.py builds with networkx

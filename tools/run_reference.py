@@ -152,6 +152,16 @@ def main():
             install.swap_lstm(self.model)
 
         evaluate.Evaluator.__init__ = _init_lstm
+    # model.instruction: all steps of get_instruction in one launch, the forward's second pass from its first
+    # (gnnrag_amd.modules.question_encoding.instruction; GNNRAG_HIP_INSTRUCTION=0, read at every call, leaves the
+    # reference's own methods in charge)
+    _ev_init1 = evaluate.Evaluator.__init__
+
+    def _init_instruction(self, *a, **kw):
+        _ev_init1(self, *a, **kw)
+        install.patch_instruction(self.model)
+
+    evaluate.Evaluator.__init__ = _init_instruction
     if world > 1 or force_dist:
         from gnnrag_amd import shard
         _ev_init = evaluate.Evaluator.__init__
