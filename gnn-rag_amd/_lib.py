@@ -137,6 +137,11 @@ SIGNATURES = {
     "gnnrag_frontier_read": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP]),
     # instruction generation (additive to ABI 16)
     "gnnrag_instructions": (C.c_int, [_VP] * 4 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP] * 3),
+    # relation-text features (additive to ABI 16)
+    "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
+    "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),
+    "gnnrag_rel_text_backward_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
+    "gnnrag_rel_text_pool_backward": (C.c_int, [_VP] * 8 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 4 + [C.c_size_t, _VP]),
     # reasoning paths (additive to ABI 16)
     "gnnrag_ugraph_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gnnrag_ugraph_scratch_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
@@ -192,5 +197,7 @@ def load():
 def check(code: int, what: str = ""):
     if code != 0:
         msg = load().gnnrag_error_string(code)
-        raise GnnragError("%s failed (%d): %s" % (what or "gnnrag call", code,
+        err = GnnragError("%s failed (%d): %s" % (what or "gnnrag call", code,
                                                   msg.decode() if msg else "?"))
+        err.code = code
+        raise err

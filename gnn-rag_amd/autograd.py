@@ -6,7 +6,8 @@ through ``reason_layer`` / ``reason_layer_inv`` (``reasongnn.py:61-116``) and ``
 (``gnnrag_aggregate`` / ``gnnrag_aggregate_backward``, ``gnnrag_typelayer`` /
 ``gnnrag_typelayer_backward``); the dense projections around them run on the library's matrix-core kernels in
 both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gemm_tn`` for dW).  The question
-encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``)."""
+encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``), the relation-text
+features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -156,3 +157,34 @@ class LstmFn(torch.autograd.Function):
         # b_ih and b_hh get the same values in two tensors (their .grad must not share memory)
         return (dx, dw_ih if need[1] else None, dw_hh if need[2] else None, db if need[3] else None,
                 (db.clone() if need[3] else db) if need[4] else None, dh0, dc0, None)
+
+
+class RelTextPoolFn(torch.autograd.Function):
+    """``out_fwd, out_inv = AttnEncoder(question_emb(X), mask)`` of the relation-text branch (rearev.py:101-106; X_inv None:
+    one direction, nsm.py:103-105, and ``out_inv`` is None) on ``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``.
+    W, b = ``question_emb``, a = ``attn_linear.weight``.  xbar and alpha are saved in the context of THIS call.  X (the
+    frozen LM states) and the mask never receive a gradient."""
+
+    @staticmethod
+    def forward(ctx, X_fwd, X_inv, mask, W, b, a):
+        X_fwd = X_fwd.detach()
+        X_inv = None if X_inv is None else X_inv.detach()
+        need = any(ctx.needs_input_grad[3:6])
+        out_fwd, out_inv, xbar, alpha = ops.rel_text_pool(X_fwd, X_inv, mask.detach(), W, b, a, save=need)
+        ctx.set_materialize_grads(False)            # an unused output arrives as None and goes to the library as NULL
+        ctx.two = X_inv is not None
+        ctx.a_shape = a.shape
+        if need:
+            ctx.save_for_backward(X_fwd, X_inv, W.detach(), a.detach(), xbar, alpha)
+        return out_fwd, out_inv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_fwd, g_inv):
+        X_fwd, X_inv, W, a, xbar, alpha = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        g_fwd = None if g_fwd is None else g_fwd.float()
+        g_inv = None if (g_inv is None or not ctx.two) else g_inv.float()
+        dW, db, da = ops.rel_text_pool_backward(X_fwd, X_inv, W, a, xbar, alpha, g_fwd, g_inv, need_dW=need[3],
+                                                need_db=need[4], need_da=need[5])
+        return None, None, None, dW, db, None if da is None else da.view(ctx.a_shape)

@@ -176,6 +176,7 @@ def swap(model, args: dict):
             tl.to(next(tl_old.parameters()).device)
             model.type_layer = tl
         patch_instruction(model)
+        patch_rel_feature(model)
         return model
     # old.num_relation is overwritten by init_reason (reasongnn.py:55); the constructor value,
     # which sizes pos_emb, is kept by BaseModel (base_model.py:21)
@@ -203,6 +204,7 @@ def swap(model, args: dict):
         setattr(model, "reform" + str(j), new_r)
         j += 1
     if hasattr(model, "get_rel_feature"):
+        patch_rel_feature(model)            # underneath the cache: its one computation per parameter version
         cache_rel_features(model)
     swap_lstm(model)
     patch_instruction(model)
@@ -217,6 +219,14 @@ def patch_instruction(model):
         from .modules.question_encoding.instruction import patch_instruction as _patch
         _patch(model.instruction)
     return model
+
+
+def patch_rel_feature(model):
+    """``model.get_rel_feature`` with ``--relation_word_emb True`` (rearev.py:101-106, nsm.py:103-105): ``question_emb`` +
+    ``AttnEncoder`` over the relation vocabulary's LM states in one fused call, forward and backward
+    (modules/rel_text.py; ``GNNRAG_HIP_REL_TEXT=0`` - the default - leaves the reference's own method in charge)."""
+    from .modules.rel_text import patch_rel_feature as _patch
+    return _patch(model)
 
 
 def swap_lstm(model) -> int:

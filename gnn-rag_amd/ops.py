@@ -1202,6 +1202,81 @@ def instructions(hidden, node, mask, W_q, b_q, W_cq, b_cq, w_ca, b_ca, r_in=None
     return ins, attn
 
 
+REL_TEXT_MAX_T, REL_TEXT_MAX_K, REL_TEXT_MAX_D = 256, 4096, 4096     # GNNRAG_REL_TEXT_MAX_* (include/gnnrag.h)
+
+
+def rel_text_supported(R: int, T: int, K: int, D: int) -> bool:
+    """Whether ``gnnrag_rel_text_pool`` takes the shape (the header's limits)."""
+    return (0 < R <= 1 << 24 and 0 < T <= REL_TEXT_MAX_T and 0 < K <= REL_TEXT_MAX_K and K % 4 == 0 and
+            0 < D <= REL_TEXT_MAX_D)
+
+
+def _rel_text_args(X_fwd, X_inv, W, a):
+    X_fwd = _chk(X_fwd, "X_fwd")
+    if X_fwd.dim() != 3:
+        raise ValueError("X_fwd must be [R,T,K]")
+    R, T, K = X_fwd.shape
+    X_inv = None if X_inv is None else _chk(X_inv, "X_inv", shape=(R, T, K))
+    W = _chk(W.detach(), "W")
+    D = W.shape[0]
+    W = _chk(W, "W", shape=(D, K))
+    a = _chk(a.detach().reshape(-1), "a", shape=(D,))
+    return X_fwd, X_inv, W, a, (R, T, K, D)
+
+
+def rel_text_pool(X_fwd, X_inv, mask, W, b, a, save: bool = False):
+    """``get_rel_feature`` of the relation-text branch (rearev.py:101-106, nsm.py:103-105; ``gnnrag_rel_text_pool``):
+    ``AttnEncoder(question_emb(X), mask)`` for the forward and - ``X_inv`` not None - the inverse relation texts, X [R,T,K]
+    the LM token states, mask [R,T] (1 = token, shared by both directions), W [D,K] / b [D] = ``question_emb``, a [D] (or
+    ``attn_linear.weight`` [1,D]).  Returns (out_fwd [R,D], out_inv or None, xbar, alpha); ``save`` keeps xbar
+    [n_dir,R,K] and alpha [n_dir,R,T] for :func:`rel_text_pool_backward` (else both None: xbar lives in the call's
+    workspace).  A shape outside the library's limits raises ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    X_fwd, X_inv, W, a, (R, T, K, D) = _rel_text_args(X_fwd, X_inv, W, a)
+    mask = _chk(mask, "mask", shape=(R, T))
+    b = _chk(b.detach(), "b", shape=(D,))
+    n_dir = 1 if X_inv is None else 2
+    dev = X_fwd.device
+    out_fwd = _buf((R, D), torch.float32, dev, "rel_text_pool: out_fwd")
+    out_inv = None if X_inv is None else _buf((R, D), torch.float32, dev, "rel_text_pool: out_inv")
+    xbar = _buf((n_dir, R, K), torch.float32, dev, "rel_text_pool: xbar") if save else None
+    alpha = _buf((n_dir, R, T), torch.float32, dev, "rel_text_pool: alpha") if save else None
+    ws = _buf(max(lib.gnnrag_rel_text_workspace_bytes(R, T, K, D, n_dir), 16), torch.uint8, dev,
+              "rel_text_pool: workspace")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_rel_text_pool(X_fwd.data_ptr(), _ptr(X_inv), mask.data_ptr(), W.data_ptr(), b.data_ptr(),
+                                            a.data_ptr(), R, T, K, D, out_fwd.data_ptr(), _ptr(out_inv), _ptr(xbar),
+                                            _ptr(alpha), ws.data_ptr(), ws.numel(), _stream()), "gnnrag_rel_text_pool")
+    return out_fwd, out_inv, xbar, alpha
+
+
+def rel_text_pool_backward(X_fwd, X_inv, W, a, xbar, alpha, g_fwd=None, g_inv=None, need_dW=True, need_db=True,
+                           need_da=True):
+    """Backward of :func:`rel_text_pool` (``gnnrag_rel_text_pool_backward``): X, W, a as given to the forward, xbar / alpha
+    as it returned them, g_fwd / g_inv [R,D] the incoming gradients (None = zeros).  Returns (dW [D,K], db [D], da [D]);
+    an output that is not wanted is None and is not computed.  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    X_fwd, X_inv, W, a, (R, T, K, D) = _rel_text_args(X_fwd, X_inv, W, a)
+    n_dir = 1 if X_inv is None else 2
+    xbar = _chk(xbar, "xbar", shape=(n_dir, R, K))
+    alpha = _chk(alpha, "alpha", shape=(n_dir, R, T))
+    g_fwd = None if g_fwd is None else _chk(g_fwd, "g_fwd", shape=(R, D))
+    g_inv = None if g_inv is None else _chk(g_inv, "g_inv", shape=(R, D))
+    dev = X_fwd.device
+    dW = _buf((D, K), torch.float32, dev, "rel_text_pool_backward: dW") if need_dW else None
+    db = _buf((D,), torch.float32, dev, "rel_text_pool_backward: db") if need_db else None
+    da = _buf((D,), torch.float32, dev, "rel_text_pool_backward: da") if need_da else None
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn inside): query it on X's device
+        ws = _buf(max(lib.gnnrag_rel_text_backward_workspace_bytes(R, T, K, D, n_dir), 16), torch.uint8, dev,
+                  "rel_text_pool_backward: workspace")
+        _lib.check(lib.gnnrag_rel_text_pool_backward(X_fwd.data_ptr(), _ptr(X_inv), W.data_ptr(), a.data_ptr(),
+                                                     xbar.data_ptr(), alpha.data_ptr(), _ptr(g_fwd), _ptr(g_inv), R, T, K,
+                                                     D, _ptr(dW), _ptr(db), _ptr(da), ws.data_ptr(), ws.numel(),
+                                                     _stream()), "gnnrag_rel_text_pool_backward")
+    return dW, db, da
+
+
 def topp_candidates(pred_dist: torch.Tensor, eligible: torch.Tensor, ignore_prob: float, eps: float):
     """Per question: slots kept by the Evaluator's filter, sorted by probability (descending, stable), and
     how many of them the top-p cut retrieves.  Returns (slots int32 [B,N] (-1 padded), counts int32 [B,2])."""

@@ -573,6 +573,56 @@ int gnnrag_instructions(const float* hidden, const float* node, const float* mas
                         const float* w_ca, const float* b_ca, int32_t B, int32_t T, int32_t D, int32_t n_steps,
                         float* ins_out, float* attn_out, gnnrag_stream_t stream);
 
+/* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
+ * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):
+ * question_emb over the frozen LM token states of the relation vocabulary, then AttnEncoder
+ * (gnn/modules/query_update.py:46-61).  Per relation row r and direction, with W [D,K], b [D] = question_emb and
+ * a [D] = self_att_r.attn_linear.weight:
+ *   h_t   = W x_t + b                                              (rearev.py:102-103)
+ *   s_t   = a . h_t = u . x_t + c,   u = W^T a,  c = a . b          (query_update.py:58)
+ *   al    = softmax_t(s_t - (1 - mask[r,t]) * 1e8)                  (:59-60; the fp32 difference as written, row maximum
+ *                                                                    subtracted)
+ *   out_r = sum_t al_t h_t = W xbar_r + b,   xbar_r = sum_t al_t x_t   (:61; sum_t al_t = 1)
+ * A padded token of a row that has tokens gets exactly 0; a row of padding only gets the softmax of the ROUNDED values
+ * s_t - 1e8 (the uniform 1/T while |s| < 4, multiples of 8 beyond), as the reference does.
+ * X_fwd / X_inv [R,T,K] (X_inv NULL: one direction, out_inv must be NULL too), mask [R,T] (1 = token, shared by both
+ * directions: rearev.py:105-106), out_fwd / out_inv [R,D], fully written.  xbar [n_dir,R,K] / alpha [n_dir,R,T]: what the
+ * backward reads, fully written; xbar NULL: forward only, it lives in the workspace; alpha NULL: not stored.
+ * One launch computes u and c (ascending d), one streams X (a workgroup per direction and row, X read from HBM once where
+ * T K + K + 2 ceil4(T) floats fit 80 KB of LDS, else the second use re-reads the row), then out = xbar W^T + b on the
+ * exact-fp32 gnnrag_linear_pair / gnnrag_linear.  One fixed summation order, no atomics, no allocation, nothing waits for
+ * the stream; a row's xbar / alpha bits do not depend on R.
+ * Limits: 1 <= T <= GNNRAG_REL_TEXT_MAX_T, K % 4 == 0 and K <= GNNRAG_REL_TEXT_MAX_K, 1 <= D <= GNNRAG_REL_TEXT_MAX_D,
+ * 1 <= R <= 2^24, X / xbar / workspace 16-byte aligned, else GNNRAG_E_UNSUPPORTED before anything is launched.  A workspace
+ * below gnnrag_rel_text_workspace_bytes(R, T, K, D, n_dir) (0 for a shape outside the limits) is GNNRAG_E_WORKSPACE. */
+#define GNNRAG_REL_TEXT_MAX_T 256
+#define GNNRAG_REL_TEXT_MAX_K 4096
+#define GNNRAG_REL_TEXT_MAX_D 4096
+size_t gnnrag_rel_text_workspace_bytes(int64_t R, int32_t T, int32_t K, int32_t D, int32_t n_dir);
+int gnnrag_rel_text_pool(const float* X_fwd, const float* X_inv, const float* mask, const float* W, const float* b,
+                         const float* a, int64_t R, int32_t T, int32_t K, int32_t D, float* out_fwd, float* out_inv,
+                         float* xbar, float* alpha, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
+/* Backward of the call above: what autograd derives for question_emb.weight, .bias and attn_linear.weight (X is frozen
+ * and gets no gradient).  xbar / alpha as the forward left them, g_fwd / g_inv [R,D] the incoming gradients of out_fwd /
+ * out_inv - either may be NULL (zeros: that direction is not read).  Both directions accumulate, forward first:
+ *   dxbar = g W                                   [R,K]  (gnnrag_linear on a transposed copy of W)
+ *   dal_t = dxbar_r . x_t,   ds_t = al_t (dal_t - sum_t' al_t' dal_t')          (the second streaming pass over X)
+ *   du    = sum_r sum_t ds_t x_t                  [K]   512 workgroups per direction stride over the rows; their partial
+ *                                                       sums are added in 16 slices of workgroup order, slices in order
+ *   dW    = g^T xbar (gnnrag_gemm_tn over the stacked directions, g zero-padded to D % 4 == 0)  +  a (x) du
+ *   db    = sum_r g_r  (row slices in ascending rows, a fixed tree over the slices)        da = W du
+ * c does not move the softmax, so nothing reaches db or da through it; the stored alpha is used on rows of padding too.
+ * dW [D,K], db [D], da [D]: each may be NULL - not wanted, not computed; every requested output is fully written.
+ * No atomics, no allocation, nothing waits for the stream: a repeated call gives the same bits.  Limits as above, dW
+ * 16-byte aligned; a workspace below gnnrag_rel_text_backward_workspace_bytes (which, like gnnrag_gemm_tn_workspace_bytes,
+ * depends on the current device) is GNNRAG_E_WORKSPACE before anything is launched. */
+size_t gnnrag_rel_text_backward_workspace_bytes(int64_t R, int32_t T, int32_t K, int32_t D, int32_t n_dir);
+int gnnrag_rel_text_pool_backward(const float* X_fwd, const float* X_inv, const float* W, const float* a,
+                                  const float* xbar, const float* alpha, const float* g_fwd, const float* g_inv,
+                                  int64_t R, int32_t T, int32_t K, int32_t D, float* dW, float* db, float* da,
+                                  void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
 /* ---- Reasoning paths (additive to ABI 16: new entry points only, nothing above changes) ----------------------------------
  * The retrieval step of GNN-RAG: all shortest paths between the question's entities and the retrieved candidates in the
  * question's subgraph taken as a SIMPLE UNDIRECTED graph - what llm/src/utils/graph_utils.py builds with networkx

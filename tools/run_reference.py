@@ -162,6 +162,15 @@ def main():
         install.patch_instruction(self.model)
 
     evaluate.Evaluator.__init__ = _init_instruction
+    # model.get_rel_feature with --relation_word_emb True: question_emb + AttnEncoder over the relation vocabulary in one
+    # fused call (gnnrag_amd.modules.rel_text; GNNRAG_HIP_REL_TEXT, read at every call, default off)
+    _ev_init2 = evaluate.Evaluator.__init__
+
+    def _init_rel_text(self, *a, **kw):
+        _ev_init2(self, *a, **kw)
+        install.patch_rel_feature(self.model)
+
+    evaluate.Evaluator.__init__ = _init_rel_text
     if world > 1 or force_dist:
         from gnnrag_amd import shard
         _ev_init = evaluate.Evaluator.__init__
