@@ -324,17 +324,39 @@ __global__ __launch_bounds__(512, GNNRAG_TAB_MINBLK) void k_tables_b3(TabArgs a)
 // fragments - no multiply / relu / 3-way split beside the MFMAs (the VALU work that held k_tables_b3 at ~1/3 of the
 // matrix rate; a packed-fp32 VALU instruction beside MFMAs costs far more than its issue slot on this chip), and the
 // k extent is 2 D for every number of instructions I.  The question moves into the RIGHT operand: workgroup =
-// (question, row chunk, direction, column part); it builds V's three planes for its column part and one half at a
-// time in LDS (I weight blocks x the question's instruction rows; same layout as above), all row tiles of the
-// question (<= 5 per wave: one pass at C2) multiply against them with the accumulators held across both halves.
-// Same 6 plane products and fp32 accumulation as above; V is rounded to fp32 once per element before its exact split.
+// (question, row chunk, direction, column part); it builds V's three planes for its column part in LDS, a range of k
+// at a time (I weight blocks x the question's instruction rows), all row tiles of the question (<= 5 per wave: one
+// pass at C2) multiply against them with the accumulators held across the ranges.  Same 6 plane products and fp32
+// accumulation as above; V is rounded to fp32 once per element before its exact split.
+//
+// The product runs on the 2:4 structured-sparse instruction.  Of relu(T)[r, k] and relu(-T)[r, k] at most one is not
+// zero, so with K interleaved as k+, k-, (k+1)+, (k+1)- every group of four holds at most two non-zeros, one from each
+// (+, -) pair: the form v_smfmac_f32_16x16x64_bf16 takes.  Its compressed left operand is the planes of |T| - plane+
+// OR plane-, bit for bit, because the half that is zero holds 0x0000 in all three planes - and the 2-bit positions are
+// the signs of T, read off the - half (vq_compress); one index word serves all three planes.  7 sparse blocks of 32 k
+// replace 14 dense ones per (row tile, column tile, plane product).  The relation planes stay as k_rel_transform writes
+// them ([+ half | - half], kVqHalf apart); V is what gets interleaved, by the staging (vq_stage), in k ranges of 3, 3
+// and 1 blocks - a whole interleaved row does not fit the planes' LDS.  B fragments cost the same LDS bytes per k as
+// before against half the matrix-pipe time, so two row tiles share each one (one column tile at a time, the two
+// tiles' accumulator chains alternating) where the dense form took two column tiles of one row tile.
+//
+// What the instruction expects, as measured by tools/probe/smfmac_probe.hip (profiles/r07a_smfmac_probe.txt):
+//   * A (compressed, 8 bf16 per lane): lane l holds compressed k 8 (l / 16) .. + 7 of row l % 16; compressed k c belongs
+//     to the group of four c / 2 and lands at interleaved K 4 (c / 2) + its 2-bit position;
+//   * the positions of the lane's 8 values are 16 bits of the index register, element e at bits 2 e; abid selects the
+//     half of the register (abid 0: bits 15:0), the other 16 bits are ignored;
+//   * B (dense, 16 bf16 per lane) comes in TWO halves of 32 K, not as 16 contiguous K: elements 0-7 are K 8 (l / 16)
+//     .. + 7, elements 8-15 are K 32 + 8 (l / 16) .. + 7, of column l % 16;
+//   * the accumulator is the dense 16x16 one: rows 4 (l / 16) + q, column l % 16;
+//   * rate: 8 independent accumulators, one or two waves per SIMD: 1.08 - 1.13 x the time of v_mfma_f32_16x16x32_bf16
+//     per instruction, i.e. 1.77 - 1.86 x its K rate.
 constexpr int kVqHalf = 32 * kTabNKB;          // bf16 elements per half row of the relation planes (224: k >= D are zero)
 constexpr int kVqRowB = 2 * kVqHalf * 2;       // bytes per plane row: [relu(T) | relu(-T)]
 #ifndef GNNRAG_VQ_TPW
 #define GNNRAG_VQ_TPW 5
 #endif
 #ifndef GNNRAG_VQ_UN
-#define GNNRAG_VQ_UN 3
+#define GNNRAG_VQ_UN 2       // staging pieces per thread and round (3 spills beside the 140 accumulators)
 #endif
 constexpr int kVqTPW = GNNRAG_VQ_TPW;          // row tiles per wave and pass
 
@@ -353,53 +375,119 @@ struct VqArgs {
   int64_t zero_n;
 };
 
-// V planes of one half and one column part -> LDS:  V[n, k] = sum_i W[col0 + n, (1 + 2 i + d) D + k] * max(+-ins[g, i, k], 0)
-// UN pieces (4 k each) per thread and round; indices are recomputed rather than kept (register pressure)
+typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
+constexpr int kVqSub = 3 * 64;                 // byte offset of the second sub-plane in a V plane row (see vq_stage)
+
+// (V+[k], V-[k]) dwords of 4 consecutive k from the packed planes of V+ and V-
+__device__ __forceinline__ uint4 vq_interleave(uint2 p, uint2 n) {
+  return make_uint4((p.x & 0xffffu) | (n.x << 16), (p.x >> 16) | (n.x & 0xffff0000u), (p.y & 0xffffu) | (n.y << 16),
+                    (p.y >> 16) | (n.y & 0xffff0000u));
+}
+// the lane's B fragment of one plane: 16 bytes from each sub-plane (see vq_stage)
+__device__ __forceinline__ bf16x16 vq_read_b(const unsigned char* p) {
+  struct { f32x4 lo, hi; } v = {*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + kVqSub)};
+  return __builtin_bit_cast(bf16x16, v);
+}
+
+// row of (row, block) slot x when a row has nb = 3 or 1 blocks (x < 43690)
+__device__ __forceinline__ int vq_row(int x, int nb) { return nb == 3 ? (int)(((unsigned)x * 43691u) >> 17) : x; }
+
+// V planes of nb k blocks (32 k each, from block blk0) and one column part -> LDS, in the interleaved order of the sparse
+// product:  V+[n, k] = sum_i W[col0 + n, (1 + 2 i + d) D + k] * max(ins[g, i, k], 0),  V-[n, k] the same with -ins; one
+// dword holds (V+[n, k], V-[n, k]), so both signs of a k come from one read of W and ins.  Row n of a plane (kTabSlots
+// x 16 B) holds two sub-planes of 3 x 64 B (a stage of one block fills a third of each): the lane of k-group fg reads
+// the dwords of k = 4 fg .. 4 fg + 3 of a block from sub-plane 0 and those of k = 16 + 4 fg .. + 3 from sub-plane 1
+// (kVqSub further: the instruction takes B in two halves of 32 interleaved K), each at row * RB + block * 64 + fg * 16 - the bank pattern of the dense kernels' fragment reads,
+// conflict free; the lane's 32 bytes in one piece (fg * 32) would put lanes 4-11 of a ds_read_b128 group on the
+// banks of lanes 0-3 and 12-15 at the 416-byte row stride: 2-way.  UN pieces (4 k: 16 bytes per plane) per thread and
+// round; indices are recomputed rather than kept (register pressure).  Pieces with k >= D and columns past the part
+// are written as zeros: every byte the fragment reads touch is written by the stage that precedes them (the reads
+// stay inside the staged rows: no slack row as in the dense kernels).
 template <int CTN, int UN>
 __device__ __forceinline__ void vq_stage(const VqArgs& a, unsigned char* lds, const float* qarea, int col0, int ncol,
-                                         int d, int s) {
+                                         int d, int blk0, int nb) {
   constexpr int RB = kTabSlots * 16;
   constexpr int PL = kTabNTH * 16 * RB;
+  const int total = CTN * 16 * 8 * nb;                          // 8 pieces per (row, block); nb is 3 or 1
   const int tid = threadIdx.x;
   const int D = a.D, I = a.I, KC = D >> 2;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  const int total = tab_stage_rows(CTN) * kTabSlots * 2;        // 8-byte pieces (4 k) per plane
   for (int base = 0; base < total; base += 512 * UN) {
-    f32x4 v[UN];
+    f32x4 vp[UN], vn[UN];
 #pragma unroll
-    for (int u = 0; u < UN; ++u) v[u] = zero4;
+    for (int u = 0; u < UN; ++u) vp[u] = vn[u] = zero4;
     for (int i = 0; i < I; ++i) {
       f32x4 w[UN];
       const float* wsrc = a.W + (size_t)col0 * a.ldw + (1 + 2 * i + d) * D;
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
         const int idx = base + u * 512 + tid;
-        const int j = idx / (kTabSlots * 2), kc = idx - j * (kTabSlots * 2);
-        // dead pieces (k >= D, columns past the part) read a valid address and are zeroed below
+        const int j = vq_row(idx >> 3, nb), kc = (blk0 + (idx >> 3) - j * nb) * 8 + (idx & 7);
+        // dead pieces (k >= D, columns past the part, idx >= total) read a valid address and are zeroed / skipped below
         w[u] = *reinterpret_cast<const f32x4*>(wsrc + (size_t)min(j, ncol - 1) * a.ldw + 4 * min(kc, KC - 1));
       }
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
         const int idx = base + u * 512 + tid;
-        const int kc = idx % (kTabSlots * 2);
-        f32x4 q = *reinterpret_cast<const f32x4*>(qarea + i * D + 4 * min(kc, KC - 1));
-        q = __builtin_elementwise_max(s ? -q : q, zero4);
-        v[u] += w[u] * q;
+        const int kc = (blk0 + (idx >> 3) - vq_row(idx >> 3, nb) * nb) * 8 + (idx & 7);
+        const f32x4 q = *reinterpret_cast<const f32x4*>(qarea + i * D + 4 * min(kc, KC - 1));
+        vp[u] += w[u] * __builtin_elementwise_max(q, zero4);
+        vn[u] += w[u] * __builtin_elementwise_max(-q, zero4);
       }
     }
 #pragma unroll
     for (int u = 0; u < UN; ++u) {
       const int idx = base + u * 512 + tid;
-      const int j = idx / (kTabSlots * 2), kc = idx - j * (kTabSlots * 2);
+      const int j = vq_row(idx >> 3, nb), b = (idx >> 3) - j * nb, pc = idx & 7, kc = (blk0 + b) * 8 + pc;
       if (idx < total) {
-        const Split3 sp = split3(j < ncol && kc < KC ? v[u] : zero4);
-        unsigned char* dst = lds + tab_lds_row(j) * RB + kc * 8;
-        *reinterpret_cast<uint2*>(dst) = sp.hi;
-        *reinterpret_cast<uint2*>(dst + PL) = sp.mid;
-        *reinterpret_cast<uint2*>(dst + 2 * PL) = sp.lo;
+        const bool live = j < ncol && kc < KC;
+        const Split3 sp = split3(live ? vp[u] : zero4), sn = split3(live ? vn[u] : zero4);
+        unsigned char* dst = lds + tab_lds_row(j) * RB + (pc >> 2) * kVqSub + b * 64 + (pc & 3) * 16;
+        *reinterpret_cast<uint4*>(dst) = vq_interleave(sp.hi, sn.hi);
+        *reinterpret_cast<uint4*>(dst + PL) = vq_interleave(sp.mid, sn.mid);
+        *reinterpret_cast<uint4*>(dst + 2 * PL) = vq_interleave(sp.lo, sn.lo);
       }
     }
   }
+}
+
+// The lane's operands of one (row tile, k block) for the sparse product: the three planes of |T| and the index word.
+struct VqA {
+  bf16x8 pl[3];
+  int idx;
+};
+// ... as they arrive from the relation planes: the lane's 16 bytes of the + half and of the - half of each plane
+struct VqRaw {
+  uint4 p[3], n[3];
+};
+__device__ __forceinline__ VqRaw vq_load_a(const unsigned char* const (&plane_base)[3], unsigned off) {
+  VqRaw r;
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+    r.p[pl] = *reinterpret_cast<const uint4*>(plane_base[pl] + off);
+    r.n[pl] = *reinterpret_cast<const uint4*>(plane_base[pl] + (off + (unsigned)(kVqHalf * 2)));
+  }
+  return r;
+}
+// |T|'s planes are plane+ OR plane- (the half that is zero holds 0 in all three planes); the 2-bit index of the lane's
+// compressed element e sits at bits 2 e of the index word: element 2 i (the first of group i) is at position 0 (+) or
+// 1 (-) of its group of four, element 2 i + 1 at position 2 (+) or 3 (-) - always ascending.  "-" is decided on
+// hi | mid | lo of the - half, so a value whose hi plane is zero still selects its own half of V.
+__device__ __forceinline__ VqA vq_compress(const VqRaw& r) {
+  VqA o;
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl) {
+    const uint4 c = make_uint4(r.p[pl].x | r.n[pl].x, r.p[pl].y | r.n[pl].y, r.p[pl].z | r.n[pl].z, r.p[pl].w | r.n[pl].w);
+    o.pl[pl] = __builtin_bit_cast(bf16x8, c);
+  }
+  const unsigned m[4] = {r.n[0].x | r.n[1].x | r.n[2].x, r.n[0].y | r.n[1].y | r.n[2].y, r.n[0].z | r.n[1].z | r.n[2].z,
+                         r.n[0].w | r.n[1].w | r.n[2].w};
+  unsigned ix = 0x8888u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)      // (min with 1, shifts and ors with inline constants: selects would hold their masks in registers)
+    ix |= (min(m[i] & 0xffffu, 1u) | (min(m[i] >> 16, 1u) << 2)) << (4 * i);
+  o.idx = (int)ix;
+  return o;
 }
 
 template <int CTN>
@@ -407,6 +495,7 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
   constexpr int RB = kTabSlots * 16;
   constexpr int PL = kTabNTH * 16 * RB;
   constexpr int NKB = kTabNKB;
+  constexpr int NPAIR = (kVqTPW + 1) / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
   const int d = a.dir0 + blockIdx.y;
@@ -415,7 +504,6 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
   const int r0 = a.rel_off[g], r1 = a.rel_off[g + 1];
   if (r1 <= r0) return;                                       // a question without facts has no rows
   const int ncol = min(CTN * 16, D - col0);
-  const int KC = D >> 2;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   float* P = a.P + (size_t)d * a.M * D;
   const unsigned char* planes = a.planes + (size_t)d * 3 * a.R1 * kVqRowB;
@@ -428,7 +516,6 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
   const int w0 = c0 + (c1 - c0) * wv / 8, w1 = c0 + (c1 - c0) * (wv + 1) / 8;
   const int npass = ((c1 - c0 + 7) / 8 + kVqTPW - 1) / kVqTPW;     // workgroup-uniform (the barriers below)
 
-  if (tid < 16) reinterpret_cast<unsigned*>(lds + 3 * PL)[tid] = 0u;   // slack behind the last plane stays finite
   float* qarea = reinterpret_cast<float*>(lds + 3 * PL + 64);          // ins[g, :, :]
   for (int x = tid * 4; x < I * D; x += 512 * 4)
     *reinterpret_cast<f32x4*>(qarea + x) = *reinterpret_cast<const f32x4*>(a.ins + (size_t)g * I * D + x);
@@ -450,49 +537,55 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
     }
     const unsigned char* const plane_base[3] = {planes, planes + plane_stride, planes + 2 * plane_stride};
 
-    for (int s = 0; s < 2; ++s) {           // (rolled: the peeled form spills ~300 registers)
-      __syncthreads();                                        // q rows staged / the previous half's fragment reads done
-      // ---- V planes of this half ----
-      vq_stage<CTN, GNNRAG_VQ_UN>(a, lds, qarea, col0, ncol, d, s);
+    // A operands are requested where they are used: the pair's 12 plane loads (L2 hits) go out together and the other
+    // wave of the SIMD has a pair's products (84 instructions) to issue meanwhile.  Holding the next pair's raw loads
+    // beside the pair in use (48 registers, or 37 in a two-step form) spills: 140 accumulators + 26 A + 2 x 24 B.
+    for (int s = 0; s < 3; ++s) {           // k blocks 0-2, 3-5, 6 (rolled: register pressure)
+      __syncthreads();                                        // q rows staged / the previous stage's fragment reads done
+      const int nblk = s < 2 ? 3 : 1;
+      vq_stage<CTN, GNNRAG_VQ_UN>(a, lds, qarea, col0, ncol, d, 3 * s, nblk);
       __syncthreads();
-
-      // ---- MFMA phase: a tile's A fragments of k block kb + 1 are requested as soon as its MFMAs of kb are issued,
-      // i.e. the other tiles' MFMAs (kVqTPW - 1 times 6 CTN) before their use ----
-      bf16x8 ap[kVqTPW][3];
-#pragma unroll
-      for (int j = 0; j < kVqTPW; ++j)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl)
-          ap[j][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(plane_base[pl] + (aoff[j] + (unsigned)(s * (kVqHalf * 2)))));
-      for (int kb = 0; kb < NKB; ++kb) {        // (not unrolled: register pressure)
-        const int kbn = min(kb + 1, NKB - 1);   // (the last block requests itself again: no branch around a load)
+      for (int kb = 0; kb < nblk; ++kb) {       // (not unrolled: register pressure)
+        const int blk = 3 * s + kb;
         const unsigned char* wb = lds + fr * RB + kb * 64 + fg * 16;
         constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
         constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
 #pragma unroll
-        for (int j = 0; j < kVqTPW; ++j) {
-          if (j < ntile) {                                    // wave-uniform
+        for (int p = 0; p < NPAIR; ++p) {
+          const int j0 = 2 * p, j1 = 2 * p + 1 < kVqTPW ? 2 * p + 1 : 2 * p;
+          const bool two = 2 * p + 1 < kVqTPW;
+          VqA cur[2];
+          {
+            cur[0] = vq_compress(vq_load_a(plane_base, aoff[j0] + (unsigned)(blk * 64)));
+            cur[1] = two ? vq_compress(vq_load_a(plane_base, aoff[j1] + (unsigned)(blk * 64))) : cur[0];
+          }
+          // wave-uniform.  Two row tiles share every B fragment; a slot whose second tile is past the wave's run still
+          // computes it (never stored: at most one tile per wave and k block for nothing, none with 4 or 5 tiles as at
+          // C2) - a third branch for it sinks the second tile's loads behind the branch, where they are issued one at
+          // a time, each waiting for the one before
+          if (two && j0 < ntile) {
 #pragma unroll
-            for (int nt = 0; nt < CTN; nt += 2) {
-              bf16x8 b0[3], b1[3];
+            for (int nt = 0; nt < CTN; ++nt) {
+              bf16x16 b[3];
 #pragma unroll
-              for (int pl = 0; pl < 3; ++pl) {
-                b0[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wb + pl * PL + nt * 16 * RB));
-                b1[pl] = b0[pl];
-                if (nt + 1 < CTN)
-                  b1[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wb + pl * PL + (nt + 1) * 16 * RB));
-              }
+              for (int pl = 0; pl < 3; ++pl) b[pl] = vq_read_b(wb + pl * PL + nt * 16 * RB);
 #pragma unroll
-              for (int p = 0; p < 6; ++p) {
-                acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[j][PA[p]], b0[PB[p]], acc[j][nt], 0, 0, 0);
-                if (nt + 1 < CTN)
-                  acc[j][nt + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[j][PA[p]], b1[PB[p]], acc[j][nt + 1], 0, 0, 0);
+              for (int q = 0; q < 6; ++q) {
+                acc[j0][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[0].pl[PA[q]], b[PB[q]], acc[j0][nt], cur[0].idx, 0, 0);
+                acc[j1][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[1].pl[PA[q]], b[PB[q]], acc[j1][nt], cur[1].idx, 0, 0);
               }
             }
-          }
+          } else if (!two && j0 < ntile) {                  // the odd last row tile
 #pragma unroll
-          for (int pl = 0; pl < 3; ++pl)                      // refill: this tile's fragments of the next k block
-            ap[j][pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(plane_base[pl] + (aoff[j] + (unsigned)(s * (kVqHalf * 2) + kbn * 64))));
+            for (int nt = 0; nt < CTN; ++nt) {
+              bf16x16 b[3];
+#pragma unroll
+              for (int pl = 0; pl < 3; ++pl) b[pl] = vq_read_b(wb + pl * PL + nt * 16 * RB);
+#pragma unroll
+              for (int q = 0; q < 6; ++q)
+                acc[j0][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[0].pl[PA[q]], b[PB[q]], acc[j0][nt], cur[0].idx, 0, 0);
+            }
+          }
         }
       }
     }

@@ -29,7 +29,7 @@ VARIANTS = {
     "sl_t512_g1": {"GNNRAG_SLICE_THREADS": 512, "GNNRAG_SLICE_WPE": 4, "GNNRAG_SLICE_BL_GROUP": 1},
     "sl_t768": {"GNNRAG_SLICE_THREADS": 768, "GNNRAG_SLICE_WPE": 6},
     "sl_t640": {"GNNRAG_SLICE_THREADS": 640, "GNNRAG_SLICE_WPE": 5},
-    "vq_un2": {"GNNRAG_VQ_UN": 2}, "vq_un4": {"GNNRAG_VQ_UN": 4},      # tables_b3.hip: V pieces in flight while staging
+    "vq_un3": {"GNNRAG_VQ_UN": 3}, "vq_un4": {"GNNRAG_VQ_UN": 4},      # tables_b3.hip: V pieces in flight while staging
     # gather walk (tables larger than LDS, BASELINE config 5; GNNRAG_TUNE_WORKLOAD=C5)
     "light_npw1": {"GNNRAG_LIGHT_NPW": 1}, "light_npw4": {"GNNRAG_LIGHT_NPW": 4},
     "quad_off": {"GNNRAG_LIGHT_QUAD": 0}, "quad_s2": {"GNNRAG_QUAD_STEPS": 2}, "quad_unmerged": {"GNNRAG_QUAD_MERGED": 0},
