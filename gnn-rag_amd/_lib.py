@@ -48,6 +48,12 @@ class UGraphStruct(C.Structure):
                 ("u_ptr", C.c_void_p), ("u_adj", C.c_void_p)]
 
 
+class DenseFormStruct(C.Structure):
+    """Mirror of ``struct gnnrag_dense_form_t`` (include/gnnrag.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "block_family", "launches", "epi", "nt", "mt", "v4", "math", "nw",
+                                          "v4out", "n0", "nc", "has_add", "kguard")]
+
+
 class LayerParams(C.Structure):
     """Mirror of ``struct gnnrag_layer_params`` (include/gnnrag.h)."""
     _fields_ = [("W_rel", C.c_void_p), ("b_rel", C.c_void_p), ("pos_fwd", C.c_void_p), ("pos_inv", C.c_void_p),
@@ -109,6 +115,9 @@ SIGNATURES = {
                                             C.c_int32, C.c_int32, _VP]),
     "gnnrag_update_score": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32,
                                       C.c_int32, C.c_int32, _VP]),
+    # which kernel a dense call runs (host only; additive to ABI 16)
+    "gnnrag_dense_form": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                    C.c_int32, C.c_int32, C.POINTER(DenseFormStruct)]),
     "gnnrag_masked_softmax": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP]),
     "gnnrag_typelayer": (C.c_int, [C.POINTER(CsrStruct), _VP, C.c_int, _VP, C.c_int32, _VP, C.c_size_t, _VP]),
     "gnnrag_layer_workspace_bytes": (C.c_size_t, [C.POINTER(CsrStruct), C.c_int32, C.c_int32]),

@@ -721,6 +721,26 @@ static int wres_stride(const GemmArgs& g) {
   return S;
 }
 
+// ---- dispatch: what ONE place decides ----------------------------------------------------------------------------------
+// The launchers below switch on a DenseForm; gnnrag_dense_form (host only) reports the same struct, so a test can name
+// the kernel a shape runs on.  gemm_form / wres_class / update_form are the only holders of the selection rules.
+struct DenseForm {
+  int family, block_family;               // GNNRAG_DENSE_*
+  int epi, nt, mt, v4, math, nw, v4out, n0;   // k_gemm_f32 template arguments and its two runtime switches
+  int nc, has_add, kguard, afl, S;        // k_gemm_wres template arguments and its LDS row stride
+};
+
+// (NT, NC) class and the compile-time switches of k_gemm_wres; false: no compiled class takes the shape
+static bool wres_class(const GemmArgs& g, DenseForm* f) {
+  const int nc = (g.K + 15) / 16, nt = (g.Nout + 15) / 16;
+  const int cls = (nt <= 4 && nc <= 4) ? 4 : (nt <= 8 && nc <= 8) ? 8 : (nt <= 13 && nc <= 13) ? 13 : 0;
+  f->nt = f->nc = cls;
+  f->has_add = g.add != nullptr;
+  f->afl = g.add && g.add_flag;
+  f->kguard = cls && g.K <= 16 * (cls - 1);
+  return cls != 0;
+}
+
 template <int EPI>
 static int launch_wres(const GemmArgs& g, int S, hipStream_t stream) {
   int cus = 0;
@@ -733,7 +753,8 @@ static int launch_wres(const GemmArgs& g, int S, hipStream_t stream) {
   if (grid * 8 > tiles) grid = (tiles + 7) / 8;
   const int LR = wres_rows(g.Nout, g.K);
   const size_t lds = (size_t)LR * S * 16 + (size_t)g.Nout * 8;           // W (ColMap rows), bias, score weights
-  const int nc = (g.K + 15) / 16, nt = (g.Nout + 15) / 16;
+  DenseForm f;
+  if (!wres_class(g, &f)) return GNNRAG_E_UNSUPPORTED;
 #define GNNRAG_WRES1(NTT, NCC, HA, KG, FL)                                                                      \
   do {                                                                                                          \
     static DeviceMask cap;                                                                                      \
@@ -743,18 +764,16 @@ static int launch_wres(const GemmArgs& g, int S, hipStream_t stream) {
   } while (0)
 #define GNNRAG_WRES(NTT, NCC)                                                                                   \
   do {                                                                                                          \
-    const bool kg = g.K <= 16 * (NCC - 1);                                                                      \
-    if (g.add && g.add_flag && kg) GNNRAG_WRES1(NTT, NCC, true, true, true);                                    \
-    else if (g.add && g.add_flag) GNNRAG_WRES1(NTT, NCC, true, false, true);                                    \
-    else if (g.add && kg) GNNRAG_WRES1(NTT, NCC, true, true, false);                                            \
-    else if (g.add) GNNRAG_WRES1(NTT, NCC, true, false, false);                                                 \
-    else if (kg) GNNRAG_WRES1(NTT, NCC, false, true, false);                                                    \
+    if (f.afl && f.kguard) GNNRAG_WRES1(NTT, NCC, true, true, true);                                            \
+    else if (f.afl) GNNRAG_WRES1(NTT, NCC, true, false, true);                                                  \
+    else if (f.has_add && f.kguard) GNNRAG_WRES1(NTT, NCC, true, true, false);                                  \
+    else if (f.has_add) GNNRAG_WRES1(NTT, NCC, true, false, false);                                             \
+    else if (f.kguard) GNNRAG_WRES1(NTT, NCC, false, true, false);                                              \
     else GNNRAG_WRES1(NTT, NCC, false, false, false);                                                           \
   } while (0)
-  if (nt <= 4 && nc <= 4) GNNRAG_WRES(4, 4);
-  else if (nt <= 8 && nc <= 8) GNNRAG_WRES(8, 8);
-  else if (nt <= 13 && nc <= 13) GNNRAG_WRES(13, 13);
-  else return GNNRAG_E_UNSUPPORTED;
+  if (f.nt == 4) GNNRAG_WRES(4, 4);
+  else if (f.nt == 8) GNNRAG_WRES(8, 8);
+  else GNNRAG_WRES(13, 13);
 #undef GNNRAG_WRES
 #undef GNNRAG_WRES1
   GNNRAG_LAUNCH_CHECK();
@@ -924,21 +943,22 @@ static int launch_update_skinny(const GemmArgs& g, hipStream_t stream) {
 
 static bool math_ok(int math) { return math == GNNRAG_MATH_FP32 || math == GNNRAG_MATH_BF16X3 || math == GNNRAG_MATH_MIXED; }
 
-template <int EPI, int AMODE>
-static int launch_gemm(GemmArgs g, hipStream_t stream, int math) {
-  if (g.M <= 0) return 0;
-  const bool v4 = (g.K % 4 == 0) && (g.K0 % 4 == 0) && (g.ldw % 4 == 0) && (g.wc0 % 4 == 0) &&
-                  aligned16(g.A0) && aligned16(g.W) && (g.A1 == nullptr || aligned16(g.A1)) &&
-                  (g.C_b == nullptr || aligned16(g.A0b)) &&
-                  (AMODE != AMODE_GEN || g.gen_D % 4 == 0);
-  if (EPI == EPI_LINEAR && AMODE == AMODE_PLAIN && g.M <= kSkinnyMaxM && g.n0 == 0) {
-    const dim3 grid((g.M + 15) / 16, (g.Nout + 255) / 256, g.C_b ? 2 : 1);
-    if (v4) hipLaunchKernelGGL((k_gemm_skinny<true>), grid, dim3(256), 0, stream, g);
-    else hipLaunchKernelGGL((k_gemm_skinny<false>), grid, dim3(256), 0, stream, g);
-    GNNRAG_LAUNCH_CHECK();
-    return 1 << 30;   // "all columns done" marker for the column-block loop of the caller
+// Form of ONE k_gemm_skinny / k_gemm_f32 launch (g.n0 = the launch's column block).
+static DenseForm gemm_form(const GemmArgs& g, int epi, int amode, int math) {
+  DenseForm f;
+  memset(&f, 0, sizeof(f));
+  f.epi = epi;
+  f.n0 = g.n0;
+  f.v4 = (g.K % 4 == 0) && (g.K0 % 4 == 0) && (g.ldw % 4 == 0) && (g.wc0 % 4 == 0) &&
+         aligned16(g.A0) && aligned16(g.W) && (g.A1 == nullptr || aligned16(g.A1)) &&
+         (g.C_b == nullptr || aligned16(g.A0b)) &&
+         (amode != AMODE_GEN || g.gen_D % 4 == 0);
+  if (epi == EPI_LINEAR && amode == AMODE_PLAIN && g.M <= kSkinnyMaxM && g.n0 == 0) {
+    f.family = f.block_family = GNNRAG_DENSE_SKINNY;      // one launch finishes every column block of the call
+    return f;
   }
-  const int ny = AMODE == AMODE_GEN ? 2 : 1;
+  f.family = f.block_family = GNNRAG_DENSE_KTILED;
+  const int ny = amode == AMODE_GEN ? 2 : 1;
   // 128-row tiles unless they would leave the chip badly quantised (2 workgroups per CU = 512 slots):
   // mid-size problems (a few hundred tiles) run as twice as many 64-row tiles
   const int tiles128 = ((g.M + 127) / 128) * ny;
@@ -949,36 +969,143 @@ static int launch_gemm(GemmArgs g, hipStream_t stream, int math) {
   const int t8 = tiles128;
   const bool nw8 = small_tiles && (t8 >= 3 * slots8 / 2 || (t8 % slots8 == 0) || (t8 % slots8) > slots8 / 2) &&
                    GNNRAG_GEMM_MT1_NW == 8;
-  const int bm = small_tiles ? (nw8 ? 128 : 64) : 128;
-  const dim3 grid((g.M + bm - 1) / bm, ny);
+  f.mt = small_tiles ? 1 : 2;
+  f.nw = nw8 ? 8 : 4;
+  // MIXED: the k-tiled kernel runs its bf16x3 form; the scalar loaders exist in the exact-fp32 form only
+  f.math = f.v4 && math != GNNRAG_MATH_FP32;
+  f.v4out = (g.Nout % 4 == 0) && (g.n0 % 4 == 0) && aligned16(g.C) && (g.add == nullptr || aligned16(g.add));
   const int ncol = g.Nout - g.n0;
-  const bool b3 = math != GNNRAG_MATH_FP32;       // MIXED: the k-tiled kernel runs its bf16x3 form
-  g.v4out = (g.Nout % 4 == 0) && (g.n0 % 4 == 0) && aligned16(g.C) && (g.add == nullptr || aligned16(g.add));
+  f.nt = ncol <= 64 ? 4 : ncol <= 128 ? 8 : 13;
+  return f;
+}
+
+template <int EPI, int AMODE>
+static int launch_gemm(GemmArgs g, hipStream_t stream, int math) {
+  if (g.M <= 0) return 0;
+  const DenseForm f = gemm_form(g, EPI, AMODE, math);
+  if (f.family == GNNRAG_DENSE_SKINNY) {
+    const dim3 grid((g.M + 15) / 16, (g.Nout + 255) / 256, g.C_b ? 2 : 1);
+    if (f.v4) hipLaunchKernelGGL((k_gemm_skinny<true>), grid, dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL((k_gemm_skinny<false>), grid, dim3(256), 0, stream, g);
+    GNNRAG_LAUNCH_CHECK();
+    return 1 << 30;   // "all columns done" marker for the column-block loop of the caller
+  }
+  const int bm = 16 * f.mt * f.nw;
+  const dim3 grid((g.M + bm - 1) / bm, AMODE == AMODE_GEN ? 2 : 1);
+  g.v4out = f.v4out;
 #define GNNRAG_GEMM_LAUNCH(NT, MT, V, MATH, NW) \
   hipLaunchKernelGGL((k_gemm_f32<NT, MT, V, EPI, AMODE, MATH, NW>), grid, dim3(64 * NW), 0, stream, g)
 #define GNNRAG_GEMM_CASE(NT)                                                        \
   do {                                                                              \
-    if (small_tiles && nw8) {                                                       \
-      if (v4 && b3) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 8);                          \
-      else if (v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 8);                           \
+    if (f.mt == 1 && f.nw == 8) {                                                   \
+      if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 8);                    \
+      else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 8);                         \
       else GNNRAG_GEMM_LAUNCH(NT, 1, false, 0, 8);                                  \
-    } else if (small_tiles) {                                                       \
-      if (v4 && b3) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 4);                          \
-      else if (v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 4);                           \
+    } else if (f.mt == 1) {                                                         \
+      if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 4);                    \
+      else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 4);                         \
       else GNNRAG_GEMM_LAUNCH(NT, 1, false, 0, 4);                                  \
     } else {                                                                        \
-      if (v4 && b3) GNNRAG_GEMM_LAUNCH(NT, 2, true, 1, 4);                          \
-      else if (v4) GNNRAG_GEMM_LAUNCH(NT, 2, true, 0, 4);                           \
+      if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 2, true, 1, 4);                    \
+      else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 2, true, 0, 4);                         \
       else GNNRAG_GEMM_LAUNCH(NT, 2, false, 0, 4);                                  \
     }                                                                               \
   } while (0)
-  if (ncol <= 64) GNNRAG_GEMM_CASE(4);
-  else if (ncol <= 128) GNNRAG_GEMM_CASE(8);
+  if (f.nt == 4) GNNRAG_GEMM_CASE(4);
+  else if (f.nt == 8) GNNRAG_GEMM_CASE(8);
   else GNNRAG_GEMM_CASE(13);
 #undef GNNRAG_GEMM_CASE
 #undef GNNRAG_GEMM_LAUNCH
   GNNRAG_LAUNCH_CHECK();
   return 0;
+}
+
+// Form of a self-block / concatenated update (both gnnrag_update_score* entry points): family, and for the k-tiled and
+// W-resident kernels their template arguments.  GNNRAG_DENSE_NONE: no kernel takes the call (row gates on a shape
+// whose kernel has no gated form).  WIDE: block_family .. n0 describe the column block g.n0.
+static DenseForm update_form(const GemmArgs& g_in, int64_t BN, int32_t D, int math) {
+  GemmArgs g = g_in;
+  DenseForm f;
+  memset(&f, 0, sizeof(f));
+  if (D <= 208) {
+    g.n0 = 0;
+    // short K, exact fp32, aligned operands: the W-resident kernel (whole weight block in LDS)
+    const bool al = aligned16(g.A0) && aligned16(g.W) && aligned16(g.C) && (!g.add || aligned16(g.add)) &&
+                    g.ldw % 4 == 0 && g.wc0 % 4 == 0 && (!g.add || g.add_rows >= g.M);
+    const bool flag_ok = !g.add_flag || ((uintptr_t)g.add_flag & 3) == 0;
+    if (GNNRAG_UPDATE_B3 && math != GNNRAG_MATH_FP32 && al && g.add && !g.A1 && g.K == D && flag_ok &&
+        update_b3_shape_ok(BN, D, g.ldw)) {
+      f.family = f.block_family = GNNRAG_DENSE_UPDATE_B3;
+      return f;
+    }
+    const int S = (GNNRAG_GEMM_WRES && math != GNNRAG_MATH_BF16X3 && al && g.M >= 4096 && flag_ok) ? wres_stride(g) : 0;
+    if (S && wres_class(g, &f)) {
+      f.family = f.block_family = GNNRAG_DENSE_WRES;
+      f.S = S;
+      return f;
+    }
+    if (GNNRAG_UPDATE_SKINNY && update_skinny_ok(g)) {      // small batches: exact fp32
+      f.family = f.block_family = GNNRAG_DENSE_UPDATE_SKINNY;
+      return f;
+    }
+    if (g.add_flag) return f;                                // the k-tiled kernel has no row-gated form: nothing launched
+    return gemm_form(g, EPI_UPDATE, AMODE_PLAIN, math);
+  }
+  if (g.add_flag) return f;
+  // wide hidden sizes: column blocks of 208 with bias(+add)+ReLU epilogue, then a row-dot for the score
+  g.relu = 1;
+  f = gemm_form(g, EPI_LINEAR, AMODE_PLAIN, math);
+  f.family = GNNRAG_DENSE_WIDE;
+  return f;
+}
+
+// ---- the entry points' kernel arguments (shared with gnnrag_dense_form, which fills in stand-in pointers) ------------
+static GemmArgs linear_args(const float* A, int64_t M, int32_t K, const float* W, const float* bias, const float* add,
+                            int64_t add_rows, int relu, float* C, int32_t Nout) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A0 = A; g.W = W; g.bias = bias; g.add = add; g.C = C;
+  g.M = (int32_t)M; g.K = K; g.K0 = K; g.Nout = Nout; g.ldw = K;
+  g.add_rows = add ? (int32_t)(add_rows < M ? add_rows : M) : 0;
+  g.relu = relu;
+  return g;
+}
+
+// gnnrag_linear_pair above the skinny bound is two gnnrag_linear calls
+static bool pair_is_two_calls(int64_t M) { return M > kSkinnyMaxM; }
+
+static GemmArgs pair_args(const float* A0, const float* A1, int64_t M, int32_t K, const float* W, const float* bias,
+                          const float* add0, const float* add1, int64_t add_rows, float* C0, float* C1, int32_t Nout) {
+  GemmArgs g = linear_args(A0, M, K, W, bias, add0, add_rows, 0, C0, Nout);
+  g.A0b = A1; g.add_b = add1; g.C_b = C1;
+  return g;
+}
+
+static GemmArgs update_args(const float* h, const float* agg, const float* W, const float* b, const float* w_s,
+                            const float* b_s, const float* mask, float* h_out, float* score, int64_t BN, int32_t D,
+                            int32_t I) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A0 = h; g.A1 = agg; g.W = W; g.bias = b; g.C = h_out;
+  g.w_s = w_s; g.b_s = b_s; g.mask = mask; g.score = score;
+  g.M = (int32_t)BN; g.K = (2 * I + 1) * D; g.K0 = D; g.Nout = D; g.ldw = g.K;
+  g.relu = 1;
+  return g;
+}
+
+static GemmArgs update_fused_args(const float* h, const float* nbr, const uint8_t* add_flag, const float* W,
+                                  const float* b, const float* w_s, const float* b_s, const float* mask, float* h_out,
+                                  float* score, int64_t BN, int32_t D, int32_t I) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  // only the self block W[:, 0:D] of e2e_linear is multiplied here; the neighbour blocks were
+  // pushed into the relation tables and arrive already reduced in `nbr`
+  g.A0 = h; g.W = W; g.bias = b; g.add = nbr; g.add_rows = (int32_t)BN; g.C = h_out;
+  g.w_s = w_s; g.b_s = b_s; g.mask = mask; g.score = score;
+  g.M = (int32_t)BN; g.K = D; g.K0 = D; g.Nout = D; g.ldw = (2 * I + 1) * D; g.wc0 = 0;
+  g.relu = 1;
+  g.add_flag = add_flag;
+  return g;
 }
 
 }  // namespace gnnrag
@@ -991,12 +1118,7 @@ extern "C" int gnnrag_linear(const float* A, int64_t M, int32_t K, const float* 
                              int32_t math, gnnrag_stream_t stream) {
   if (!A || !W || !C || M < 0 || K <= 0 || Nout <= 0 || !math_ok(math)) return GNNRAG_E_BADARG;
   if (M >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A0 = A; g.W = W; g.bias = bias; g.add = add; g.C = C;
-  g.M = (int32_t)M; g.K = K; g.K0 = K; g.Nout = Nout; g.ldw = K;
-  g.add_rows = add ? (int32_t)(add_rows < M ? add_rows : M) : 0;
-  g.relu = relu;
+  GemmArgs g = linear_args(A, M, K, W, bias, add, add_rows, relu, C, Nout);
   for (int n0 = 0; n0 < Nout; n0 += 208) {
     g.n0 = n0;
     const int rc = launch_gemm<EPI_LINEAR, AMODE_PLAIN>(g, (hipStream_t)stream, math);
@@ -1008,25 +1130,17 @@ extern "C" int gnnrag_linear(const float* A, int64_t M, int32_t K, const float* 
 
 // shared by the two update entry points: h' = relu(A.W^T + b (+ add)), score = score_func(h') + mask term
 static int update_common(GemmArgs g, int64_t BN, int32_t D, hipStream_t stream, int math, bool score_zeroed = false) {
-  if (D <= 208) {
-    g.n0 = 0;
-    // short K, exact fp32, aligned operands: the W-resident kernel (whole weight block in LDS)
-    const bool al = aligned16(g.A0) && aligned16(g.W) && aligned16(g.C) && (!g.add || aligned16(g.add)) &&
-                    g.ldw % 4 == 0 && g.wc0 % 4 == 0 && (!g.add || g.add_rows >= g.M);
-    if (GNNRAG_UPDATE_B3 && math != GNNRAG_MATH_FP32 && al && g.add && !g.A1 && g.K == D &&
-        (!g.add_flag || ((uintptr_t)g.add_flag & 3) == 0)) {
-      const int rc = update_b3_launch_f(g.A0, g.add, g.add_flag, g.W, g.bias, g.w_s, g.b_s, g.mask, g.C, g.score, BN, D,
-                                        g.ldw, stream, score_zeroed);
-      if (rc != GNNRAG_E_UNSUPPORTED) return rc;
-    }
-    const int S = (GNNRAG_GEMM_WRES && math != GNNRAG_MATH_BF16X3 && al && g.M >= 4096 &&
-                   (!g.add_flag || ((uintptr_t)g.add_flag & 3) == 0)) ? wres_stride(g) : 0;
-    if (S) return launch_wres<EPI_UPDATE>(g, S, stream);
-    if (GNNRAG_UPDATE_SKINNY && update_skinny_ok(g)) return launch_update_skinny(g, stream);    // small batches: exact fp32
-    if (g.add_flag) return GNNRAG_E_UNSUPPORTED;      // the k-tiled kernel has no row-gated form: nothing launched
-    return launch_gemm<EPI_UPDATE, AMODE_PLAIN>(g, stream, math);
+  const DenseForm f = update_form(g, BN, D, math);
+  switch (f.family) {
+    case GNNRAG_DENSE_UPDATE_B3:
+      return update_b3_launch_f(g.A0, g.add, g.add_flag, g.W, g.bias, g.w_s, g.b_s, g.mask, g.C, g.score, BN, D, g.ldw,
+                                stream, score_zeroed);
+    case GNNRAG_DENSE_WRES: g.n0 = 0; return launch_wres<EPI_UPDATE>(g, f.S, stream);
+    case GNNRAG_DENSE_UPDATE_SKINNY: g.n0 = 0; return launch_update_skinny(g, stream);
+    case GNNRAG_DENSE_KTILED: g.n0 = 0; return launch_gemm<EPI_UPDATE, AMODE_PLAIN>(g, stream, math);
+    case GNNRAG_DENSE_WIDE: break;
+    default: return GNNRAG_E_UNSUPPORTED;      // row gates on a shape without a gated kernel: nothing launched
   }
-  if (g.add_flag) return GNNRAG_E_UNSUPPORTED;
   // wide hidden sizes: column blocks of 208 with bias(+add)+ReLU epilogue, then a row-dot for the score
   g.relu = 1;
   for (int n0 = 0; n0 < D; n0 += 208) {
@@ -1046,16 +1160,12 @@ extern "C" int gnnrag_linear_pair(const float* A0, const float* A1, int64_t M, i
                                   float* C0, float* C1, int32_t Nout, int32_t math, gnnrag_stream_t stream) {
   if (!A0 || !A1 || !W || !C0 || !C1 || M < 0 || K <= 0 || Nout <= 0 || !math_ok(math)) return GNNRAG_E_BADARG;
   if ((add0 == nullptr) != (add1 == nullptr)) return GNNRAG_E_BADARG;
-  if (M > kSkinnyMaxM) {     // large problems: two ordinary launches
+  if (pair_is_two_calls(M)) {     // large problems: two ordinary launches
     int rc = gnnrag_linear(A0, M, K, W, bias, add0, add_rows, 0, C0, Nout, math, stream);
     if (rc) return rc;
     return gnnrag_linear(A1, M, K, W, bias, add1, add_rows, 0, C1, Nout, math, stream);
   }
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A0 = A0; g.A0b = A1; g.W = W; g.bias = bias; g.add = add0; g.add_b = add1; g.C = C0; g.C_b = C1;
-  g.M = (int32_t)M; g.K = K; g.K0 = K; g.Nout = Nout; g.ldw = K;
-  g.add_rows = add0 ? (int32_t)(add_rows < M ? add_rows : M) : 0;
+  GemmArgs g = pair_args(A0, A1, M, K, W, bias, add0, add1, add_rows, C0, C1, Nout);
   const int rc = launch_gemm<EPI_LINEAR, AMODE_PLAIN>(g, (hipStream_t)stream, math);
   return rc == (1 << 30) ? 0 : rc;
 }
@@ -1068,12 +1178,7 @@ extern "C" int gnnrag_update_score(const float* h, const float* agg, const float
       !math_ok(math))
     return GNNRAG_E_BADARG;
   if (BN >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.A0 = h; g.A1 = agg; g.W = W; g.bias = b; g.C = h_out;
-  g.w_s = w_s; g.b_s = b_s; g.mask = mask; g.score = score;
-  g.M = (int32_t)BN; g.K = (2 * I + 1) * D; g.K0 = D; g.Nout = D; g.ldw = g.K;
-  g.relu = 1;
+  const GemmArgs g = update_args(h, agg, W, b, w_s, b_s, mask, h_out, score, BN, D, I);
   return update_common(g, BN, D, (hipStream_t)stream, math);
 }
 
@@ -1087,17 +1192,13 @@ extern "C" int gnnrag_update_score_fused(const float* h, const float* nbr, const
 
 bool gnnrag::update_rows_supported(const float* h, const float* nbr, const float* W, const float* h_out, int64_t BN,
                                    int32_t D, int32_t I, int32_t math) {
-  if (D > 208 || BN >= ((int64_t)1 << 31)) return false;
-  const int ldw = (2 * I + 1) * D;
-  const bool al = aligned16(h) && aligned16(W) && aligned16(h_out) && aligned16(nbr) && ldw % 4 == 0;
-  if (!al) return false;
-  if (GNNRAG_UPDATE_B3 && math != GNNRAG_MATH_FP32 && update_b3_shape_ok(BN, D, ldw)) return true;
-  if (GNNRAG_UPDATE_SKINNY && BN < 4096 && D % 4 == 0) return true;                 // k_update_skinny
-  if (!(GNNRAG_GEMM_WRES && math != GNNRAG_MATH_BF16X3 && BN >= 4096)) return false;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  g.M = (int32_t)BN; g.K = D; g.K0 = D; g.Nout = D; g.ldw = ldw;
-  return wres_stride(g) != 0;
+  if (!h || !nbr || !W || !h_out || BN < 0 || BN >= ((int64_t)1 << 31) || D <= 0 || I <= 0) return false;
+  // the form update_score_fused_rows would take with (4-byte aligned) row gates: only these three kernels read them
+  static const uint32_t gates = 0;
+  float* const out = const_cast<float*>(h_out);      // only its alignment is read
+  const GemmArgs g = update_fused_args(h, nbr, reinterpret_cast<const uint8_t*>(&gates), W, h, h, h, h, out, out, BN, D, I);
+  const int family = update_form(g, BN, D, math).family;
+  return family == GNNRAG_DENSE_UPDATE_B3 || family == GNNRAG_DENSE_WRES || family == GNNRAG_DENSE_UPDATE_SKINNY;
 }
 
 int gnnrag::update_score_fused_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
@@ -1114,16 +1215,73 @@ int gnnrag::update_score_fused_rows(const float* h, const float* nbr, const uint
       !math_ok(math))
     return GNNRAG_E_BADARG;
   if (BN >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
-  GemmArgs g;
-  memset(&g, 0, sizeof(g));
-  // only the self block W[:, 0:D] of e2e_linear is multiplied here; the neighbour blocks were
-  // pushed into the relation tables and arrive already reduced in `nbr`
-  g.A0 = h; g.W = W; g.bias = b; g.add = nbr; g.add_rows = (int32_t)BN; g.C = h_out;
-  g.w_s = w_s; g.b_s = b_s; g.mask = mask; g.score = score;
-  g.M = (int32_t)BN; g.K = D; g.K0 = D; g.Nout = D; g.ldw = (2 * I + 1) * D; g.wc0 = 0;
-  g.relu = 1;
-  g.add_flag = add_flag;
+  const GemmArgs g = update_fused_args(h, nbr, add_flag, W, b, w_s, b_s, mask, h_out, score, BN, D, I);
   return update_common(g, BN, D, stream, math, score_zeroed);
+}
+
+// Host only.  The operands are stand-in addresses that are never dereferenced: the decision functions read nothing of a
+// pointer but "null or not" and its low four bits.
+extern "C" int gnnrag_dense_form(int32_t entry, int64_t M, int32_t K, int32_t Nout, int32_t math, int32_t has_add,
+                                 int64_t add_rows, int32_t misaligned, int32_t block, gnnrag_dense_form_t* out) {
+  if (!out || M <= 0 || K <= 0 || Nout <= 0 || block < 0 || !math_ok(math) || M >= ((int64_t)1 << 31))
+    return GNNRAG_E_BADARG;
+  auto stand_in = [&](int slot, int bit) {
+    return reinterpret_cast<float*>((uintptr_t)0x1000 * (slot + 1) + ((misaligned & bit) ? 4 : 0));
+  };
+  float* A = stand_in(0, GNNRAG_DENSE_MISALIGNED_A);
+  float* W = stand_in(1, GNNRAG_DENSE_MISALIGNED_W);
+  float* C = stand_in(2, GNNRAG_DENSE_MISALIGNED_C);
+  float* add = stand_in(3, GNNRAG_DENSE_MISALIGNED_ADD);
+  float* A1 = stand_in(4, GNNRAG_DENSE_MISALIGNED_A1);
+  float* other = stand_in(5, 0);          // bias, score weights, mask, the pair's second add / C: alignment is not read
+  DenseForm f;
+  int launches = 1;
+  if (entry == GNNRAG_DENSE_ENTRY_LINEAR || entry == GNNRAG_DENSE_ENTRY_LINEAR_PAIR) {
+    const bool pair = entry == GNNRAG_DENSE_ENTRY_LINEAR_PAIR;
+    const bool split = pair && pair_is_two_calls(M);
+    GemmArgs g = (pair && !split)
+                     ? pair_args(A, A1, M, K, W, other, has_add ? add : nullptr, has_add ? other : nullptr, add_rows, C,
+                                 other, Nout)
+                     : linear_args(A, M, K, W, other, has_add ? add : nullptr, add_rows, 0, C, Nout);
+    f = gemm_form(g, EPI_LINEAR, AMODE_PLAIN, math);           // column block 0 decides how many launches there are
+    launches = f.block_family == GNNRAG_DENSE_SKINNY ? 1 : (Nout + 207) / 208;
+    if (block >= launches) return GNNRAG_E_BADARG;
+    if (block) {
+      g.n0 = 208 * block;
+      f = gemm_form(g, EPI_LINEAR, AMODE_PLAIN, math);
+    }
+    if (split) launches *= 2;
+  } else if (entry == GNNRAG_DENSE_ENTRY_UPDATE || entry == GNNRAG_DENSE_ENTRY_UPDATE_FUSED) {
+    const int64_t BN = M;
+    const int32_t D = K, I = Nout;
+    if ((int64_t)(2 * (int64_t)I + 1) * D >= ((int64_t)1 << 31)) return GNNRAG_E_BADARG;
+    GemmArgs g = entry == GNNRAG_DENSE_ENTRY_UPDATE
+                     ? update_args(A, A1, W, other, other, other, other, C, other, BN, D, I)
+                     : update_fused_args(A, add, nullptr, W, other, other, other, other, C, other, BN, D, I);
+    f = update_form(g, BN, D, math);
+    if (f.family == GNNRAG_DENSE_WIDE) {
+      launches = f.block_family == GNNRAG_DENSE_SKINNY ? 1 : (D + 207) / 208;
+      if (block >= launches) return GNNRAG_E_BADARG;
+      if (block) {
+        g.n0 = 208 * block;
+        f = update_form(g, BN, D, math);
+      }
+    } else if (block) {
+      return GNNRAG_E_BADARG;
+    }
+  } else {
+    return GNNRAG_E_BADARG;
+  }
+  memset(out, 0, sizeof(*out));
+  out->family = f.family; out->block_family = f.block_family; out->launches = launches;
+  out->v4 = f.v4;
+  if (f.block_family == GNNRAG_DENSE_KTILED) {
+    out->epi = f.epi; out->nt = f.nt; out->mt = f.mt; out->math = f.math; out->nw = f.nw;
+    out->v4out = f.v4out; out->n0 = f.n0;
+  } else if (f.family == GNNRAG_DENSE_WRES) {
+    out->nt = f.nt; out->nc = f.nc; out->has_add = f.has_add; out->kguard = f.kguard;
+  }
+  return 0;
 }
 
 extern "C" int gnnrag_relation_tables(const gnnrag_csr* csr, const float* T_fwd, const float* T_inv,

@@ -2,6 +2,7 @@
 PyTorch-ROCm (plumbing), every computation is a call into libgnnrag_hip.so."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Optional
@@ -527,6 +528,31 @@ def aggregate_fused_variant(plan: CsrPlan, D: int) -> int:
     if v < 0:
         _lib.check(v, "gnnrag_aggregate_fused_variant")
     return v
+
+
+DENSE_ENTRIES = {"linear": 0, "linear_pair": 1, "update_score": 2, "update_score_fused": 3}
+DENSE_MISALIGNED_A, DENSE_MISALIGNED_W, DENSE_MISALIGNED_C, DENSE_MISALIGNED_ADD, DENSE_MISALIGNED_A1 = 1, 2, 4, 8, 16
+(DENSE_NONE, DENSE_SKINNY, DENSE_KTILED, DENSE_WRES, DENSE_UPDATE_SKINNY, DENSE_UPDATE_B3,
+ DENSE_WIDE) = range(7)
+DENSE_KERNEL_NAMES = {DENSE_NONE: "nothing launched", DENSE_SKINNY: "k_gemm_skinny", DENSE_KTILED: "k_gemm_f32",
+                      DENSE_WRES: "k_gemm_wres", DENSE_UPDATE_SKINNY: "k_update_skinny", DENSE_UPDATE_B3: "k_update_b3",
+                      DENSE_WIDE: "EPI_LINEAR column blocks + k_score_rows"}
+DenseForm = collections.namedtuple("DenseForm", [n for n, _ in _lib.DenseFormStruct._fields_])
+
+
+def dense_form(entry: str, M: int, K: int, Nout: int, math: Optional[int] = None, add_rows: Optional[int] = None,
+               misaligned: int = 0, block: int = 0) -> DenseForm:
+    """Which kernel a dense call runs (``gnnrag_dense_form``: host only, the launchers' own decision function).
+    ``entry``: "linear", "linear_pair", "update_score" or "update_score_fused"; the update entry points pass
+    (BN, D, I) as (M, K, Nout).  ``add_rows=None``: no ``add``.  ``misaligned``: OR of DENSE_MISALIGNED_* (operands
+    that are not 16-byte aligned).  ``block``: column block of a call that makes several launches.
+    Returns a :class:`DenseForm`: ``family`` (DENSE_*), and for k_gemm_f32 its template arguments ``nt, mt, v4, epi,
+    math, nw`` with the runtime switches ``v4out, n0``; for k_gemm_wres ``nt, nc, has_add, kguard``."""
+    out = _lib.DenseFormStruct()
+    _lib.check(_lib.load().gnnrag_dense_form(DENSE_ENTRIES[entry], int(M), int(K), int(Nout), _math(math),
+                                             int(add_rows is not None), int(add_rows or 0), int(misaligned), int(block),
+                                             C.byref(out)), "gnnrag_dense_form")
+    return DenseForm(*(getattr(out, n) for n in DenseForm._fields))
 
 
 HUB_FORM_NONE, HUB_FORM_DENSE, HUB_FORM_CHUNKED = 0, 1, 2

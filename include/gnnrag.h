@@ -340,6 +340,46 @@ int gnnrag_update_score_fused(const float* h, const float* nbr, const float* W_e
                               float* h_out, float* score, int64_t BN, int32_t D, int32_t I, int32_t math,
                               gnnrag_stream_t stream);
 
+/* ---- Which kernel a dense call runs (additive to ABI 16) ---------------------------------------------------------------
+ * HOST ONLY: no device, no HIP call.  Describes a gnnrag_linear / gnnrag_linear_pair / gnnrag_update_score /
+ * gnnrag_update_score_fused call and returns what the launcher would choose - it runs the launchers' own decision
+ * function on the same arguments (stand-in pointers carry the alignment), so tests can assert the kernel they mean to
+ * test and a moved threshold fails a test instead of emptying it (the dense twin of gnnrag_aggregate_fused_variant).
+ *   entry            GNNRAG_DENSE_ENTRY_*
+ *   M, K, Nout       of the linear entry points; the update entry points pass (BN, D, I) in their place
+ *   math             GNNRAG_MATH_*
+ *   has_add/add_rows the linear entry points' `add` (ignored for the update entry points: nbr is always there)
+ *   misaligned       OR of GNNRAG_DENSE_MISALIGNED_*: operands that are NOT 16-byte aligned
+ *   block            column block (208 columns each) of a call that makes several launches; 0 otherwise
+ * GNNRAG_E_BADARG: sizes <= 0, unknown entry / math, a block the call does not launch. */
+#define GNNRAG_DENSE_ENTRY_LINEAR       0
+#define GNNRAG_DENSE_ENTRY_LINEAR_PAIR  1   /* above the skinny bound: two gnnrag_linear calls, the form is theirs       */
+#define GNNRAG_DENSE_ENTRY_UPDATE       2   /* gnnrag_update_score                                                     */
+#define GNNRAG_DENSE_ENTRY_UPDATE_FUSED 3   /* gnnrag_update_score_fused                                               */
+#define GNNRAG_DENSE_MISALIGNED_A   1       /* A / A0 / h                                                              */
+#define GNNRAG_DENSE_MISALIGNED_W   2
+#define GNNRAG_DENSE_MISALIGNED_C   4       /* C / C0 / h_out                                                          */
+#define GNNRAG_DENSE_MISALIGNED_ADD 8       /* add / add0 / nbr                                                        */
+#define GNNRAG_DENSE_MISALIGNED_A1  16      /* A1 of the pair / agg                                                    */
+#define GNNRAG_DENSE_NONE          0        /* nothing is launched (GNNRAG_E_UNSUPPORTED)                              */
+#define GNNRAG_DENSE_SKINNY        1        /* k_gemm_skinny: exact fp32 in every math mode, all columns in one launch  */
+#define GNNRAG_DENSE_KTILED        2        /* k_gemm_f32<NT, MT, V4, EPI, AMODE_PLAIN, MATH, NW>                      */
+#define GNNRAG_DENSE_WRES          3        /* k_gemm_wres<NT, NC, EPI_UPDATE, HAS_ADD, KGUARD, false>                 */
+#define GNNRAG_DENSE_UPDATE_SKINNY 4        /* k_update_skinny                                                         */
+#define GNNRAG_DENSE_UPDATE_B3     5        /* k_update_b3 (tables_b3.hip)                                             */
+#define GNNRAG_DENSE_WIDE          6        /* D > 208: EPI_LINEAR column blocks, then k_score_rows                    */
+typedef struct gnnrag_dense_form_t {
+  int32_t family;        /* GNNRAG_DENSE_*                                                                               */
+  int32_t block_family;  /* family of the described GEMM launch: = family, except WIDE (SKINNY or KTILED)                */
+  int32_t launches;      /* GEMM launches of the call (column blocks; x 2 for a pair above the skinny bound)             */
+  int32_t epi;           /* KTILED: 0 = EPI_LINEAR, 1 = EPI_UPDATE                                                       */
+  int32_t nt, mt, v4, math, nw;   /* KTILED template arguments (nt also WRES; v4 also SKINNY)                            */
+  int32_t v4out, n0;     /* KTILED runtime: float4 epilogue, first output column of the block                            */
+  int32_t nc, has_add, kguard;    /* WRES template arguments                                                             */
+} gnnrag_dense_form_t;
+int gnnrag_dense_form(int32_t entry, int64_t M, int32_t K, int32_t Nout, int32_t math, int32_t has_add, int64_t add_rows,
+                      int32_t misaligned, int32_t block, gnnrag_dense_form_t* out);
+
 /* One whole ReasonGNNLayer.forward (reasongnn.py:134-174) enqueued with a single call:
  * rel transform (both directions) -> aggregation -> update+score -> softmax.
  * path: GNNRAG_PATH_UNFUSED = aggregate [BN,2I*D] then one [(2I+1)D -> D] GEMM (the reference's

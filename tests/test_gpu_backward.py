@@ -297,11 +297,18 @@ def test_gemm_tn_weight_gradient_vs_fp64(dev, M, N1, N2):
 
 
 @pytest.mark.parametrize("M,K,Nout,relu,bias", [(3000, 200, 200, True, True), (513, 1000, 200, False, True),
-                                                (602, 200, 200, False, False), (9000, 200, 200, True, True)])
+                                                (602, 200, 200, False, False), (9000, 200, 200, True, True),
+                                                (16391, 1000, 200, True, True), (16391, 200, 1000, False, True)])
 def test_linear_autograd_function_matches_torch(dev, M, K, Nout, relu, bias):
     """autograd.LinearFn (forward and dx on gnnrag_linear, dW on gnnrag_gemm_tn) against torch's own nn.Linear autograd
-    in float64."""
+    in float64.  Up to 16384 rows forward and dx run k_gemm_skinny; the two 16391-row shapes run both on k_gemm_f32,
+    dx = g W^T of (16391, 1000, 200) through five column blocks."""
+    from gnnrag_amd import ops
     from gnnrag_amd.autograd import linear
+    for (k, n) in ((K, Nout), (Nout, K)):          # forward, dx
+        f = ops.dense_form("linear", M, k, n)
+        assert f.family == (ops.DENSE_KTILED if M > 16384 else ops.DENSE_SKINNY)
+        assert f.launches == ((n + 207) // 208 if M > 16384 else 1)
     rng = np.random.default_rng(K + M)
     x = rng.standard_normal((M, K)).astype(np.float32)
     W = (rng.standard_normal((Nout, K)) / np.sqrt(K)).astype(np.float32)

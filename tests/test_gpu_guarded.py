@@ -325,12 +325,23 @@ def test_structure_builds(dev, g, name):
 @pytest.mark.parametrize("math", [0, 1, 2], ids=["fp32", "bf16x3", "mixed"])
 @pytest.mark.parametrize("M,K,Nout,with_add,relu", [(602, 200, 200, True, False), (9, 50, 50, True, True),
                                                     (257, 1000, 200, False, True), (4099, 250, 50, False, True),
-                                                    (33, 30, 30, False, False), (8209, 200, 200, False, True)])
+                                                    (33, 30, 30, False, False), (8209, 200, 200, False, True),
+                                                    (16391, 200, 200, True, True), (16391, 36, 216, True, True),
+                                                    (16391, 30, 72, False, False)])
 def test_linear_and_linear_pair(dev, g, math, M, K, Nout, with_add, relu):
-    """gnnrag_linear and gnnrag_linear_pair (skinny, k-tiled and W-resident kernels; M not a multiple of the 16-row
-    tile) in every math mode against fp64, tolerance of test_linear_vs_fp64."""
+    """gnnrag_linear and gnnrag_linear_pair in every math mode against fp64, tolerance of test_linear_vs_fp64; M not a
+    multiple of the row tile.  Up to 16384 rows both run k_gemm_skinny (the pair in one launch); the 16391-row shapes
+    run k_gemm_f32 - the pair as two gnnrag_linear calls - with `add` and relu, a second column block (Nout = 216) and
+    the scalar loaders (K = 30).  There is no W-resident kernel for these entry points."""
     from gnnrag_amd import _lib, ops
     lib = _lib.load()
+    for entry in ("linear", "linear_pair"):
+        f = ops.dense_form(entry, M, K, Nout, math=math, add_rows=max(M - 1, 1) if with_add else None)
+        if M <= 16384:
+            assert (f.family, f.launches) == (ops.DENSE_SKINNY, 1)
+        else:
+            assert f.family == ops.DENSE_KTILED and f.math == int(math != 0 and K % 4 == 0)
+            assert f.launches == (Nout + 207) // 208 * (2 if entry == "linear_pair" else 1)
 
     def data(seed):
         rng = np.random.default_rng(seed)

@@ -173,7 +173,10 @@ def test_csr_plan_empty_and_validation(dev):
     (300, 250, 50, False, True), (130, 64, 300, False, False), (1, 8, 8, False, False),
     (257, 1000, 200, False, True)])
 def test_linear_vs_fp64(dev, M, K, Nout, with_add, relu):
+    """gnnrag_linear on k_gemm_skinny (every shape here has M <= 16384) against float64; the k-tiled kernel is held to
+    float64 form by form in tests/test_gpu_dense_forms.py."""
     from gnnrag_amd import ops
+    assert ops.dense_form("linear", M, K, Nout, add_rows=max(M - 1, 1) if with_add else None).family == ops.DENSE_SKINNY
     rng = np.random.default_rng(M + K)
     A = rng.standard_normal((M, K)).astype(np.float32)
     W = (rng.standard_normal((Nout, K)) / np.sqrt(K)).astype(np.float32)
@@ -579,11 +582,23 @@ def bf16x3(dev, request):
     ops.set_dense_math(old)
 
 
-@pytest.mark.parametrize("M,K,Nout", [(5000, 200, 200), (6000, 1000, 200), (4500, 250, 50), (40000, 400, 200)])
+@pytest.mark.parametrize("M,K,Nout", [(5000, 200, 200), (6000, 1000, 200), (4500, 250, 50), (40000, 400, 200),
+                                      (16391, 1000, 200), (20000, 250, 50), (16391, 200, 1000)])
 def test_bf16x3_linear_is_fp32_class(dev, bf16x3, M, K, Nout):
     """The split-bf16 math mode against float64, and against the exact-fp32 MFMA mode: its error must
-    be of the same class (fp32 rounding), not bf16 class."""
+    be of the same class (fp32 rounding), not bf16 class.  Up to 16384 rows both modes run k_gemm_skinny (exact fp32:
+    the comparison is then of a kernel with itself, kept as the proof that the skinny kernel ignores the mode); the
+    shapes above run k_gemm_f32 - its two MFMA forms where K % 4 == 0, (16391, 200, 1000) through five column blocks."""
     from gnnrag_amd import ops
+    f3 = ops.dense_form("linear", M, K, Nout, math=ops.MATH_BF16X3)
+    f32 = ops.dense_form("linear", M, K, Nout, math=ops.MATH_FP32)
+    if M <= 16384:
+        assert f3 == f32 and f3.family == ops.DENSE_SKINNY
+    else:
+        # K % 4 != 0 takes the scalar loaders, which exist in the exact-fp32 form only: (20000, 250, 50) runs the SAME
+        # k_gemm_f32 instantiation in both modes, the other two shapes its two MFMA forms
+        assert f3.family == f32.family == ops.DENSE_KTILED and (f3.math, f32.math) == (int(K % 4 == 0), 0)
+        assert f3._replace(math=0) == f32 and f3.launches == (Nout + 207) // 208
     rng = np.random.default_rng(K)
     A = (rng.standard_normal((M, K)) * np.exp(rng.uniform(-6, 6, (M, 1)))).astype(np.float32)   # wide dynamic range
     W = (rng.standard_normal((Nout, K)) / np.sqrt(K)).astype(np.float32)
