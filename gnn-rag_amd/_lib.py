@@ -146,6 +146,13 @@ SIGNATURES = {
     "gnnrag_frontier_read": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP]),
     # instruction generation (additive to ABI 16)
     "gnnrag_instructions": (C.c_int, [_VP] * 4 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP] * 3),
+    # training form of instruction generation (additive to ABI 16)
+    "gnnrag_instructions_reserve_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_instructions_train": (C.c_int, [_VP] * 4 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 7 + [C.c_int32] * 4 +
+                                  [_VP] * 3 + [C.c_size_t, _VP]),
+    "gnnrag_instructions_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_instructions_backward": (C.c_int, [_VP] * 3 + [C.POINTER(C.c_void_p)] + [_VP] * 8 + [C.c_size_t] + [_VP] * 5 +
+                                     [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP, C.c_size_t, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

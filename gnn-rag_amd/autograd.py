@@ -7,7 +7,8 @@ through ``reason_layer`` / ``reason_layer_inv`` (``reasongnn.py:61-116``) and ``
 ``gnnrag_typelayer_backward``); the dense projections around them run on the library's matrix-core kernels in
 both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gemm_tn`` for dW).  The question
 encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``), the relation-text
-features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``)."""
+features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``), instruction generation on
+:class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -188,3 +189,41 @@ class RelTextPoolFn(torch.autograd.Function):
         dW, db, da = ops.rel_text_pool_backward(X_fwd, X_inv, W, a, xbar, alpha, g_fwd, g_inv, need_dW=need[3],
                                                 need_db=need[4], need_da=need[5])
         return None, None, None, dW, db, None if da is None else da.view(ctx.a_shape)
+
+
+class InstructionsFn(torch.autograd.Function):
+    """``ins [n,B,D], attn [n,B,T]`` = n chained ``get_instruction`` steps (base_encoder.py:82-101) on
+    ``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``.  r_in [B,D] or None (zeros); drop_node / drop_cat /
+    drop_tok: the multipliers of ``linear_drop`` or None (see :func:`ops.instructions_train`); ``lin``: the steps'
+    ``question_linear`` weights, then their biases (2 n tensors).  The reserve and the multipliers are saved in the context
+    of THIS call.  The mask and the multipliers never receive a gradient."""
+
+    @staticmethod
+    def forward(ctx, hidden, node, mask, r_in, W_cq, b_cq, w_ca, b_ca, drop_node, drop_cat, drop_tok, *lin):
+        n = len(lin) // 2
+        W_q, b_q = list(lin[:n]), list(lin[n:])
+        hidden, node = hidden.detach().float(), node.detach().float()
+        r_in = None if r_in is None else r_in.detach().float()
+        ins, attn, reserve = ops.instructions_train(hidden, node, mask.detach(), W_q, b_q, W_cq, b_cq, w_ca, b_ca, r_in=r_in,
+                                                    drop_node=drop_node, drop_cat=drop_cat, drop_tok=drop_tok)
+        ctx.set_materialize_grads(False)            # an unused output arrives as None and goes to the library as NULL
+        ctx.n, ctx.w_ca_shape, ctx.b_ca_shape = n, w_ca.shape, b_ca.shape
+        ctx.save_for_backward(hidden, node, r_in, W_cq.detach(), w_ca.detach(), drop_node, drop_cat, drop_tok, ins, attn,
+                              reserve, *[w.detach() for w in W_q])
+        return ins, attn
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ins, g_attn):
+        hidden, node, r_in, W_cq, w_ca, drop_node, drop_cat, drop_tok, ins, attn, reserve = ctx.saved_tensors[:11]
+        W_q = list(ctx.saved_tensors[11:])
+        n, nig = ctx.n, ctx.needs_input_grad
+        need = {"dhidden": nig[0], "dnode": nig[1], "dr_in": nig[3] and r_in is not None, "dW_cq": nig[4], "db_cq": nig[5],
+                "dw_ca": nig[6], "db_ca": nig[7], "dW_q": list(nig[11:11 + n]), "db_q": list(nig[11 + n:11 + 2 * n])}
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as ins.sum().backward() delivers
+        g_ins, g_attn = (None if g is None else g.float() for g in (g_ins, g_attn))
+        g = ops.instructions_backward(hidden, node, W_q, W_cq, w_ca, ins, attn, reserve, g_ins, g_attn, r_in=r_in,
+                                      drop_node=drop_node, drop_cat=drop_cat, drop_tok=drop_tok, need=need)
+        view = lambda t, shape: None if t is None else t.view(shape)      # noqa: E731
+        return (g["dhidden"], g["dnode"], None, g["dr_in"], g["dW_cq"], g["db_cq"], view(g["dw_ca"], ctx.w_ca_shape),
+                view(g["db_ca"], ctx.b_ca_shape), None, None, None, *g["dW_q"], *g["db_q"])

@@ -20,6 +20,16 @@ a second time; ``nsm.py:117,205-208`` alike).
 
 The fast path needs CUDA fp32 tensors, a shape the library takes, inactive dropout and no autograd; otherwise - and with
 ``GNNRAG_HIP_INSTRUCTION=0`` (read at every call) - the wrapped originals run unchanged.  Nothing is read on the host.
+
+Training (``GNNRAG_HIP_INSTRUCTION_TRAIN=1``, read at every call, default off; it acts inside ``GNNRAG_HIP_INSTRUCTION=1``):
+a call the rule above refuses - autograd needs the result, or ``linear_drop`` is active in training mode - goes through
+``autograd.InstructionsFn`` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``) where the backward takes the
+shape.  With ``linear_drop.p > 0`` in training mode the module draws the three dropout multipliers itself
+(:func:`draw_masks`: ``bernoulli_(1 - p) / (1 - p)`` from torch's generator).  They are NOT the draws ``F.dropout`` would
+have made at the reference's three call sites: a loss curve is comparable, not equal.  With the switch set, the direct
+``init_reason`` + ``get_instruction`` chain (``rearev.py:192-196``, ``nsm.py:205-208``) also makes ONE all-steps call from
+``init_reason``, and its ``get_instruction`` calls pick the steps up by identity as above; a foreign ``relational_ins``
+still gets a single-step call.
 """
 from __future__ import annotations
 
@@ -28,14 +38,31 @@ import os
 import torch
 import torch.nn as nn
 
-from ... import ops
+from ... import autograd, ops
 
 DEFAULT = "0"        # GNNRAG_HIP_INSTRUCTION when unset (the rule and the measurement)
+TRAIN_DEFAULT = "0"  # GNNRAG_HIP_INSTRUCTION_TRAIN when unset: off until measured
 
 
 def enabled() -> bool:
     """Whether the patched methods use the library (read at every call: the switch can change in-process)."""
     return os.environ.get("GNNRAG_HIP_INSTRUCTION", DEFAULT) != "0"
+
+
+def train_enabled() -> bool:
+    """Whether a call that needs autograd or active dropout runs on the library (read at every call)."""
+    return os.environ.get("GNNRAG_HIP_INSTRUCTION_TRAIN", TRAIN_DEFAULT) != "0"
+
+
+def draw_masks(p: float, n: int, B: int, T: int, D: int, device):
+    """The three dropout multipliers of ``n`` steps - node [n,B,D], concatenation [n,B,4D], token products [n,B,T,D] -
+    each 0 with probability p, else 1/(1-p); drawn from torch's generator of ``device``."""
+    keep = 1.0 - float(p)
+
+    def one(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=device).bernoulli_(keep).div_(keep)
+
+    return one(n, B, D), one(n, B, 4 * D), one(n, B, T, D)
 
 
 def _linear_ok(m, out_f: int, in_f: int) -> bool:
@@ -60,8 +87,23 @@ def _mode_ok(instr, tensors) -> bool:
     return not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
 
 
+def _drop_p(instr) -> float:
+    """The probability ``linear_drop`` applies in this call (0 outside training mode)."""
+    return float(getattr(instr.linear_drop, "p", 0.0)) if instr.training else 0.0
+
+
+def _mode(instr, tensors, T, D, n):
+    """"infer": the inference launch; "train": ``InstructionsFn`` (the switch is set, the backward takes the shape);
+    None: the originals."""
+    if _mode_ok(instr, tensors):
+        return "infer"
+    if train_enabled() and _drop_p(instr) < 1.0 and ops.instructions_backward_supported(T, D, n):
+        return "train"
+    return None
+
+
 def _eligible(instr, steps, r_in, node):
-    """(hidden, node [B,D], mask) when ``steps`` of ``instr`` can run on the library from ``r_in``, else None."""
+    """(hidden, node [B,D], mask, mode) when ``steps`` of ``instr`` can run on the library from ``r_in``, else None."""
     hidden, mask = getattr(instr, "query_hidden_emb", None), getattr(instr, "query_mask", None)
     if not (_f32_cuda(hidden) and _f32_cuda(node) and _f32_cuda(mask) and _f32_cuda(r_in)) or hidden.dim() != 3:
         return None
@@ -74,14 +116,22 @@ def _eligible(instr, steps, r_in, node):
     if not (all(_linear_ok(m, D, D) for m in lins) and _linear_ok(instr.cq_linear, D, 4 * D) and
             _linear_ok(instr.ca_linear, 1, D)):
         return None
-    if not _mode_ok(instr, _lin_params(instr, steps) + [hidden, node, mask, r_in]):
+    mode = _mode(instr, _lin_params(instr, steps) + [hidden, node, mask, r_in], T, D, len(steps))
+    if mode is None:
         return None
-    return hidden, node.reshape(B, D), mask
+    return hidden, node.reshape(B, D), mask, mode
 
 
 def _launch(instr, steps, r_in, enc):
-    hidden, node, mask = enc
+    hidden, node, mask, mode = enc
     lins = [getattr(instr, "question_linear%d" % s) for s in steps]
+    if mode == "train":
+        B, T, D = hidden.shape
+        p = _drop_p(instr)
+        masks = draw_masks(p, len(steps), B, T, D, hidden.device) if p > 0.0 else (None, None, None)
+        return autograd.InstructionsFn.apply(hidden, node, mask, r_in, instr.cq_linear.weight, instr.cq_linear.bias,
+                                             instr.ca_linear.weight, instr.ca_linear.bias, *masks,
+                                             *[m.weight for m in lins], *[m.bias for m in lins])
     return ops.instructions(hidden, node, mask, [m.weight for m in lins], [m.bias for m in lins], instr.cq_linear.weight,
                             instr.cq_linear.bias, instr.ca_linear.weight, instr.ca_linear.bias, r_in=r_in)
 
@@ -94,9 +144,10 @@ class _Patch:
         self.instr = instr
         self.orig_forward, self.orig_init, self.orig_get = instr.forward, instr.init_reason, instr.get_instruction
         # text / params / enc: what the last encode saw and left; zero: the zero tensor its init_reason created;
-        # ins / attn: the per-step views of the one all-steps result (None: nothing cached); all: inside forward
+        # ins / attn: the per-step views of the one all-steps result (None: nothing cached); all: inside forward;
+        # mode: how that result was made ("infer" / "train" and the dropout probability it saw)
         self.st = {"text": None, "text_v": None, "params": None, "enc": None, "zero": None, "zero_v": None,
-                   "ins": None, "attn": None, "out_v": None, "lin": None, "all": False}
+                   "ins": None, "attn": None, "out_v": None, "lin": None, "all": False, "mode": None}
 
     def param_key(self):
         return tuple((p.data_ptr(), p._version) for p in self.instr.parameters())
@@ -145,9 +196,11 @@ class _Patch:
             if quiet and all(isinstance(t, torch.Tensor) for t in enc):
                 st["text"], st["text_v"], st["params"] = query_text, query_text._version, self.param_key()
                 st["enc"] = tuple((t, t._version) for t in enc)
-        if st["all"] and st["ins"] is None:
+        if (st["all"] or train_enabled()) and st["ins"] is None:
             steps = list(range(int(instr.num_ins)))
             enc = _eligible(instr, steps, instr.relational_ins, getattr(instr, "query_node_emb", None)) if steps else None
+            if enc is not None and not st["all"] and enc[3] != "train":
+                enc = None                          # outside forward only the training form computes all steps ahead
             if enc is not None:
                 if st["enc"] is None:              # outside evaluation: valid for this pass only (no repeated-encode reuse)
                     st["enc"] = tuple((t, t._version) for t in self.encoded())
@@ -155,6 +208,7 @@ class _Patch:
                 st["ins"] = [ins[s] for s in steps]
                 st["attn"] = [attn[s].unsqueeze(-1) for s in steps]
                 st["out_v"], st["lin"] = (ins._version, attn._version), self.lin_key()
+                st["mode"] = (enc[3], _drop_p(instr) if enc[3] == "train" else 0.0)
 
     def get_instruction(self, relational_ins, step=0, query_node_emb=None):
         instr, st = self.instr, self.st
@@ -165,8 +219,11 @@ class _Patch:
                 hit = relational_ins is st["zero"] and relational_ins._version == st["zero_v"]
             else:
                 hit = relational_ins is st["ins"][step - 1]         # its _version: cache_intact()
-            if hit and _mode_ok(instr, _lin_params(instr, [step]) + [t for t, _ in st["enc"]]):
-                return st["ins"][step], st["attn"][step]
+            if hit:
+                B, T, D = st["enc"][0][0].shape
+                mode = _mode(instr, _lin_params(instr, [step]) + [t for t, _ in st["enc"]], T, D, len(st["ins"]))
+                if mode is not None and st["mode"] == (mode, _drop_p(instr) if mode == "train" else 0.0):
+                    return st["ins"][step], st["attn"][step]
         node = getattr(instr, "query_node_emb", None) if query_node_emb is None else query_node_emb
         enc = _eligible(instr, [step], relational_ins, node)
         if enc is None:

@@ -1228,6 +1228,109 @@ def instructions(hidden, node, mask, W_q, b_q, W_cq, b_cq, w_ca, b_ca, r_in=None
     return ins, attn
 
 
+def instructions_backward_supported(T: int, D: int, n_steps: int) -> bool:
+    """Whether ``gnnrag_instructions_train`` / ``gnnrag_instructions_backward`` take the shape (the header's LDS budgets;
+    every T <= 64 with D <= 256 at 8 steps fits)."""
+    return (instructions_supported(T, D, n_steps) and T * D <= 40960 and
+            4 * ((T * D + 3) // 4 * 4 + 12 * D + 3 * T) <= 160 * 1024)
+
+
+def _ins_args(hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok):
+    hidden = _chk(hidden, "hidden")
+    if hidden.dim() != 3:
+        raise ValueError("hidden must be [B,T,D]")
+    B, T, D = hidden.shape
+    n = len(W_q)
+    node = _chk(node, "node", shape=(B, D))
+    W_q = [_chk(w.detach(), "W_q[%d]" % i, shape=(D, D)) for i, w in enumerate(W_q)]
+    W_cq = _chk(W_cq.detach(), "W_cq", shape=(D, 4 * D))
+    w_ca = _chk(w_ca.detach().reshape(-1), "w_ca", shape=(D,))
+    r_in = None if r_in is None else _chk(r_in, "r_in", shape=(B, D))
+    drop_node = None if drop_node is None else _chk(drop_node, "drop_node", shape=(n, B, D))
+    drop_cat = None if drop_cat is None else _chk(drop_cat, "drop_cat", shape=(n, B, 4 * D))
+    drop_tok = None if drop_tok is None else _chk(drop_tok, "drop_tok", shape=(n, B, T, D))
+    return hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok, (B, T, D, n)
+
+
+def instructions_train(hidden, node, mask, W_q, b_q, W_cq, b_cq, w_ca, b_ca, r_in=None, drop_node=None, drop_cat=None,
+                       drop_tok=None):
+    """:func:`instructions` for training (``gnnrag_instructions_train``): the same kernel, plus the three dropout
+    multipliers of ``linear_drop`` - drop_node [n,B,D], drop_cat [n,B,4D], drop_tok [n,B,T,D], values 0 or 1/(1-p), None =
+    ones - and the reserve (q_s and cq of every step, a uint8 tensor of ``gnnrag_instructions_reserve_bytes``) that
+    :func:`instructions_backward` reads.  Without multipliers ins / attn are the bits of :func:`instructions`.  The reserve
+    is allocated per call and returned: it belongs to this forward.  Returns (ins [n,B,D], attn [n,B,T], reserve)."""
+    lib = _lib.load()
+    hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok, (B, T, D, n) = _ins_args(
+        hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok)
+    if len(b_q) != n:
+        raise ValueError("instructions_train: W_q and b_q must be lists of the same length")
+    mask = _chk(mask, "mask", shape=(B, T))
+    b_q = [_chk(v.detach(), "b_q[%d]" % i, shape=(D,)) for i, v in enumerate(b_q)]
+    b_cq = _chk(b_cq.detach(), "b_cq", shape=(D,))
+    b_ca = _chk(b_ca.detach().reshape(-1), "b_ca", shape=(1,))
+    dev = hidden.device
+    ins = _buf((max(n, 1), B, D), torch.float32, dev, "instructions_train: ins_out")
+    attn = _buf((max(n, 1), B, T), torch.float32, dev, "instructions_train: attn_out")
+    reserve = _buf(lib.gnnrag_instructions_reserve_bytes(B, T, D, n), torch.uint8, dev, "instructions_train: reserve")
+    Wp = (C.c_void_p * max(n, 1))(*[w.data_ptr() for w in W_q])
+    bp = (C.c_void_p * max(n, 1))(*[v.data_ptr() for v in b_q])
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_instructions_train(hidden.data_ptr(), node.data_ptr(), mask.data_ptr(), _ptr(r_in), Wp, bp,
+                                                 W_cq.data_ptr(), b_cq.data_ptr(), w_ca.data_ptr(), b_ca.data_ptr(),
+                                                 _ptr(drop_node), _ptr(drop_cat), _ptr(drop_tok), B, T, D, n,
+                                                 ins.data_ptr(), attn.data_ptr(), reserve.data_ptr(), reserve.numel(),
+                                                 _stream()), "gnnrag_instructions_train")
+    return ins, attn, reserve
+
+
+INS_GRADS = ("dhidden", "dnode", "dr_in", "dW_q", "db_q", "dW_cq", "db_cq", "dw_ca", "db_ca")
+
+
+def instructions_backward(hidden, node, W_q, W_cq, w_ca, ins, attn, reserve, g_ins=None, g_attn=None, r_in=None,
+                          drop_node=None, drop_cat=None, drop_tok=None, need=None):
+    """Backward of :func:`instructions_train` (``gnnrag_instructions_backward``): hidden, node, the weights, r_in (None =
+    zeros) and the multipliers as given to the forward, ins / attn / reserve as it returned them, g_ins [n,B,D] /
+    g_attn [n,B,T] the incoming gradients (None = zeros).  ``need``: a dict over ``INS_GRADS`` of what is wanted (None: all; ``dW_q`` /
+    ``db_q`` take one bool or a list with one per step).  Returns a dict over ``INS_GRADS``: dhidden
+    [B,T,D], dnode [B,D], dr_in [B,D], dW_q / db_q lists per step, dW_cq [D,4D], db_cq [D], dw_ca [D], db_ca [1] (exactly
+    zero); an output that is not wanted is None and is not computed.  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok, (B, T, D, n) = _ins_args(
+        hidden, node, W_q, W_cq, w_ca, r_in, drop_node, drop_cat, drop_tok)
+    ins = _chk(ins, "ins", shape=(n, B, D))
+    attn = _chk(attn, "attn", shape=(n, B, T))
+    reserve = _chk(reserve, "reserve", dtype=torch.uint8)
+    g_ins = None if g_ins is None else _chk(g_ins, "g_ins", shape=(n, B, D))
+    g_attn = None if g_attn is None else _chk(g_attn, "g_attn", shape=(n, B, T))
+    need = {k: True for k in INS_GRADS} if need is None else need
+
+    def per_step(k):
+        v = need.get(k)
+        return [bool(x) for x in v] if isinstance(v, (list, tuple)) else [bool(v)] * n
+
+    dev = hidden.device
+    role = "instructions_backward: "
+    shapes = {"dhidden": (B, T, D), "dnode": (B, D), "dr_in": (B, D), "dW_cq": (D, 4 * D), "db_cq": (D,), "dw_ca": (D,),
+              "db_ca": (1,)}
+    out = {k: (_buf(shp, torch.float32, dev, role + k) if need.get(k) else None) for k, shp in shapes.items()}
+    out["dW_q"] = [_buf((D, D), torch.float32, dev, role + "dW_q") if w else None for w in per_step("dW_q")]
+    out["db_q"] = [_buf((D,), torch.float32, dev, role + "db_q") if w else None for w in per_step("db_q")]
+    Wp = (C.c_void_p * n)(*[w.data_ptr() for w in W_q])
+    dWp = (C.c_void_p * n)(*[_ptr(t) for t in out["dW_q"]])
+    dbp = (C.c_void_p * n)(*[_ptr(t) for t in out["db_q"]])
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn inside): query it on hidden's device
+        ws = _buf(max(lib.gnnrag_instructions_backward_workspace_bytes(B, T, D, n), 16), torch.uint8, dev,
+                  role + "workspace")
+        _lib.check(lib.gnnrag_instructions_backward(
+            hidden.data_ptr(), node.data_ptr(), _ptr(r_in), Wp, W_cq.data_ptr(), w_ca.data_ptr(), _ptr(drop_node),
+            _ptr(drop_cat), _ptr(drop_tok), ins.data_ptr(), attn.data_ptr(), reserve.data_ptr(), reserve.numel(),
+            _ptr(g_ins), _ptr(g_attn), _ptr(out["dhidden"]), _ptr(out["dnode"]), _ptr(out["dr_in"]), dWp, dbp,
+            _ptr(out["dW_cq"]), _ptr(out["db_cq"]), _ptr(out["dw_ca"]), _ptr(out["db_ca"]), B, T, D, n, ws.data_ptr(),
+            ws.numel(), _stream()), "gnnrag_instructions_backward")
+    return out
+
+
 REL_TEXT_MAX_T, REL_TEXT_MAX_K, REL_TEXT_MAX_D = 256, 4096, 4096     # GNNRAG_REL_TEXT_MAX_* (include/gnnrag.h)
 
 

@@ -613,6 +613,56 @@ int gnnrag_instructions(const float* hidden, const float* node, const float* mas
                         const float* w_ca, const float* b_ca, int32_t B, int32_t T, int32_t D, int32_t n_steps,
                         float* ins_out, float* attn_out, gnnrag_stream_t stream);
 
+/* ---- Training form of instruction generation (additive to ABI 16; SURVEY.md section 8 f-4, the instruction side) --------
+ * gnnrag_instructions_train is gnnrag_instructions - the same kernel behind compile-time switches - plus
+ *   drop_node [n_steps,B,D], drop_cat [n_steps,B,4D], drop_tok [n_steps,B,T,D]: the three multipliers of linear_drop
+ *     (base_encoder.py:92, :93, :95; 0 or 1/(1-p)), each may be NULL (all ones):
+ *       n_s = node * drop_node[s]          z = [r, q, q - r, q * r] * drop_cat[s]
+ *       ca_t = sum_d w_ca[d] ((cq[d] hidden[t,d]) * drop_tok[s,t,d]) + b_ca
+ *   reserve: caller-owned, gnnrag_instructions_reserve_bytes(B, T, D, n_steps) bytes, fully written: q_s [D] then cq [D]
+ *     of every (step, question), [n_steps,B,2D].  It belongs to ONE forward call.
+ * With all three multipliers NULL, ins_out / attn_out are the bits of gnnrag_instructions.  Limits as there; a reserve below
+ * the stated size is GNNRAG_E_WORKSPACE before anything is launched. */
+size_t gnnrag_instructions_reserve_bytes(int32_t B, int32_t T, int32_t D, int32_t n_steps);
+int gnnrag_instructions_train(const float* hidden, const float* node, const float* mask, const float* r_in,
+                              const float* const* W_q, const float* const* b_q, const float* W_cq, const float* b_cq,
+                              const float* w_ca, const float* b_ca, const float* drop_node, const float* drop_cat,
+                              const float* drop_tok, int32_t B, int32_t T, int32_t D, int32_t n_steps, float* ins_out,
+                              float* attn_out, void* reserve, size_t reserve_bytes, gnnrag_stream_t stream);
+
+/* Backward of the call above: what autograd derives for get_instruction in Trainer_KBQA.train_epoch
+ * (train_model.py:209-233).  hidden, node, r_in (NULL = zeros), W_q, W_cq, w_ca and the multipliers as given to the
+ * forward, ins / attn / reserve as it left them; g_ins [n_steps,B,D], g_attn [n_steps,B,T]: the incoming gradients, each
+ * may be NULL (zeros).  With r = the instruction before step s and dr' = g_ins[s] + carry, for s = n_steps-1 .. 0:
+ *   da_t  = dr' . hidden[t,:] + g_attn[s,t]          dca_t = a_t (da_t - sum_u a_u da_u)
+ *   dhidden[t,d] += a_t dr'[d] + dca_t w_ca[d] cq[d] drop_tok[t,d]
+ *   u[d]  = sum_t dca_t hidden[t,d] drop_tok[t,d]    dcq = w_ca * u          dw_ca += cq * u
+ *   dz    = (W_cq^T dcq) * drop_cat                  carry = dz0 - dz2 + dz3 * q        dq = dz1 + dz2 + dz3 * r
+ *   dW_cq += dcq (x) z    db_cq += dcq    dW_q[s] += dq (x) n_s    db_q[s] += dq    dnode += (W_q[s]^T dq) * drop_node
+ * and dr_in = carry after step 0.  The gradient passes the mask addition with derivative 1, as autograd's does (a question
+ * of padding only has a = 1/T and a non-zero dca).  b_ca does not move the softmax: db_ca is written as exactly 0.
+ * dhidden [B,T,D], dnode [B,D], dr_in [B,D], dW_q / db_q (HOST arrays of n_steps device pointers, [D,D] and [D]; the
+ * array or an entry may be NULL), dW_cq [D,4D], db_cq [D], dw_ca [D], db_ca [1]: each may be NULL - not wanted, not
+ * computed; every requested output is fully written.
+ * One workgroup per question walks the chain with its token states in LDS; a dhidden element belongs to one thread in
+ * every step; the transposed products sum over the rows of W in ascending order; the token sums use the forward's
+ * __shfl_xor tree and ascending t.  The parameter gradients are gnnrag_gemm_tn products over the per-(step, question) rows
+ * the kernel leaves in the workspace (zero-padded copies for D % 4 != 0) and column sums in 8 row slices added in order.
+ * One fixed summation order, no atomics, no allocation, nothing waits for the stream: a repeated call gives the same bits.
+ * Limits: n_steps <= GNNRAG_MAX_INS and a working set of 4 * (ceil4(T D) + 12 D + 3 T) bytes within 160 KB (every
+ * T <= 64 with D <= 256 fits), workspace 16-byte aligned, else GNNRAG_E_UNSUPPORTED.  A reserve below
+ * gnnrag_instructions_reserve_bytes or a workspace below gnnrag_instructions_backward_workspace_bytes(B, T, D, n_steps)
+ * (0 for a shape outside the limits; like gnnrag_gemm_tn_workspace_bytes it depends on the current device) is
+ * GNNRAG_E_WORKSPACE.  Both are answered before anything is launched. */
+size_t gnnrag_instructions_backward_workspace_bytes(int32_t B, int32_t T, int32_t D, int32_t n_steps);
+int gnnrag_instructions_backward(const float* hidden, const float* node, const float* r_in, const float* const* W_q,
+                                 const float* W_cq, const float* w_ca, const float* drop_node, const float* drop_cat,
+                                 const float* drop_tok, const float* ins, const float* attn, const void* reserve,
+                                 size_t reserve_bytes, const float* g_ins, const float* g_attn, float* dhidden,
+                                 float* dnode, float* dr_in, float* const* dW_q, float* const* db_q, float* dW_cq,
+                                 float* db_cq, float* dw_ca, float* db_ca, int32_t B, int32_t T, int32_t D,
+                                 int32_t n_steps, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
 /* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
  * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):
  * question_emb over the frozen LM token states of the relation vocabulary, then AttnEncoder
