@@ -153,6 +153,14 @@ SIGNATURES = {
     "gnnrag_instructions_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
     "gnnrag_instructions_backward": (C.c_int, [_VP] * 3 + [C.POINTER(C.c_void_p)] + [_VP] * 8 + [C.c_size_t] + [_VP] * 5 +
                                      [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP, C.c_size_t, _VP]),
+    # training form of the instruction update (additive to ABI 16)
+    "gnnrag_query_reform_reserve_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_query_reform_train": (C.c_int, [C.POINTER(C.c_void_p), _VP, _VP, C.c_int64] + [C.POINTER(C.c_void_p)] * 2 +
+                                  [_VP, _VP, C.c_size_t] + [C.c_int32] * 4 + [_VP]),
+    "gnnrag_query_reform_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_query_reform_backward": (C.c_int, [C.POINTER(C.c_void_p), _VP] + [C.POINTER(C.c_void_p)] * 2 +
+                                     [_VP, C.c_size_t] + [C.POINTER(C.c_void_p)] * 4 + [_VP] + [C.c_int32] * 4 +
+                                     [_VP, C.c_size_t, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

@@ -8,7 +8,8 @@ through ``reason_layer`` / ``reason_layer_inv`` (``reasongnn.py:61-116``) and ``
 both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gemm_tn`` for dW).  The question
 encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``), the relation-text
 features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``), instruction generation on
-:class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``)."""
+:class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``), the instruction update between
+two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -227,3 +228,41 @@ class InstructionsFn(torch.autograd.Function):
         view = lambda t, shape: None if t is None else t.view(shape)      # noqa: E731
         return (g["dhidden"], g["dnode"], None, g["dr_in"], g["dW_cq"], g["db_cq"], view(g["dw_ca"], ctx.w_ca_shape),
                 view(g["db_ca"], ctx.b_ca_shape), None, None, None, *g["dW_q"], *g["db_q"])
+
+
+class QueryReformFn(torch.autograd.Function):
+    """``out_0 .. out_{n-1}`` [B,D] = the n reforms of one ReaRev iteration (rearev.py:217-221; query_update.py:26-44) on
+    ``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``.  ``rest``: the reforms' instructions [B,D], then their
+    ``fusion.r.weight``, then their ``fusion.g.weight`` (3 n tensors).  ent_emb [B,N,D] is the shared node state: it gets ONE
+    dense gradient (the reforms' seed-row gradients added inside the kernel), and none is computed when it needs none.  The
+    reserve is saved in the context of THIS call.  ``seed_info`` never receives a gradient."""
+
+    @staticmethod
+    def forward(ctx, seed_info, ent_emb, *rest):
+        n = len(rest) // 3
+        qs = [q.detach().float() for q in rest[:n]]
+        W_rs, W_gs = [w.detach() for w in rest[n:2 * n]], [w.detach() for w in rest[2 * n:]]
+        seed_info = seed_info.detach()
+        out, reserve = ops.query_reform_train(qs, seed_info, ent_emb.detach(), W_rs, W_gs)
+        ctx.set_materialize_grads(False)            # an unused output arrives as None and goes to the library as NULL
+        ctx.n, ctx.ent_width = n, ent_emb.shape[2]
+        ctx.save_for_backward(seed_info, reserve, *qs, *W_rs, *W_gs)
+        return tuple(out.unbind(0))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *g_outs):
+        n, nig = ctx.n, ctx.needs_input_grad
+        seed_info, reserve = ctx.saved_tensors[:2]
+        qs, W_rs, W_gs = (list(ctx.saved_tensors[2 + k * n:2 + (k + 1) * n]) for k in range(3))
+        need = {"d_ent": nig[1], "dq": list(nig[2:2 + n]), "dW_r": list(nig[2 + n:2 + 2 * n]),
+                "dW_g": list(nig[2 + 2 * n:2 + 3 * n])}
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as out.sum().backward() delivers
+        g_outs = [None if g is None else g.float() for g in g_outs]
+        if all(g is None for g in g_outs):
+            return (None,) * (2 + 3 * n)
+        g = ops.query_reform_backward(qs, seed_info, W_rs, W_gs, reserve, g_outs, need=need)
+        d_ent = g["d_ent"]
+        if d_ent is not None and ctx.ent_width != d_ent.shape[2]:       # a node state wider than the instructions
+            d_ent = torch.nn.functional.pad(d_ent, (0, ctx.ent_width - d_ent.shape[2]))
+        return (None, d_ent, *g["dq"], *g["dW_r"], *g["dW_g"])

@@ -39,12 +39,16 @@ __global__ __launch_bounds__(256) void k_seed_retrieve(const float* __restrict__
 // Workgroup (b, s): part s of the D outputs of question b (every part retrieves y itself: one or two rows); a wave
 // owns an output at a time, its lanes stride over the 3 D terms (coalesced rows of W), fixed shuffle tree: one
 // summation order.  ent_emb rows may be padded (row stride ldE >= D).
-__global__ __launch_bounds__(256) void k_query_reform(const float* __restrict__ q, const float* __restrict__ seed,
-                                                      const float* __restrict__ ent, const float* __restrict__ Wr,
-                                                      const float* __restrict__ Wg, float* __restrict__ out, int N, int D,
-                                                      int ldE) {
+// The body of k_query_reform / k_query_reform_train for question b, output part `part` of `nparts`.  SAVE (training form):
+// the retrieved y (once per question: by part 0 when save_y) and a_r = W_r feats, the gate of every output go to the caller's
+// reserve; the arithmetic and its order are the same instructions either way, so the outputs carry the same bits.
+template <bool SAVE>
+__device__ __forceinline__ void query_reform_body(const float* __restrict__ q, const float* __restrict__ seed,
+                                                  const float* __restrict__ ent, const float* __restrict__ Wr,
+                                                  const float* __restrict__ Wg, float* __restrict__ out, int N, int D,
+                                                  int ldE, int b, int part, int nparts, float* __restrict__ y_res,
+                                                  float* __restrict__ ag_res, bool save_y) {
   extern __shared__ float feats[];                       // [3 D]
-  const int b = blockIdx.x, part = blockIdx.y, nparts = gridDim.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float* s = seed + (size_t)b * N;
   const float* e = ent + (size_t)b * N * ldE;
@@ -67,6 +71,7 @@ __global__ __launch_bounds__(256) void k_query_reform(const float* __restrict__ 
       feats[c] = x;
       feats[D + c] = acc;
       feats[2 * D + c] = x - acc;
+      if (SAVE && save_y) y_res[(size_t)b * D + c] = acc;
     }
   }
   __syncthreads();
@@ -97,12 +102,49 @@ __global__ __launch_bounds__(256) void k_query_reform(const float* __restrict__ 
     if (lane == 0) {
       const float gate = 1.f / (1.f + expf(-ag0));
       out[(size_t)b * D + j] = gate * ar0 + (1.f - gate) * feats[j];
+      if (SAVE) {
+        ag_res[(size_t)b * 2 * D + j] = ar0;
+        ag_res[(size_t)b * 2 * D + D + j] = gate;
+      }
     }
     if (lane == 1 && jb != j) {
       const float gate = 1.f / (1.f + expf(-ag1));
       out[(size_t)b * D + jb] = gate * ar1 + (1.f - gate) * feats[jb];
+      if (SAVE) {
+        ag_res[(size_t)b * 2 * D + jb] = ar1;
+        ag_res[(size_t)b * 2 * D + D + jb] = gate;
+      }
     }
   }
+}
+
+__global__ __launch_bounds__(256) void k_query_reform(const float* __restrict__ q, const float* __restrict__ seed,
+                                                      const float* __restrict__ ent, const float* __restrict__ Wr,
+                                                      const float* __restrict__ Wg, float* __restrict__ out, int N, int D,
+                                                      int ldE) {
+  query_reform_body<false>(q, seed, ent, Wr, Wg, out, N, D, ldE, blockIdx.x, blockIdx.y, gridDim.y, nullptr, nullptr,
+                           false);
+}
+
+// The reforms of one iteration (rearev.py:217-221) in one launch: workgroup (b, part, j) is k_query_reform's (b, part) on
+// reform j's instruction and Fusion weights; the reforms share the node state and the seeds.
+struct QrTrainArgs {
+  const float* q[GNNRAG_MAX_REFORMS];    // [B, D]
+  const float* Wr[GNNRAG_MAX_REFORMS];   // [D, 3D]
+  const float* Wg[GNNRAG_MAX_REFORMS];   // [D, 3D]
+  const float* seed;                     // [B, N]
+  const float* ent;                      // [B, N, ldE]
+  float* out;                            // [n, B, D]
+  float* y;                              // reserve: [B, D]
+  float* ag;                             // reserve: [n, B, 2D]  (a_r, gate)
+  int32_t B, N, D, ldE;
+};
+
+__global__ __launch_bounds__(256) void k_query_reform_train(const QrTrainArgs g) {
+  const int j = blockIdx.z;
+  query_reform_body<true>(g.q[j], g.seed, g.ent, g.Wr[j], g.Wg[j], g.out + (size_t)j * g.B * g.D, g.N, g.D, g.ldE,
+                          blockIdx.x, blockIdx.y, gridDim.y, g.y, g.ag + (size_t)j * g.B * 2 * g.D,
+                          j == 0 && blockIdx.y == 0);
 }
 
 }  // namespace gnnrag
@@ -128,6 +170,41 @@ extern "C" int gnnrag_query_reform(const float* q_node, const float* seed_info, 
   parts = parts < 1 ? 1 : parts > 8 ? 8 : parts;
   hipLaunchKernelGGL(k_query_reform, dim3(B, parts), dim3(256), (size_t)3 * D * sizeof(float), (hipStream_t)stream, q_node,
                      seed_info, ent_emb, W_r, W_g, out, N, D, (int)ld_ent);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t gnnrag_query_reform_reserve_bytes(int32_t B, int32_t D, int32_t n) {
+  if (B <= 0 || D <= 0 || D > GNNRAG_QUERY_REFORM_MAX_D || n <= 0 || n > GNNRAG_MAX_REFORMS) return 0;
+  return ((size_t)B * D + (size_t)n * B * 2 * D) * sizeof(float);
+}
+
+extern "C" int gnnrag_query_reform_train(const float* const* q, const float* seed_info, const float* ent_emb,
+                                         int64_t ld_ent, const float* const* W_r, const float* const* W_g, float* out,
+                                         void* reserve, size_t reserve_bytes, int32_t B, int32_t N, int32_t D, int32_t n,
+                                         gnnrag_stream_t stream) {
+  if (!q || !seed_info || !ent_emb || !W_r || !W_g || !out || B <= 0 || N <= 0 || D <= 0 || n <= 0 || ld_ent < D)
+    return GNNRAG_E_BADARG;
+  if (n > GNNRAG_MAX_REFORMS || D > GNNRAG_QUERY_REFORM_MAX_D || ld_ent > INT32_MAX) return GNNRAG_E_UNSUPPORTED;
+  for (int j = 0; j < n; ++j)
+    if (!q[j] || !W_r[j] || !W_g[j]) return GNNRAG_E_BADARG;
+  if (!reserve || reserve_bytes < gnnrag_query_reform_reserve_bytes(B, D, n)) return GNNRAG_E_WORKSPACE;
+  QrTrainArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int j = 0; j < n; ++j) {
+    a.q[j] = q[j];
+    a.Wr[j] = W_r[j];
+    a.Wg[j] = W_g[j];
+  }
+  a.seed = seed_info; a.ent = ent_emb; a.out = out;
+  a.y = (float*)reserve;
+  a.ag = a.y + (size_t)B * D;
+  a.B = B; a.N = N; a.D = D; a.ldE = (int32_t)ld_ent;
+  // as gnnrag_query_reform, counting the (question, reform) pairs: no output depends on the number of parts
+  int parts = (int)((256 + (int64_t)B * n - 1) / ((int64_t)B * n));
+  parts = parts < 1 ? 1 : parts > 8 ? 8 : parts;
+  hipLaunchKernelGGL(k_query_reform_train, dim3(B, parts, n), dim3(256), (size_t)3 * D * sizeof(float),
+                     (hipStream_t)stream, a);
   GNNRAG_LAUNCH_CHECK();
   return 0;
 }

@@ -203,6 +203,8 @@ def swap(model, args: dict):
         new_r.train(old_r.training)
         setattr(model, "reform" + str(j), new_r)
         j += 1
+    from .modules.query_update import bind_reforms
+    bind_reforms(model)                     # an iteration's reforms as one call (GNNRAG_HIP_QUERY_REFORM_TRAIN=1)
     if hasattr(model, "get_rel_feature"):
         patch_rel_feature(model)            # underneath the cache: its one computation per parameter version
         cache_rel_features(model)

@@ -1184,6 +1184,114 @@ def query_reform(q_node: torch.Tensor, seed_info: torch.Tensor, ent_emb: torch.T
     return out
 
 
+MAX_REFORMS, QUERY_REFORM_MAX_D = 8, 4096       # GNNRAG_MAX_REFORMS, GNNRAG_QUERY_REFORM_MAX_D (include/gnnrag.h)
+
+
+def query_reform_backward_supported(D: int, n: int) -> bool:
+    """Whether ``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward`` take the shape.  The backward's LDS need
+    (5 D floats) stays inside a CU's 160 KB at the forward's limit, so the limits are the forward's."""
+    return 0 < D <= QUERY_REFORM_MAX_D and 0 < n <= MAX_REFORMS
+
+
+def _ent_in_place(ent_emb: torch.Tensor, B: int, N: int):
+    """(tensor, row stride): a node state whose last dimension is contiguous and whose rows are evenly spaced (a
+    zero-padded state, or the view ``padded[:, :, :D]`` of one) is read where it lies; anything else is copied."""
+    ld = ent_emb.stride(1)
+    if ent_emb.stride(2) == 1 and ld >= ent_emb.shape[2] and ent_emb.stride(0) == N * ld:
+        return ent_emb, ld
+    ent_emb = ent_emb.contiguous()
+    return ent_emb, ent_emb.shape[2]
+
+
+def _qr_args(qs, seed_info, W_rs, W_gs):
+    n = len(qs)
+    if n == 0 or len(W_rs) != n or len(W_gs) != n:
+        raise ValueError("query_reform: qs, W_rs and W_gs must be lists of the same length >= 1")
+    qs = [_chk(q.detach(), "qs[%d]" % j) for j, q in enumerate(qs)]
+    if qs[0].dim() != 2:
+        raise ValueError("query_reform: every q must be [B,D]")
+    B, D = qs[0].shape
+    seed_info = _chk(seed_info.detach(), "seed_info")
+    if seed_info.dim() != 2 or seed_info.shape[0] != B:
+        raise ValueError("query_reform: seed_info must be [B,N]")
+    for j in range(n):
+        _chk(qs[j], "qs[%d]" % j, shape=(B, D))
+    W_rs = [_chk(w.detach(), "W_rs[%d]" % j, shape=(D, 3 * D)) for j, w in enumerate(W_rs)]
+    W_gs = [_chk(w.detach(), "W_gs[%d]" % j, shape=(D, 3 * D)) for j, w in enumerate(W_gs)]
+    return qs, seed_info, W_rs, W_gs, (B, seed_info.shape[1], D, n)
+
+
+def _ptr_array(tensors):
+    return (C.c_void_p * max(len(tensors), 1))(*[_ptr(t) for t in tensors])
+
+
+def query_reform_train(qs, seed_info, ent_emb, W_rs, W_gs):
+    """The ``n = len(qs)`` reforms of one ReaRev iteration (rearev.py:217-221) in one launch
+    (``gnnrag_query_reform_train``): ``qs`` / ``W_rs`` / ``W_gs`` LISTS of the reforms' instructions [B,D] and Fusion weights
+    [D,3D]; one seed_info [B,N] and one ent_emb [B,N,D'] (D' >= D; last dimension contiguous and evenly spaced rows: read in
+    place by its row stride) for all of them.  Returns (out [n,B,D], reserve): ``out[j]`` carries the bits of
+    :func:`query_reform` on reform j; the reserve (a uint8 tensor of ``gnnrag_query_reform_reserve_bytes``: the retrieved
+    rows, ``W_r f`` and the gates) is allocated per call and belongs to this forward - :func:`query_reform_backward` reads it.
+    A shape outside the library's limits raises ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    qs, seed_info, W_rs, W_gs, (B, N, D, n) = _qr_args(qs, seed_info, W_rs, W_gs)
+    if not ent_emb.is_cuda:
+        _chk(ent_emb, "ent_emb")
+    if ent_emb.dtype != torch.float32:
+        raise TypeError("ent_emb must be torch.float32, got %s" % ent_emb.dtype)
+    if ent_emb.dim() != 3 or ent_emb.shape[0] != B or ent_emb.shape[1] != N or ent_emb.shape[2] < D:
+        raise ValueError("query_reform_train: q [B,D], seed_info [B,N], ent_emb [B,N,>=D]")
+    ent_emb, ld = _ent_in_place(ent_emb.detach(), B, N)
+    dev = qs[0].device
+    out = _buf((n, B, D), torch.float32, dev, "query_reform_train: out")
+    reserve = _buf(lib.gnnrag_query_reform_reserve_bytes(B, D, n), torch.uint8, dev, "query_reform_train: reserve")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_query_reform_train(_ptr_array(qs), seed_info.data_ptr(), ent_emb.data_ptr(), ld,
+                                                 _ptr_array(W_rs), _ptr_array(W_gs), out.data_ptr(), reserve.data_ptr(),
+                                                 reserve.numel(), B, N, D, n, _stream()), "gnnrag_query_reform_train")
+    return out, reserve
+
+
+QR_GRADS = ("dq", "dW_r", "dW_g", "d_ent")
+
+
+def query_reform_backward(qs, seed_info, W_rs, W_gs, reserve, g_outs, need=None):
+    """Backward of :func:`query_reform_train` (``gnnrag_query_reform_backward``): qs, seed_info and the weights as given to
+    the forward, the reserve it returned, ``g_outs``: a list of n gradients [B,D] of ``out[j]``; a ``None`` entry means that
+    reform's output was not used - nothing is computed for it and it adds nothing to ``d_ent``.  ``need``: a dict over
+    ``QR_GRADS`` of what is wanted (None: all; ``dq`` / ``dW_r`` / ``dW_g`` take one bool or a list with one per reform).
+    Returns a dict over ``QR_GRADS``: dq / dW_r / dW_g lists per reform ([B,D], [D,3D]; None where not wanted or where the
+    reform's ``g_outs`` entry is None), d_ent [B,N,D] (every element written; None when not wanted).  One fixed summation
+    order: the same bits every time."""
+    lib = _lib.load()
+    qs, seed_info, W_rs, W_gs, (B, N, D, n) = _qr_args(qs, seed_info, W_rs, W_gs)
+    reserve = _chk(reserve, "reserve", dtype=torch.uint8)
+    if len(g_outs) != n:
+        raise ValueError("query_reform_backward: g_outs must have one entry (or None) per reform")
+    g_outs = [None if g is None else _chk(g, "g_outs[%d]" % j, shape=(B, D)) for j, g in enumerate(g_outs)]
+    need = {k: True for k in QR_GRADS} if need is None else need
+
+    def per_reform(k):
+        v = need.get(k)
+        v = [bool(x) for x in v] if isinstance(v, (list, tuple)) else [bool(v)] * n
+        return [w and g is not None for w, g in zip(v, g_outs)]
+
+    dev = qs[0].device
+    role = "query_reform_backward: "
+    out = {"dq": [_buf((B, D), torch.float32, dev, role + "dq") if w else None for w in per_reform("dq")],
+           "dW_r": [_buf((D, 3 * D), torch.float32, dev, role + "dW_r") if w else None for w in per_reform("dW_r")],
+           "dW_g": [_buf((D, 3 * D), torch.float32, dev, role + "dW_g") if w else None for w in per_reform("dW_g")],
+           "d_ent": _buf((B, N, D), torch.float32, dev, role + "d_ent") if need.get("d_ent") else None}
+    with torch.cuda.device(dev):
+        ws = _buf(max(lib.gnnrag_query_reform_backward_workspace_bytes(B, N, D, n), 16), torch.uint8, dev,
+                  role + "workspace")
+        _lib.check(lib.gnnrag_query_reform_backward(
+            _ptr_array(qs), seed_info.data_ptr(), _ptr_array(W_rs), _ptr_array(W_gs), reserve.data_ptr(), reserve.numel(),
+            _ptr_array(g_outs), _ptr_array(out["dq"]), _ptr_array(out["dW_r"]), _ptr_array(out["dW_g"]),
+            _ptr(out["d_ent"]), B, N, D, n, ws.data_ptr(), ws.numel(), _stream()), "gnnrag_query_reform_backward")
+    return out
+
+
 MAX_INS = 8                                     # GNNRAG_MAX_INS (include/gnnrag.h)
 
 

@@ -546,6 +546,44 @@ int gnnrag_query_reform(const float* q_node, const float* seed_info, const float
                         const float* W_r, const float* W_g, float* out, int32_t B, int32_t N, int32_t D,
                         gnnrag_stream_t stream);
 
+/* Training form of the instruction update (additive to ABI 16): the n reforms of one ReaRev iteration
+ * (gnn/models/ReaRev/rearev.py:217-221) in ONE launch.  The reforms share seed_info [B, N] and ent_emb [B, N, ld_ent]; reform
+ * j < n has its own instruction q[j] [B, D] and Fusion weights W_r[j], W_g[j] [D, 3 D] - host arrays of n device pointers,
+ * carried in the kernel arguments.  out: [n, B, D]; out[j] carries the bits of a gnnrag_query_reform call on reform j's
+ * operands (the same kernel body), whatever grid the launcher picks.  reserve: caller-owned device memory of
+ * gnnrag_query_reform_reserve_bytes(B, D, n) bytes (0 for a shape outside the limits) that the backward reads: the retrieved
+ * y [B, D] once, then a_r = W_r f and the gate g = sigmoid(W_g f) as [n, B, 2 D].
+ * Limits: 1 <= n <= GNNRAG_MAX_REFORMS, D <= GNNRAG_QUERY_REFORM_MAX_D, else GNNRAG_E_UNSUPPORTED; a NULL entry in an array,
+ * n <= 0 or ld_ent < D is GNNRAG_E_BADARG; a reserve below the stated size is GNNRAG_E_WORKSPACE.  All are answered before
+ * anything is launched. */
+#define GNNRAG_MAX_REFORMS 8
+#define GNNRAG_QUERY_REFORM_MAX_D 4096
+size_t gnnrag_query_reform_reserve_bytes(int32_t B, int32_t D, int32_t n);
+int gnnrag_query_reform_train(const float* const* q, const float* seed_info, const float* ent_emb, int64_t ld_ent,
+                              const float* const* W_r, const float* const* W_g, float* out, void* reserve,
+                              size_t reserve_bytes, int32_t B, int32_t N, int32_t D, int32_t n, gnnrag_stream_t stream);
+
+/* Backward of gnnrag_query_reform_train (query_update_bwd.hip).  q, seed_info, W_r, W_g as given to the forward, its
+ * reserve, and g_out: n device pointers [B, D], the gradients of out[j]; a NULL ENTRY means that reform's output was not
+ * used: nothing is computed for it and it adds nothing to d_ent (a dq / dW asked for it anyway is written as zeros).  With
+ * x = q[j][b], f = [x, y, x - y], G = g_out[j][b]:
+ *   da_r = G g    da_g = G (a_r - x) g (1 - g)    df = W_r^T da_r + W_g^T da_g
+ *   dq[j][b] = G (1 - g) + df[0:D] + df[2D:3D]     dy_j = df[D:2D] - df[2D:3D]
+ *   dW_r[j] = sum_b da_r[b] (x) f[b]   dW_g[j] alike   d_ent[b,n,:] = seed_info[b,n] * (dy_j[b] added in ascending j)
+ * Outputs, each optional (a NULL array or entry is not computed): dq [n] x [B, D], dW_r / dW_g [n] x [D, 3 D], d_ent
+ * [B, N, D] contiguous - EVERY element is written (zero where seed_info is zero), nothing is accumulated into what it held.
+ * No atomics, no allocation, nothing waits for the stream; one summation order (rows of W ascending, questions ascending,
+ * reforms ascending): a second call gives the same bits, dq and d_ent of a question do not depend on B or on its place in
+ * the batch.  LDS: 5 D floats, inside a CU's 160 KB at the forward's limit: the limits are the forward's.  workspace:
+ * gnnrag_query_reform_backward_workspace_bytes(B, N, D, n) bytes (0 outside the limits); too small a reserve or workspace is
+ * GNNRAG_E_WORKSPACE before anything is launched. */
+size_t gnnrag_query_reform_backward_workspace_bytes(int32_t B, int32_t N, int32_t D, int32_t n);
+int gnnrag_query_reform_backward(const float* const* q, const float* seed_info, const float* const* W_r,
+                                 const float* const* W_g, const void* reserve, size_t reserve_bytes,
+                                 const float* const* g_out, float* const* dq, float* const* dW_r, float* const* dW_g,
+                                 float* d_ent, int32_t B, int32_t N, int32_t D, int32_t n, void* workspace,
+                                 size_t workspace_bytes, gnnrag_stream_t stream);
+
 /* The question encoder's LSTM (the instruction path): one layer, one direction, batch_first,
  * torch.nn.LSTM semantics and parameter layout (gate order i, f, g, o) - what
  * gnn/modules/question_encoding/lstm_encoder.py:27-36 builds and calls as

@@ -90,6 +90,17 @@ def main():
             # the question encoder's nn.LSTM -> HipLSTM: under autograd it trains on the library unless
             # GNNRAG_HIP_LSTM_TRAIN=0 hands the call back to the parent class (MIOpen's RNN)
             install.swap_lstm(tr.model)
+        # an iteration's reforms as one call; acts only with GNNRAG_HIP_QUERY_REFORM_TRAIN=1
+        from gnnrag_amd.modules.query_update import bind_reforms
+        bind_reforms(tr.model)
+        from gnnrag_amd import ops
+        _qr_train = ops.query_reform_train
+
+        def _counted(qs, *args, **kw):
+            qr_calls.append(len(qs))
+            return _qr_train(qs, *args, **kw)
+        ops.query_reform_train = _counted
+    qr_calls = []                # reforms per ops.query_reform_train call (none with the switch off)
     sync = (lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
     tr.model.train()
@@ -129,7 +140,10 @@ def main():
            "padded_nodes_per_question": int(tr.train_data.max_local_entity), "native_library": native,
            "layer_class": type(tr.model.reasoning).__module__,
            "lstm_class": sorted({type(m).__name__ for m in tr.model.modules() if isinstance(m, torch.nn.LSTM)}),
-           "hip_lstm_train": None if a.pure else os.environ.get("GNNRAG_HIP_LSTM_TRAIN", "default")}
+           "hip_lstm_train": None if a.pure else os.environ.get("GNNRAG_HIP_LSTM_TRAIN", "default"),
+           "hip_query_reform_train": None if a.pure else os.environ.get("GNNRAG_HIP_QUERY_REFORM_TRAIN", "default"),
+           "query_reform_train_calls_per_step": len(qr_calls) / float(a.warm + a.steps),
+           "reforms_per_query_reform_train_call": sorted(set(qr_calls))}
     import shutil
     shutil.rmtree(ck, ignore_errors=True)
     print("GNNRAG_TRAIN " + json.dumps(out))
