@@ -161,6 +161,11 @@ SIGNATURES = {
     "gnnrag_query_reform_backward": (C.c_int, [C.POINTER(C.c_void_p), _VP] + [C.POINTER(C.c_void_p)] * 2 +
                                      [_VP, C.c_size_t] + [C.POINTER(C.c_void_p)] * 4 + [_VP] + [C.c_int32] * 4 +
                                      [_VP, C.c_size_t, _VP]),
+    # the tail of the reasoning layer under autograd (additive to ABI 16)
+    "gnnrag_layer_tail_train": (C.c_int, [_VP] * 3 + [C.c_float] + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 4),
+    "gnnrag_layer_tail_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_layer_tail_backward": (C.c_int, [_VP] * 3 + [C.c_float] + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 4 +
+                                   [C.c_size_t, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

@@ -9,7 +9,8 @@ both directions (:class:`LinearFn`: ``gnnrag_linear`` for y and dx, ``gnnrag_gem
 encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnrag_lstm_backward``), the relation-text
 features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``), instruction generation on
 :class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``), the instruction update between
-two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``)."""
+two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``), the tail of the
+reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -266,3 +267,39 @@ class QueryReformFn(torch.autograd.Function):
         if d_ent is not None and ctx.ent_width != d_ent.shape[2]:       # a node state wider than the instructions
             d_ent = torch.nn.functional.pad(d_ent, (0, ctx.ent_width - d_ent.shape[2]))
         return (None, d_ent, *g["dq"], *g["dW_r"], *g["dW_g"])
+
+
+class LayerTailFn(torch.autograd.Function):
+    """``(h, score, dist)`` = the tail of the reasoning layer (reasongnn.py:163-169) on ``gnnrag_layer_tail_train`` /
+    ``gnnrag_layer_tail_backward``: pre_a, pre_b [B*N,D] (pre_b may be None) the pre-activations, keep [B*N,D] uint8 / scale
+    the dropout in front of the score function (keep None: none), w = ``score_func.weight`` [1,D], b = ``score_func.bias``
+    [1], mask [B,N].  ``score`` is not differentiable (the reference hands it out with ``return_score`` only, and the module
+    keeps that case on torch); pre_a and pre_b receive the one gradient buffer the library writes."""
+
+    @staticmethod
+    def forward(ctx, pre_a, pre_b, keep, scale, w, b, mask):
+        wd = w.detach().float().reshape(-1)
+        h, score, dist = ops.layer_tail_train(pre_a.detach(), None if pre_b is None else pre_b.detach(), keep, scale, wd,
+                                              b.detach().float(), mask.detach())
+        ctx.mark_non_differentiable(score)
+        ctx.set_materialize_grads(False)            # an unused h or dist arrives as None and goes to the library as NULL
+        ctx.scale, ctx.has_keep, ctx.has_b = float(scale), keep is not None, pre_b is not None
+        ctx.w_shape, ctx.b_shape = w.shape, b.shape
+        ctx.save_for_backward(h, dist, wd, *([keep] if keep is not None else []))
+        return h, score, dist
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_h, _g_score, g_dist):
+        if g_h is None and g_dist is None:
+            return (None,) * 7
+        h, dist, wd = ctx.saved_tensors[:3]
+        keep = ctx.saved_tensors[3] if ctx.has_keep else None
+        nig = ctx.needs_input_grad
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as h.sum().backward() delivers
+        g = ops.layer_tail_backward(h, dist, keep, ctx.scale, wd, None if g_h is None else g_h.float(),
+                                    None if g_dist is None else g_dist.float(), need_dw=nig[4], need_db=nig[5])
+        g_pre = g["g_pre"]
+        return (g_pre if nig[0] else None, g_pre if (ctx.has_b and nig[1]) else None, None, None,
+                None if g["dw"] is None else g["dw"].view(ctx.w_shape), None if g["db"] is None else g["db"].view(ctx.b_shape),
+                None)

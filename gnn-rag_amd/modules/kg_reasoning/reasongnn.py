@@ -21,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ...autograd import AggregateFn, FusedAggregateFn, linear as ag_linear, relation_tables_dense
+from ...autograd import AggregateFn, FusedAggregateFn, LayerTailFn, linear as ag_linear, relation_tables_dense
 from .base_gnn import BaseGNNLayer
 
 VERY_NEG_NUMBER = -100000000000
@@ -273,7 +273,11 @@ class ReasonGNNLayer(BaseGNNLayer):
             W = e2e_linear.weight
             P = relation_tables_dense(self.plan, T_fwd, T_inv, relational_ins.float(), W)
             nbr = FusedAggregateFn.apply(self.plan, current_dist.float(), P)
-            pre = ag_linear(self.local_entity_emb.float().reshape(B * N, D), W[:, :D], e2e_linear.bias) + nbr
+            pre_self = ag_linear(self.local_entity_emb.float().reshape(B * N, D), W[:, :D], e2e_linear.bias)
+            got = self._layer_tail(pre_self, nbr, return_score)
+            if got is not None:
+                return got
+            pre = pre_self + nbr
             self.local_entity_emb = F.relu(pre).view(B, N, D)
             mask = self.local_entity_mask
             self.possible_cand.append(mask)
@@ -285,14 +289,50 @@ class ReasonGNNLayer(BaseGNNLayer):
             # e2e_linear over cat(h, agg) as two products (no [BN, (2I+1)D] copy of the concatenation): dropout acts
             # elementwise, so dropping the two parts separately is the same operator (reasongnn.py:161-163)
             W = e2e_linear.weight
-            pre = ag_linear(self.linear_drop(self.local_entity_emb.float()).reshape(B * N, D), W[:, :D], e2e_linear.bias) \
-                + ag_linear(self.linear_drop(agg), W[:, D:], None)
+            pre_self = ag_linear(self.linear_drop(self.local_entity_emb.float()).reshape(B * N, D), W[:, :D], e2e_linear.bias)
+            pre_nbr = ag_linear(self.linear_drop(agg), W[:, D:], None)
+            got = self._layer_tail(pre_self, pre_nbr, return_score)
+            if got is not None:
+                return got
+            pre = pre_self + pre_nbr
             self.local_entity_emb = F.relu(pre).view(B, N, D)
         else:
             state = torch.cat((self.local_entity_emb.float(), agg.view(B, N, -1)), dim=2)  # [h | fwd_0 | inv_0 | ...]
-            self.local_entity_emb = F.relu(e2e_linear(self.linear_drop(state)))
+            pre = e2e_linear(self.linear_drop(state))
+            got = self._layer_tail(pre, None, return_score)
+            if got is not None:
+                return got
+            self.local_entity_emb = F.relu(pre)
         mask = self.local_entity_mask
         self.possible_cand.append(mask)
         score = self.score_func(self.linear_drop(self.local_entity_emb)).squeeze(dim=2) + (1 - mask) * VERY_NEG_NUMBER
         new_dist = self.softmax_d1(score)
         return (score, new_dist) if return_score else (new_dist, self.local_entity_emb)
+
+    def _layer_tail(self, pre_a, pre_b, return_score):
+        """The rest of the layer (reasongnn.py:163-169: add, relu, dropout, score_func, mask, softmax) as ONE autograd node on
+        the library (``autograd.LayerTailFn``) when ``GNNRAG_HIP_LAYER_TAIL_TRAIN=1`` (read at every call, default off) and
+        the call is eligible; None otherwise - the caller then runs the torch ops, exactly as without the switch.  With
+        ``linear_drop`` active the keep flags of the dropout in front of ``score_func`` are drawn here from torch's
+        generator of the device: not the draws ``F.dropout`` would have made - a loss curve is comparable, not equal."""
+        if return_score or os.environ.get("GNNRAG_HIP_LAYER_TAIL_TRAIN", "0") != "1":
+            return None
+        B, N, D = self.batch_size, self.max_local_entity, self.entity_dim
+        sf, mask = self.score_func, self.local_entity_mask
+        if not (isinstance(sf, nn.Linear) and sf.bias is not None and tuple(sf.weight.shape) == (1, D)
+                and ops.layer_tail_supported(D)):
+            return None
+        pre_a = pre_a.reshape(B * N, D)
+        for t in (pre_a, pre_b, mask, sf.weight, sf.bias):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                return None
+        keep, scale, p = None, 1.0, self.linear_dropout
+        if self.training and p > 0:
+            if p >= 1:
+                return None
+            keep = torch.empty((B * N, D), dtype=torch.uint8, device=pre_a.device).bernoulli_(1 - p)
+            scale = 1.0 / (1.0 - p)
+        h, _, new_dist = LayerTailFn.apply(pre_a, pre_b, keep, scale, sf.weight, sf.bias, mask)
+        self.local_entity_emb = h.view(B, N, D)
+        self.possible_cand.append(mask)
+        return new_dist, self.local_entity_emb

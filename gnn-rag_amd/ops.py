@@ -1292,6 +1292,82 @@ def query_reform_backward(qs, seed_info, W_rs, W_gs, reserve, g_outs, need=None)
     return out
 
 
+LAYER_TAIL_MAX_D = 4096                         # GNNRAG_LAYER_TAIL_MAX_D (include/gnnrag.h)
+
+
+def layer_tail_supported(D: int) -> bool:
+    """Whether ``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward`` take the hidden size."""
+    return 0 < D <= LAYER_TAIL_MAX_D
+
+
+def _lt_keep(keep, rows: int, D: int, scale: float):
+    if keep is None:
+        return None, 1.0
+    return _chk(keep, "keep", dtype=torch.uint8, shape=(rows, D)), float(scale)
+
+
+def layer_tail_train(pre_a, pre_b, keep, scale, w, b, mask):
+    """The tail of the reasoning layer under autograd (reasongnn.py:163-169; ``gnnrag_layer_tail_train``): pre_a [B*N,D] and
+    pre_b (the same shape, or None) are the layer's pre-activations, ``keep`` [B*N,D] uint8 0/1 with ``scale`` the dropout
+    in front of ``score_func`` (None: no dropout, scale taken as 1), w [D] / b [1] the score function, mask [B,N].  Returns
+    (h [B*N,D] = relu(pre_a + pre_b), score [B,N], dist [B,N]); dist carries the bits of :func:`masked_softmax` of score.  A
+    hidden size outside the library's limit raises ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    mask = _chk(mask, "mask")
+    if mask.dim() != 2:
+        raise ValueError("layer_tail_train: mask must be [B,N]")
+    B, N = mask.shape
+    pre_a = _chk(pre_a, "pre_a")
+    if pre_a.dim() != 2 or pre_a.shape[0] != B * N:
+        raise ValueError("layer_tail_train: pre_a must be [B*N,D] for a mask [B,N]")
+    D = pre_a.shape[1]
+    pre_b = None if pre_b is None else _chk(pre_b, "pre_b", shape=(B * N, D))
+    keep, scale = _lt_keep(keep, B * N, D, scale)
+    w = _chk(w.reshape(-1), "w", shape=(D,))
+    b = _chk(b.reshape(-1), "b", shape=(1,))
+    dev, role = pre_a.device, "layer_tail_train: "
+    h = _buf((B * N, D), torch.float32, dev, role + "h")
+    score = _buf((B, N), torch.float32, dev, role + "score")
+    dist = _buf((B, N), torch.float32, dev, role + "dist")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_layer_tail_train(pre_a.data_ptr(), _ptr(pre_b), _ptr(keep), scale, w.data_ptr(), b.data_ptr(),
+                                               mask.data_ptr(), B, N, D, h.data_ptr(), score.data_ptr(), dist.data_ptr(),
+                                               _stream()), "gnnrag_layer_tail_train")
+    return h, score, dist
+
+
+def layer_tail_backward(h, dist, keep, scale, w, g_h, g_dist, need_dw: bool = True, need_db: bool = True):
+    """Backward of :func:`layer_tail_train` (``gnnrag_layer_tail_backward``): h and dist as it returned them, keep / scale / w
+    as it was given them, g_h [B*N,D] and g_dist [B,N] the upstream gradients (either may be None: that output was not
+    used; both None is refused by the library).  Returns a dict: ``g_pre`` [B*N,D] (the gradient of pre_a and of pre_b
+    alike, every element written), ``dw`` [D] and ``db`` [1] (exactly 0) or None where not wanted.  One fixed summation
+    order: the same bits every time."""
+    lib = _lib.load()
+    dist = _chk(dist, "dist")
+    if dist.dim() != 2:
+        raise ValueError("layer_tail_backward: dist must be [B,N]")
+    B, N = dist.shape
+    h = _chk(h, "h")
+    if h.dim() != 2 or h.shape[0] != B * N:
+        raise ValueError("layer_tail_backward: h must be [B*N,D] for a dist [B,N]")
+    D = h.shape[1]
+    keep, scale = _lt_keep(keep, B * N, D, scale)
+    w = _chk(w.reshape(-1), "w", shape=(D,))
+    g_h = None if g_h is None else _chk(g_h, "g_h", shape=(B * N, D))
+    g_dist = None if g_dist is None else _chk(g_dist, "g_dist", shape=(B, N))
+    dev, role = h.device, "layer_tail_backward: "
+    out = {"g_pre": _buf((B * N, D), torch.float32, dev, role + "g_pre"),
+           "dw": _buf((D,), torch.float32, dev, role + "dw") if need_dw else None,
+           "db": _buf((1,), torch.float32, dev, role + "db") if need_db else None}
+    with torch.cuda.device(dev):
+        ws = _buf(max(lib.gnnrag_layer_tail_backward_workspace_bytes(B, N, D), 16), torch.uint8, dev, role + "workspace")
+        _lib.check(lib.gnnrag_layer_tail_backward(h.data_ptr(), dist.data_ptr(), _ptr(keep), scale, w.data_ptr(), _ptr(g_h),
+                                                  _ptr(g_dist), B, N, D, out["g_pre"].data_ptr(), _ptr(out["dw"]),
+                                                  _ptr(out["db"]), ws.data_ptr(), ws.numel(), _stream()),
+                   "gnnrag_layer_tail_backward")
+    return out
+
+
 MAX_INS = 8                                     # GNNRAG_MAX_INS (include/gnnrag.h)
 
 

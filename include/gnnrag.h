@@ -584,6 +584,40 @@ int gnnrag_query_reform_backward(const float* const* q, const float* seed_info, 
                                  float* d_ent, int32_t B, int32_t N, int32_t D, int32_t n, void* workspace,
                                  size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* The tail of the reasoning layer under autograd (additive to ABI 16; layer_tail.hip): what
+ * gnn/modules/kg_reasoning/reasongnn.py:163-169 does after the dense products.  Rows r = b N + n, all tensors contiguous.
+ *   h     = max(pre_a + pre_b, 0)                       one fp32 add (pre_b NULL: none), then the relu
+ *   s     = scale * sum_d h[d] keep[d] w_score[d] + b_score        keep: 0/1 bytes, the dropout in front of score_func;
+ *                                                                   keep NULL: no dropout, scale is taken as 1
+ *   score = s + (1 - mask) * (-1e11)                    added in fp32 without contraction: a masked score is float(-1e11)
+ *   dist  = gnnrag_masked_softmax(score): the same launch, the same bits
+ * Two launches.  float4 accesses where D % 4 == 0 and the bases are 16-byte aligned (keep: 4-byte), element accesses with
+ * the same summation order otherwise: the same bits either way.  b_score is read on the device.
+ * Limits: D <= GNNRAG_LAYER_TAIL_MAX_D and B N < 2^31, else GNNRAG_E_UNSUPPORTED; a NULL among the required pointers or a
+ * size <= 0 is GNNRAG_E_BADARG.  Both are answered before anything is launched. */
+#define GNNRAG_LAYER_TAIL_MAX_D 4096
+int gnnrag_layer_tail_train(const float* pre_a, const float* pre_b, const uint8_t* keep, float scale,
+                            const float* w_score, const float* b_score, const float* mask, int32_t B, int32_t N, int32_t D,
+                            float* h_out, float* score, float* dist, gnnrag_stream_t stream);
+
+/* Backward of gnnrag_layer_tail_train from g_h [B N, D] (the gradient of h) and g_dist [B, N]; h and dist as the forward
+ * wrote them, keep / scale / w_score as it was given them.  Per question sigma = sum_n dist g_dist in one fixed order and
+ * gs[n] = dist[n] (g_dist[n] - sigma): the mask addition passes the gradient with derivative 1, as autograd does (a fully
+ * padded question has dist = 1/N and a non-zero gs).
+ *   g_pre[r,d] = h[r,d] > 0 ? g_h[r,d] + gs[r] w_score[d] keep[r,d] scale : 0     the gradient of pre_a and of pre_b alike;
+ *                                                                                 EVERY element is written
+ *   dw_score[d] = sum_r gs[r] keep[r,d] scale h[r,d]            db_score = 0 exactly (a softmax does not move under a shift)
+ * g_dist NULL: gs = 0 (g_pre = (h > 0) g_h, dw_score written as zeros); g_h NULL: that term is absent; both NULL is
+ * GNNRAG_E_BADARG.  dw_score / db_score NULL: not wanted.  Up to three launches, no atomics, no allocation, nothing waits
+ * for the stream; the grid and every summation order depend on (B, N, D) only: a second call gives the same bits, g_pre of a
+ * question does not depend on the batch around it.  workspace: gnnrag_layer_tail_backward_workspace_bytes(B, N, D) bytes (0
+ * outside the limits); a smaller one is GNNRAG_E_WORKSPACE before anything is launched. */
+size_t gnnrag_layer_tail_backward_workspace_bytes(int32_t B, int32_t N, int32_t D);
+int gnnrag_layer_tail_backward(const float* h, const float* dist, const uint8_t* keep, float scale, const float* w_score,
+                               const float* g_h, const float* g_dist, int32_t B, int32_t N, int32_t D, float* g_pre,
+                               float* dw_score, float* db_score, void* workspace, size_t workspace_bytes,
+                               gnnrag_stream_t stream);
+
 /* The question encoder's LSTM (the instruction path): one layer, one direction, batch_first,
  * torch.nn.LSTM semantics and parameter layout (gate order i, f, g, o) - what
  * gnn/modules/question_encoding/lstm_encoder.py:27-36 builds and calls as

@@ -100,7 +100,14 @@ def main():
             qr_calls.append(len(qs))
             return _qr_train(qs, *args, **kw)
         ops.query_reform_train = _counted
+        _lt_train = ops.layer_tail_train
+
+        def _lt_counted(*args, **kw):
+            lt_calls.append(1)
+            return _lt_train(*args, **kw)
+        ops.layer_tail_train = _lt_counted
     qr_calls = []                # reforms per ops.query_reform_train call (none with the switch off)
+    lt_calls = []                # ops.layer_tail_train calls (none without GNNRAG_HIP_LAYER_TAIL_TRAIN=1)
     sync = (lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
     tr.model.train()
@@ -143,7 +150,9 @@ def main():
            "hip_lstm_train": None if a.pure else os.environ.get("GNNRAG_HIP_LSTM_TRAIN", "default"),
            "hip_query_reform_train": None if a.pure else os.environ.get("GNNRAG_HIP_QUERY_REFORM_TRAIN", "default"),
            "query_reform_train_calls_per_step": len(qr_calls) / float(a.warm + a.steps),
-           "reforms_per_query_reform_train_call": sorted(set(qr_calls))}
+           "reforms_per_query_reform_train_call": sorted(set(qr_calls)),
+           "hip_layer_tail_train": None if a.pure else os.environ.get("GNNRAG_HIP_LAYER_TAIL_TRAIN", "default"),
+           "layer_tail_train_calls_per_step": len(lt_calls) / float(a.warm + a.steps)}
     import shutil
     shutil.rmtree(ck, ignore_errors=True)
     print("GNNRAG_TRAIN " + json.dumps(out))
