@@ -166,6 +166,11 @@ SIGNATURES = {
     "gnnrag_layer_tail_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "gnnrag_layer_tail_backward": (C.c_int, [_VP] * 3 + [C.c_float] + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 4 +
                                    [C.c_size_t, _VP]),
+    # training loss and batch metrics (additive to ABI 16)
+    "gnnrag_kl_loss_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "gnnrag_kl_loss_train": (C.c_int, [_VP] * 3 + [C.c_int32] * 2 + [_VP] * 3 + [C.c_size_t, _VP]),
+    "gnnrag_kl_loss_backward": (C.c_int, [_VP] * 5 + [C.c_int32] * 2 + [_VP] * 2),
+    "gnnrag_train_metrics": (C.c_int, [_VP] * 4 + [C.c_int64, C.c_double] + [C.c_int32] * 2 + [_VP] * 5),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

@@ -10,7 +10,8 @@ encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnr
 features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``), instruction generation on
 :class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``), the instruction update between
 two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``), the tail of the
-reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``)."""
+reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``), the KL loss behind
+the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -303,3 +304,25 @@ class LayerTailFn(torch.autograd.Function):
         return (g_pre if nig[0] else None, g_pre if (ctx.has_b and nig[1]) else None, None, None,
                 None if g["dw"] is None else g["dw"].view(ctx.w_shape), None if g["db"] is None else g["db"].view(ctx.b_shape),
                 None)
+
+
+class KLLossFn(torch.autograd.Function):
+    """``loss`` = ``calc_loss_label`` with ``loss_type='kl'`` (rearev.py:156-160 over base_model.py:193-215) on
+    ``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``: pred, teacher [B,N], label_valid [B] or [B,1].  Returns the 0-dim
+    batch-mean loss; saves pred, teacher, label_valid and the reserve (the answer counts).  Only pred receives a gradient:
+    the module keeps a teacher that asks for one on torch.  The upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, teacher, label_valid):
+        pred, teacher, label_valid = pred.detach(), teacher.detach(), label_valid.detach().reshape(-1)
+        loss, reserve = ops.kl_loss_train(pred, teacher, label_valid)
+        ctx.save_for_backward(pred, teacher, label_valid, reserve)
+        return loss.view(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        pred, teacher, label_valid, reserve = ctx.saved_tensors
+        return ops.kl_loss_backward(g_loss.float().reshape(1), pred, teacher, label_valid, reserve), None, None

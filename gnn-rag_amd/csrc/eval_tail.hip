@@ -13,10 +13,11 @@
 //
 // Integer / ordering work: results are bit-exact against the restatement in oracle/eval_tail.py.
 #include "gnnrag_common.h"
+#include "topp_keys.h"
 
 namespace gnnrag {
 
-// key = (~bits(p)) << 32 | slot : ascending key order = p descending (p >= 0), slot ascending
+// keys and sorting network: topp_keys.h (shared with the training-time metric of train_tail.hip)
 template <int LOG2>
 __global__ __launch_bounds__(1024) void k_topp_candidates(const float* __restrict__ prob,
                                                           const uint8_t* __restrict__ eligible, int N,
@@ -29,31 +30,10 @@ __global__ __launch_bounds__(1024) void k_topp_candidates(const float* __restric
   const float* p = prob + (size_t)b * N;
   const uint8_t* el = eligible + (size_t)b * N;
   for (int j = threadIdx.x; j < M; j += 1024) {
-    unsigned long long k = ~0ull;
-    if (j < N) {
-      const float v = p[j];
-      if (el[j] && !((double)v < ignore_prob))                               // evaluate.py:198-205
-        k = ((unsigned long long)(~__float_as_uint(v)) << 32) | (unsigned)j;
-    }
-    keys[j] = k;
+    keys[j] = j < N ? topp_key(p[j], el[j] != 0, ignore_prob, j) : kToppNone;          // evaluate.py:198-205
   }
   __syncthreads();
-  // bitonic sort, ascending
-  for (int size = 2; size <= M; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < M / 2; t += 1024) {
-        const int lo = ((t / stride) * stride * 2) + (t % stride);
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const unsigned long long a = keys[lo], c = keys[hi];
-        if ((a > c) == up) {
-          keys[lo] = c;
-          keys[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  topp_bitonic_sort(keys, M);
   int32_t* os = out_slot + (size_t)b * N;
   for (int j = threadIdx.x; j < N; j += 1024) {
     const unsigned long long k = keys[j];
@@ -68,7 +48,7 @@ __global__ __launch_bounds__(1024) void k_topp_candidates(const float* __restric
       if (k == ~0ull) break;
       ++kept;
       if (open) {
-        tp += (double)__uint_as_float(~(unsigned)(k >> 32));                 // evaluate.py:46
+        tp += (double)topp_key_prob(k);                                       // evaluate.py:46
         ++cut;
         if (tp > eps) open = false;                                           // evaluate.py:49-50
       }
@@ -100,11 +80,7 @@ __global__ __launch_bounds__(1024) void k_topp_candidates_big(const float* __res
   __syncthreads();
   for (int c0 = 0; c0 < N; c0 += 1024) {                  // ordered compaction of the kept slots
     const int j = c0 + tid;
-    unsigned long long k = ~0ull;
-    if (j < N) {
-      const float v = p[j];
-      if (el[j] && !((double)v < ignore_prob)) k = ((unsigned long long)(~__float_as_uint(v)) << 32) | (unsigned)j;
-    }
+    const unsigned long long k = j < N ? topp_key(p[j], el[j] != 0, ignore_prob, j) : kToppNone;
     const bool on = k != ~0ull;
     const unsigned long long m = __ballot(on);
     if (lane == 0) s_wsum[wave] = __popcll(m);
@@ -131,28 +107,14 @@ __global__ __launch_bounds__(1024) void k_topp_candidates_big(const float* __res
     for (int j = K + tid; j < M; j += 1024) gk[j] = ~0ull;
   }
   __syncthreads();
-  for (int size = 2; size <= M; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < M / 2; t += 1024) {
-        const int lo = ((t / stride) * stride * 2) + (t % stride);
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const unsigned long long x = a[lo], y = a[hi];
-        if ((x > y) == up) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  topp_bitonic_sort(a, M);
   int32_t* os = out_slot + (size_t)b * N;
   for (int j = tid; j < N; j += 1024) os[j] = j < K ? (int32_t)(a[j] & 0xffffffffu) : -1;
   if (tid == 0) {
     int cut = 0;
     double tp = 0.0;
     for (int j = 0; j < K; ++j) {
-      tp += (double)__uint_as_float(~(unsigned)(a[j] >> 32));                 // evaluate.py:46
+      tp += (double)topp_key_prob(a[j]);                                      // evaluate.py:46
       ++cut;
       if (tp > eps) break;                                                    // evaluate.py:49-50
     }

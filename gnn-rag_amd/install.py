@@ -177,6 +177,7 @@ def swap(model, args: dict):
             model.type_layer = tl
         patch_instruction(model)
         patch_rel_feature(model)
+        patch_loss_metrics(model)
         return model
     # old.num_relation is overwritten by init_reason (reasongnn.py:55); the constructor value,
     # which sizes pos_emb, is kept by BaseModel (base_model.py:21)
@@ -210,6 +211,7 @@ def swap(model, args: dict):
         cache_rel_features(model)
     swap_lstm(model)
     patch_instruction(model)
+    patch_loss_metrics(model)
     return model
 
 
@@ -228,6 +230,14 @@ def patch_rel_feature(model):
     ``AttnEncoder`` over the relation vocabulary's LM states in one fused call, forward and backward
     (modules/rel_text.py; ``GNNRAG_HIP_REL_TEXT=0`` - the default - leaves the reference's own method in charge)."""
     from .modules.rel_text import patch_rel_feature as _patch
+    return _patch(model)
+
+
+def patch_loss_metrics(model):
+    """``model.calc_loss_label`` and ``model.get_eval_metric`` (rearev.py:227-243, nsm.py:242-250): the KL loss with its
+    backward and the training step's H@1 / F1 on the library (modules/train_tail.py; ``GNNRAG_HIP_LOSS_METRICS=0`` - the
+    default - leaves the reference's own methods in charge)."""
+    from .modules.train_tail import patch_loss_metrics as _patch
     return _patch(model)
 
 

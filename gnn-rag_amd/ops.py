@@ -1368,6 +1368,82 @@ def layer_tail_backward(h, dist, keep, scale, w, g_h, g_dist, need_dw: bool = Tr
     return out
 
 
+TRAIN_METRICS_MAX_N = 16384                     # GNNRAG_TRAIN_METRICS_MAX_N (include/gnnrag.h)
+
+
+def train_metrics_supported(B: int, N: int) -> bool:
+    """Whether ``gnnrag_train_metrics`` takes the shape (a question's sort keys live in LDS)."""
+    return B > 0 and 0 < N <= TRAIN_METRICS_MAX_N
+
+
+def _kl_args(pred, teacher, label_valid, who: str):
+    pred = _chk(pred, "pred")
+    if pred.dim() != 2:
+        raise ValueError(who + ": pred must be [B,N]")
+    B, N = pred.shape
+    teacher = _chk(teacher, "teacher", shape=(B, N))
+    label_valid = _chk(label_valid.reshape(-1), "label_valid", shape=(B,))
+    return pred, teacher, label_valid, B, N
+
+
+def kl_loss_train(pred, teacher, label_valid):
+    """``calc_loss_label`` with ``loss_type='kl'`` (rearev.py:156-160 over base_model.py:193-215; ``gnnrag_kl_loss_train``):
+    pred, teacher [B,N], label_valid [B] or [B,1].  Returns (loss [1], reserve [B]): the batch-mean KL loss and the answer
+    counts ``len_b`` the backward reads.  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    pred, teacher, label_valid, B, N = _kl_args(pred, teacher, label_valid, "kl_loss_train")
+    dev, role = pred.device, "kl_loss_train: "
+    loss = _buf((1,), torch.float32, dev, role + "loss")
+    reserve = _buf((B,), torch.float32, dev, role + "reserve")
+    with torch.cuda.device(dev):
+        ws = _buf(max(lib.gnnrag_kl_loss_workspace_bytes(B), 16), torch.uint8, dev, role + "workspace")
+        _lib.check(lib.gnnrag_kl_loss_train(pred.data_ptr(), teacher.data_ptr(), label_valid.data_ptr(), B, N,
+                                            loss.data_ptr(), reserve.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "gnnrag_kl_loss_train")
+    return loss, reserve
+
+
+def kl_loss_backward(g_loss, pred, teacher, label_valid, reserve):
+    """Backward of :func:`kl_loss_train` (``gnnrag_kl_loss_backward``): g_loss a device tensor of one element (it is never
+    read on the host), reserve as the forward returned it.  Returns d_pred [B,N], every element written; exactly 0 where
+    teacher == 0 or label_valid == 0.  teacher receives no gradient."""
+    lib = _lib.load()
+    pred, teacher, label_valid, B, N = _kl_args(pred, teacher, label_valid, "kl_loss_backward")
+    g_loss = _chk(g_loss.reshape(-1), "g_loss", shape=(1,))
+    reserve = _chk(reserve, "reserve", shape=(B,))
+    d_pred = _buf((B, N), torch.float32, pred.device, "kl_loss_backward: d_pred")
+    with torch.cuda.device(pred.device):
+        _lib.check(lib.gnnrag_kl_loss_backward(g_loss.data_ptr(), pred.data_ptr(), teacher.data_ptr(),
+                                               label_valid.data_ptr(), reserve.data_ptr(), B, N, d_pred.data_ptr(),
+                                               _stream()), "gnnrag_kl_loss_backward")
+    return d_pred
+
+
+def train_metrics(pred, answer, seed, local_entity, pad_id: int, eps: float):
+    """``get_eval_metric`` of a training step (base_model.py:217-298) in one launch (``gnnrag_train_metrics``): pred, answer,
+    seed [B,N] float, local_entity [B,N] int64, pad_id the pad entity, eps the model's top-p bound.  Returns
+    (out_pred int32 [B], h1 float [B], f1 float [B], counts int32 [B,4] = (kept, n_ret, correct, n_ans)); nothing is read on
+    the host.  N beyond the library's limit raises ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    pred = _chk(pred, "pred")
+    if pred.dim() != 2:
+        raise ValueError("train_metrics: pred must be [B,N]")
+    B, N = pred.shape
+    answer = _chk(answer, "answer", shape=(B, N))
+    seed = _chk(seed, "seed", shape=(B, N))
+    local_entity = _chk(local_entity, "local_entity", dtype=torch.int64, shape=(B, N))
+    dev, role = pred.device, "train_metrics: "
+    out_pred = _buf((B,), torch.int32, dev, role + "pred")
+    h1 = _buf((B,), torch.float32, dev, role + "h1")
+    f1 = _buf((B,), torch.float32, dev, role + "f1")
+    cnt = _buf((B, 4), torch.int32, dev, role + "counts")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_train_metrics(pred.data_ptr(), answer.data_ptr(), seed.data_ptr(), local_entity.data_ptr(),
+                                            int(pad_id), float(eps), B, N, out_pred.data_ptr(), h1.data_ptr(), f1.data_ptr(),
+                                            cnt.data_ptr(), _stream()), "gnnrag_train_metrics")
+    return out_pred, h1, f1, cnt
+
+
 MAX_INS = 8                                     # GNNRAG_MAX_INS (include/gnnrag.h)
 
 

@@ -618,6 +618,52 @@ int gnnrag_layer_tail_backward(const float* h, const float* dist, const uint8_t*
                                float* dw_score, float* db_score, void* workspace, size_t workspace_bytes,
                                gnnrag_stream_t stream);
 
+/* ---- Training loss and batch metrics (additive to ABI 16; train_tail.hip) -------------------------------------------------
+ * What follows the last dist of a training forward (gnn/models/ReaRev/rearev.py:227-243, gnn/models/NSM/nsm.py:242-250).
+ *
+ * gnnrag_kl_loss_train: calc_loss_label with loss_type 'kl' (base_model.py:193-215).  pred, teacher [B, N] contiguous,
+ * label_valid [B].  Per question b, in fp32:
+ *   len_b = sum_n teacher (0 is replaced by 1)         t = teacher / len_b
+ *   l_b   = label_valid_b sum_n (t > 0 ? t (log t - log(pred + 1e-8)) : 0)           KLDivLoss(reduction='none') summed
+ *   loss  = (sum_b l_b) / B
+ * One workgroup per question (thread-strided sums, a fixed xor tree, the waves in order), then one launch that adds the l_b
+ * in ascending b.  len_b goes to the caller-owned reserve [B] (the backward reads it); the l_b pass through the workspace,
+ * gnnrag_kl_loss_workspace_bytes(B) bytes (a smaller one is GNNRAG_E_WORKSPACE before anything is launched).  No atomics,
+ * no allocation, nothing waits for the stream; a second call gives the same bits and l_b does not depend on the batch
+ * around question b.  A NULL pointer, B <= 0 or N <= 0 is GNNRAG_E_BADARG before a device is touched. */
+size_t gnnrag_kl_loss_workspace_bytes(int32_t B);
+int gnnrag_kl_loss_train(const float* pred, const float* teacher, const float* label_valid, int32_t B, int32_t N,
+                         float* loss, float* reserve, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+
+/* Backward of gnnrag_kl_loss_train: g_loss [1] ON THE DEVICE (never read on the host), reserve as the forward wrote it.
+ *   d_pred[b, n] = -g label_valid_b t / (pred + 1e-8) / B       exactly 0 where teacher == 0 or label_valid_b == 0
+ * One streaming pass that writes EVERY element of d_pred [B, N] (no memset, nothing accumulated into what it held): float4
+ * accesses where N % 4 == 0 and pred, teacher and d_pred are 16-byte aligned, element accesses with the same ownership and
+ * the same bits otherwise.  teacher receives no gradient. */
+int gnnrag_kl_loss_backward(const float* g_loss, const float* pred, const float* teacher, const float* label_valid,
+                            const float* reserve, int32_t B, int32_t N, float* d_pred, gnnrag_stream_t stream);
+
+/* get_eval_metric of a training step (base_model.py:217-298: calc_h1, calc_f1_new, f1_and_hits) in one launch, one
+ * workgroup per question.  pred, answer, seed [B, N] float, local_entity [B, N] int64, all contiguous.
+ *   out_pred [B]    argmax of pred over all N slots (seeds and pads included), the lowest slot among equal maxima
+ *   out_h1 [B]      answer[argmax] > 1e-10 as 0 / 1
+ *   eligible        !(seed > 0) and local_entity != pad_id
+ *   n_ans           eligible slots with answer > 0 (counted before the probability filter)
+ *   kept            eligible and !((double)pred < ignore_prob), ignore_prob = (1 - eps) / N formed on the host in double;
+ *                   ordered by probability descending, ties in ascending slot order
+ *   n_ret           the shortest prefix whose sequential fp64 running sum exceeds eps, else everything kept
+ *   correct         retrieved slots with answer > 0 (the slot's own flag: equal to the reference's membership test by
+ *                   entity id whenever a question's non-pad ids are distinct)
+ *   out_f1 [B]      n_ans == 0: (n_ret == 0 ? 1 : 0); n_ret == 0: 0; else p = correct / n_ret, r = correct / n_ans,
+ *                   (p != 0 && r != 0) ? 2.0 / (1.0 / p + 1.0 / r) : 0 in double; rounded to fp32 once; 0 where h1 == 0
+ *   out_cnt [B, 4]  (kept, n_ret, correct, n_ans)
+ * N <= GNNRAG_TRAIN_METRICS_MAX_N (the keys of a question live in LDS), else GNNRAG_E_UNSUPPORTED; a NULL pointer, B <= 0
+ * or N <= 0 is GNNRAG_E_BADARG.  Both are answered before anything is launched. */
+#define GNNRAG_TRAIN_METRICS_MAX_N 16384
+int gnnrag_train_metrics(const float* pred, const float* answer, const float* seed, const int64_t* local_entity,
+                         int64_t pad_id, double eps, int32_t B, int32_t N, int32_t* out_pred, float* out_h1, float* out_f1,
+                         int32_t* out_cnt, gnnrag_stream_t stream);
+
 /* The question encoder's LSTM (the instruction path): one layer, one direction, batch_first,
  * torch.nn.LSTM semantics and parameter layout (gate order i, f, g, o) - what
  * gnn/modules/question_encoding/lstm_encoder.py:27-36 builds and calls as

@@ -106,8 +106,21 @@ def main():
             lt_calls.append(1)
             return _lt_train(*args, **kw)
         ops.layer_tail_train = _lt_counted
+        # the KL loss and the step's H@1 / F1; act only with GNNRAG_HIP_LOSS_METRICS=1
+        install.patch_loss_metrics(tr.model)
+        _kl_train, _metrics = ops.kl_loss_train, ops.train_metrics
+
+        def _kl_counted(*args, **kw):
+            lm_calls["kl_loss_train"] += 1
+            return _kl_train(*args, **kw)
+
+        def _metrics_counted(*args, **kw):
+            lm_calls["train_metrics"] += 1
+            return _metrics(*args, **kw)
+        ops.kl_loss_train, ops.train_metrics = _kl_counted, _metrics_counted
     qr_calls = []                # reforms per ops.query_reform_train call (none with the switch off)
     lt_calls = []                # ops.layer_tail_train calls (none without GNNRAG_HIP_LAYER_TAIL_TRAIN=1)
+    lm_calls = {"kl_loss_train": 0, "train_metrics": 0}     # none without GNNRAG_HIP_LOSS_METRICS=1
     sync = (lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
     tr.model.train()
@@ -152,7 +165,11 @@ def main():
            "query_reform_train_calls_per_step": len(qr_calls) / float(a.warm + a.steps),
            "reforms_per_query_reform_train_call": sorted(set(qr_calls)),
            "hip_layer_tail_train": None if a.pure else os.environ.get("GNNRAG_HIP_LAYER_TAIL_TRAIN", "default"),
-           "layer_tail_train_calls_per_step": len(lt_calls) / float(a.warm + a.steps)}
+           "layer_tail_train_calls_per_step": len(lt_calls) / float(a.warm + a.steps),
+           "hip_loss_metrics": None if a.pure else os.environ.get("GNNRAG_HIP_LOSS_METRICS", "default"),
+           "kl_loss_train_calls_per_step": lm_calls["kl_loss_train"] / float(a.warm + a.steps),
+           "train_metrics_calls_per_step": lm_calls["train_metrics"] / float(a.warm + a.steps),
+           "h1_f1_last_step": [float(np.mean(x)) for x in tp_list] if tp_list else None}
     import shutil
     shutil.rmtree(ck, ignore_errors=True)
     print("GNNRAG_TRAIN " + json.dumps(out))
