@@ -60,6 +60,12 @@ class LayerParams(C.Structure):
                 ("W_e2e", C.c_void_p), ("b_e2e", C.c_void_p)]
 
 
+class BertLayer(C.Structure):
+    """Mirror of ``struct gnnrag_bert_layer`` (include/gnnrag.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("W_qkv", "b_qkv", "W_o", "b_o", "ln1_g", "ln1_b", "W_i", "b_i", "W_f", "b_f",
+                                          "ln2_g", "ln2_b")]
+
+
 # name -> (restype, argtypes); every symbol include/gnnrag.h declares
 _VP = C.c_void_p
 SIGNATURES = {
@@ -171,6 +177,11 @@ SIGNATURES = {
     "gnnrag_kl_loss_train": (C.c_int, [_VP] * 3 + [C.c_int32] * 2 + [_VP] * 3 + [C.c_size_t, _VP]),
     "gnnrag_kl_loss_backward": (C.c_int, [_VP] * 5 + [C.c_int32] * 2 + [_VP] * 2),
     "gnnrag_train_metrics": (C.c_int, [_VP] * 4 + [C.c_int64, C.c_double] + [C.c_int32] * 2 + [_VP] * 5),
+    # frozen BERT-class question encoder, inference (additive to ABI 16)
+    "gnnrag_bert_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_bert_attention": (C.c_int, [_VP] + [C.c_int32] * 4 + [_VP, _VP]),
+    "gnnrag_bert_encode": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float, C.c_int32,
+                                     C.POINTER(BertLayer)] + [C.c_int32] * 5 + [_VP, _VP, C.c_size_t, C.c_int32, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

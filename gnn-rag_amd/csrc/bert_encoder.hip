@@ -1,0 +1,320 @@
+// Inference forward of a frozen BERT-class question encoder: what the reference's
+// BERTInstruction.encode_question gets from `self.node_encoder(query_text)[0]` (gnn/modules/question_encoding/
+// bert_encoder.py:94) - transformers' BertModel on input ids alone: absolute positions, token type 0, NO attention mask
+// (pad tokens are attended like any other token), erf GELU, post-LayerNorm residual blocks; the pooler is never read.
+//
+//   x   = LN(word_emb[id] + pos_emb[t] + type_emb[0])                                   k_bert_embed_ln
+//   per layer:
+//     qkv = x W_qkv^T + b_qkv                    [B T, 3 H]   gnnrag_linear (packed weight)
+//     ctx = softmax(q k^T / sqrt(dh)) v          per head     k_bert_attention
+//     x   = LN(ctx W_o^T + b_o + x)                           gnnrag_linear (add = x), k_bert_add_ln
+//     f   = gelu(x W_i^T + b_i)                  [B T, I]     gnnrag_linear, k_bert_gelu
+//     x   = LN(f W_f^T + b_f + x)                             gnnrag_linear (add = x), k_bert_add_ln
+//
+// Eight launches per layer.  fp32 throughout, no atomics, every reduction in an order the shape alone fixes (a wave's
+// __shfl_xor tree, keys in ascending order), nothing allocated, nothing waits for the stream: safe under capture, a second
+// call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
+// attention: a workgroup per (question, head); the dense products: a row of C depends on its row of A only).
+#include "gnnrag_common.h"
+
+#ifndef GNNRAG_BERT_ATT_THREADS
+#define GNNRAG_BERT_ATT_THREADS 512  // 64 .. 1024, a multiple of 64; never changes a result
+#endif
+
+namespace gnnrag {
+
+constexpr int kBertMaxT = 128;       // keys per question: two per lane
+constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
+
+__device__ __forceinline__ float bert_wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float bert_wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// LayerNorm of one row by one wave: biased variance, two passes (mean, then sum (x - mean)^2); `load(i)` returns the
+// i-th float4 of the row (called three times per element: the row is L2 / L1 resident).  dst may be the row `load` reads:
+// a lane writes only the elements it has read itself, after both reductions.
+template <typename Load>
+__device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__ g, const float* __restrict__ bt,
+                                            float eps, int H4, int lane, float* dst) {
+  const float inv_h = 1.f / (float)(H4 * 4);
+  float s = 0.f;
+  for (int i = lane; i < H4; i += 64) {
+    const f32x4 v = load(i);
+    s += (v[0] + v[1]) + (v[2] + v[3]);
+  }
+  const float mean = bert_wave_sum(s) * inv_h;
+  float q = 0.f;
+  for (int i = lane; i < H4; i += 64) {
+    const f32x4 v = load(i);
+    const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
+    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+  }
+  const float rstd = 1.f / sqrtf(bert_wave_sum(q) * inv_h + eps);
+  for (int i = lane; i < H4; i += 64) {
+    const f32x4 v = load(i);
+    const f32x4 gg = ((const f32x4*)g)[i], bb = ((const f32x4*)bt)[i];
+    f32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * rstd * gg[e] + bb[e];
+    ((f32x4*)dst)[i] = o;
+  }
+}
+
+// x[row] = LN(word_emb[id] + pos_emb[row % T] + type_emb[0]); an id outside [0, vocab) reads nothing: its row is NaN
+__global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_t* __restrict__ ids,
+                                                                    const float* __restrict__ word_emb, int vocab,
+                                                                    const float* __restrict__ pos_emb,
+                                                                    const float* __restrict__ type_emb,
+                                                                    const float* __restrict__ g,
+                                                                    const float* __restrict__ bt, float eps, int M, int T,
+                                                                    int H4, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
+  if (row >= M) return;
+  float* dst = out + (size_t)row * H4 * 4;
+  const int64_t id = ids[row];
+  if (id < 0 || id >= (int64_t)vocab) {
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int i = lane; i < H4; i += 64) ((f32x4*)dst)[i] = (f32x4){nan, nan, nan, nan};
+    return;
+  }
+  const f32x4* w = (const f32x4*)(word_emb + (size_t)id * H4 * 4);
+  const f32x4* p = (const f32x4*)(pos_emb + (size_t)(row % T) * H4 * 4);
+  const f32x4* ty = (const f32x4*)type_emb;
+  bert_ln_row([&](int i) { return (w[i] + ty[i]) + p[i]; }, g, bt, eps, H4, lane, dst);
+}
+
+// out[row] = LN(in[row]); in already holds dense(x) + bias + residual.  out == in is allowed (no __restrict__ on the two).
+__global__ __launch_bounds__(64 * kBertLnRows) void k_bert_add_ln(const float* in, const float* __restrict__ g,
+                                                                  const float* __restrict__ bt, float eps, int M, int H4,
+                                                                  float* out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const f32x4* src = (const f32x4*)(in + (size_t)row * H4 * 4);
+  bert_ln_row([&](int i) { return src[i]; }, g, bt, eps, H4, lane, out + (size_t)row * H4 * 4);
+}
+
+__device__ __forceinline__ float bert_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
+
+// x = 0.5 x (1 + erf(x / sqrt 2)) in place over n floats (16-byte aligned); the last n % 4 by the first lanes
+__global__ __launch_bounds__(256) void k_bert_gelu(float* __restrict__ x, size_t n) {
+  const size_t n4 = n / 4, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = tid; i < n4; i += stride) {
+    f32x4 v = ((f32x4*)x)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = bert_gelu(v[e]);
+    ((f32x4*)x)[i] = v;
+  }
+  if (tid < n - n4 * 4) x[n4 * 4 + tid] = bert_gelu(x[n4 * 4 + tid]);
+}
+
+// One workgroup per (question, head).  LDS: the head's K and V slices [T, DH] with a row stride of DH + 1 floats (odd: the
+// 32 lanes of a ds_read_b32 group that read k[lane][d] fall on 32 different banks), then per wave the query row [DH] and
+// its T probabilities.  A wave owns a query row: lanes are keys (lane and lane + 64), the maximum and the sum of the row
+// come from the fixed wave tree, then lanes run over d and add p[j] v[j][d] for j = 0 .. T - 1 in order.  No mask.
+template <int DH>
+__global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict__ qkv, int T, int heads,
+                                                         float* __restrict__ ctx) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int LD = DH + 1;
+  const int b = blockIdx.x / heads, h = blockIdx.x % heads;
+  const int H = heads * DH;
+  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
+  float* ks = smem;                                   // [T, LD]
+  float* vs = ks + T * LD;                            // [T, LD]
+  float* qs = vs + T * LD + wave * (DH + kBertMaxT);  // [DH]   this wave's query row
+  float* ps = qs + DH;                                // [kBertMaxT]  its probabilities
+
+  const float* base = qkv + (size_t)b * T * 3 * H + h * DH;
+  for (int i = tid; i < T * (DH / 4); i += nthr) {
+    const int j = i / (DH / 4), c = (i % (DH / 4)) * 4;
+    const float* row = base + (size_t)j * 3 * H;
+    const f32x4 kv = *(const f32x4*)(row + H + c);
+    const f32x4 vv = *(const f32x4*)(row + 2 * H + c);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      ks[j * LD + c + e] = kv[e];
+      vs[j * LD + c + e] = vv[e];
+    }
+  }
+  __syncthreads();
+
+  const float scale = 1.f / sqrtf((float)DH);
+  const int j0 = lane, j1 = lane + 64;
+  for (int t = wave; t < T; t += nw) {
+    if (lane < DH) qs[lane] = base[(size_t)t * 3 * H + lane];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    float s0 = -INFINITY, s1 = -INFINITY;
+    if (j0 < T) {
+      const float* k = ks + j0 * LD;
+      float a = 0.f;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) a += qs[d] * k[d];
+      s0 = a * scale;
+    }
+    if (j1 < T) {
+      const float* k = ks + j1 * LD;
+      float a = 0.f;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) a += qs[d] * k[d];
+      s1 = a * scale;
+    }
+    const float m = bert_wave_max(fmaxf(s0, s1));
+    const float e0 = j0 < T ? expf(s0 - m) : 0.f, e1 = j1 < T ? expf(s1 - m) : 0.f;
+    const float sum = bert_wave_sum(e0 + e1);
+    if (j0 < T) ps[j0] = e0 / sum;
+    if (j1 < T) ps[j1] = e1 / sum;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < DH) {
+      float acc = 0.f;
+      for (int j = 0; j < T; ++j) acc += ps[j] * vs[j * LD + lane];
+      ctx[((size_t)b * T + t) * H + h * DH + lane] = acc;
+    }
+    // the next row's writes to qs / ps follow this row's reads in program order (one wave, LDS in order)
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+static inline size_t bert_att_lds_bytes(int T, int dh, int threads) {
+  return ((size_t)2 * T * (dh + 1) + (size_t)(threads / 64) * (dh + kBertMaxT)) * sizeof(float);
+}
+
+static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static int bert_attention_launch(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
+                                 hipStream_t stream) {
+  const int threads = GNNRAG_BERT_ATT_THREADS;
+  const size_t lds = bert_att_lds_bytes(T, dh, threads);
+  const dim3 grid((unsigned)((int64_t)B * heads));
+  if (dh == 32) {
+    if (lds > 64 * 1024) {
+      static DeviceMask raised{0};
+      GNNRAG_RC(raise_lds_cap(k_bert_attention<32>, raised));
+    }
+    hipLaunchKernelGGL(k_bert_attention<32>, grid, dim3(threads), lds, stream, qkv, T, heads, ctx);
+  } else {
+    if (lds > 64 * 1024) {
+      static DeviceMask raised{0};
+      GNNRAG_RC(raise_lds_cap(k_bert_attention<64>, raised));
+    }
+    hipLaunchKernelGGL(k_bert_attention<64>, grid, dim3(threads), lds, stream, qkv, T, heads, ctx);
+  }
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+static inline bool bert_att_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {
+  return (dh == 32 || dh == 64) && T >= 1 && T <= kBertMaxT && heads >= 1 && B >= 1 && B * heads < ((int64_t)1 << 31);
+}
+
+// the workspace: qkv [M, 3H], ctx [M, H], sum [M, H] (dense + residual, the LayerNorm's input), ffn [M, I]; each block
+// starts on a 256-byte boundary
+struct BertWs {
+  size_t qkv, ctx, sum, ffn, total;
+};
+
+static inline BertWs bert_ws(int64_t M, int64_t H, int64_t I) {
+  BertWs w;
+  size_t o = 0;
+  w.qkv = o;
+  o += align_up((size_t)M * 3 * H * sizeof(float), 256);
+  w.ctx = o;
+  o += align_up((size_t)M * H * sizeof(float), 256);
+  w.sum = o;
+  o += align_up((size_t)M * H * sizeof(float), 256);
+  w.ffn = o;
+  o += align_up((size_t)M * I * sizeof(float), 256);
+  w.total = o;
+  return w;
+}
+
+}  // namespace gnnrag
+
+using namespace gnnrag;
+
+extern "C" size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I) {
+  if (B <= 0 || T <= 0 || H <= 0 || I <= 0) return 0;
+  return bert_ws((int64_t)B * T, H, I).total;
+}
+
+extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
+                                     gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
+  if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
+  if (!qkv || !ctx) return GNNRAG_E_BADARG;
+  if (!aligned16(qkv) || !aligned16(ctx)) return GNNRAG_E_UNSUPPORTED;
+  return bert_attention_launch(qkv, B, T, heads, dh, ctx, (hipStream_t)stream);
+}
+
+extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                  int32_t max_pos, const float* type_emb, const float* ln_g, const float* ln_b,
+                                  float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
+                                  int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
+                                  gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L < 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
+  if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
+  // the shape rules first: they are answered whatever the pointers are
+  if (H % heads != 0 || H % 4 != 0 || T > kBertMaxT || T > max_pos) return GNNRAG_E_UNSUPPORTED;
+  const int32_t dh = H / heads;
+  if (!bert_att_shape_ok(B, T, heads, dh) || (int64_t)B * T >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
+  const int64_t M = (int64_t)B * T;
+  const BertWs w = bert_ws(M, H, I);
+  if (L > 0 && ws_bytes < w.total) return GNNRAG_E_UNSUPPORTED;
+  if (!ids || !word_emb || !pos_emb || !type_emb || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
+    return GNNRAG_E_BADARG;
+  if (!aligned16(word_emb) || !aligned16(pos_emb) || !aligned16(type_emb) || !aligned16(ln_g) || !aligned16(ln_b) ||
+      !aligned16(out) || ((uintptr_t)ids & 7) || (L > 0 && !aligned16(ws)))
+    return GNNRAG_E_UNSUPPORTED;
+  for (int l = 0; l < L; ++l) {
+    const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
+                                layers[l].ln1_g, layers[l].ln1_b, layers[l].W_i,   layers[l].b_i,
+                                layers[l].W_f,   layers[l].b_f,   layers[l].ln2_g, layers[l].ln2_b};
+    for (int i = 0; i < 12; ++i)
+      if (!p[i]) return GNNRAG_E_BADARG;
+    for (int i = 0; i < 12; ++i)
+      if (!aligned16(p[i])) return GNNRAG_E_UNSUPPORTED;
+  }
+
+  hipStream_t st = (hipStream_t)stream;
+  const int H4 = H / 4;
+  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
+  hipLaunchKernelGGL(k_bert_embed_ln, ln_grid, ln_block, 0, st, ids, word_emb, vocab, pos_emb, type_emb, ln_g, ln_b,
+                     ln_eps, (int)M, T, H4, out);
+  GNNRAG_LAUNCH_CHECK();
+  if (L == 0) return 0;
+
+  float* qkv = (float*)((char*)ws + w.qkv);
+  float* ctx = (float*)((char*)ws + w.ctx);
+  float* sum = (float*)((char*)ws + w.sum);
+  float* ffn = (float*)((char*)ws + w.ffn);
+  const size_t n_ffn = (size_t)M * I;
+  const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
+  const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
+  for (int l = 0; l < L; ++l) {
+    const gnnrag_bert_layer& p = layers[l];
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
+    GNNRAG_RC(bert_attention_launch(qkv, B, T, heads, dh, ctx, st));
+    GNNRAG_RC(gnnrag_linear(ctx, M, H, p.W_o, p.b_o, out, M, 0, sum, H, math, stream));
+    hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, p.ln1_g, p.ln1_b, ln_eps, (int)M, H4, out);
+    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, ffn, I, math, stream));
+    hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, ffn, n_ffn);
+    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(gnnrag_linear(ffn, M, I, p.W_f, p.b_f, out, M, 0, sum, H, math, stream));
+    hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, p.ln2_g, p.ln2_b, ln_eps, (int)M, H4, out);
+    GNNRAG_LAUNCH_CHECK();
+  }
+  return 0;
+}

@@ -175,6 +175,7 @@ def swap(model, args: dict):
             tl.load_state_dict(tl_old.state_dict(), strict=True)
             tl.to(next(tl_old.parameters()).device)
             model.type_layer = tl
+        patch_lm_encoder(model)
         patch_instruction(model)
         patch_rel_feature(model)
         patch_loss_metrics(model)
@@ -210,8 +211,19 @@ def swap(model, args: dict):
         patch_rel_feature(model)            # underneath the cache: its one computation per parameter version
         cache_rel_features(model)
     swap_lstm(model)
+    patch_lm_encoder(model)
     patch_instruction(model)
     patch_loss_metrics(model)
+    return model
+
+
+def patch_lm_encoder(model):
+    """``model.instruction.node_encoder`` of a ``BERTInstruction`` (bert_encoder.py:78,94): the frozen BERT-class LM's
+    forward on the library (modules/question_encoding/lm_encoder.py; ``GNNRAG_HIP_LM=0`` leaves transformers' own forward
+    in charge, and so does every call the module's rules do not take)."""
+    if getattr(model, "instruction", None) is not None:
+        from .modules.question_encoding.lm_encoder import patch_lm_encoder as _patch
+        _patch(model.instruction)
     return model
 
 

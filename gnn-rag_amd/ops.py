@@ -1591,6 +1591,75 @@ def instructions_backward(hidden, node, W_q, W_cq, w_ca, ins, attn, reserve, g_i
     return out
 
 
+BERT_MAX_T = 128                                # keys of one question: two per lane (csrc/bert_encoder.hip)
+BERT_LAYER_FIELDS = tuple(n for n, _ in _lib.BertLayer._fields_)
+
+
+def bert_encode_supported(T: int, H: int, heads: int, I: int, max_pos: int) -> bool:
+    """Whether ``gnnrag_bert_encode`` takes the shape (the header's rules)."""
+    return (0 < T <= min(BERT_MAX_T, max_pos) and H > 0 and I > 0 and heads > 0 and H % heads == 0 and H % 4 == 0 and
+            H // heads in (32, 64))
+
+
+def bert_attention(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int) -> torch.Tensor:
+    """``gnnrag_bert_attention``: qkv [B*T, 3*heads*dh] (query, key, value blocks of a row in that order) ->
+    ctx [B*T, heads*dh] = softmax(q k^T / sqrt(dh)) v per (question, head), no mask."""
+    lib = _lib.load()
+    H = heads * dh
+    qkv = _chk(qkv, "qkv", shape=(B * T, 3 * H))
+    ctx = _buf((B * T, H), torch.float32, qkv.device, "bert_attention: ctx")
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.gnnrag_bert_attention(qkv.data_ptr(), B, T, heads, dh, ctx.data_ptr(), _stream()),
+                   "gnnrag_bert_attention")
+    return ctx
+
+
+def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int, I: Optional[int] = None,
+                math: Optional[int] = None) -> torch.Tensor:
+    """``gnnrag_bert_encode``: ids [B,T] int64 -> the last hidden state [B,T,H] of a BERT-class encoder (no mask, no
+    pooler).  ``layers``: a list of dicts with the keys ``BERT_LAYER_FIELDS`` (W_qkv [3H,H] the query / key / value weights
+    stacked, b_qkv [3H], W_o, b_o, ln1_g, ln1_b, W_i [I,H], b_i, W_f [H,I], b_f, ln2_g, ln2_b); an empty list returns the
+    embedding LayerNorm (``I`` then sizes nothing and defaults to 4 H).  A shape outside the library's set raises
+    ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    lib = _lib.load()
+    ids = _chk(ids, "ids", dtype=torch.int64)
+    if ids.dim() != 2:
+        raise ValueError("ids must be [B,T]")
+    B, T = ids.shape
+    word_emb = _chk(word_emb.detach(), "word_emb")
+    vocab, H = word_emb.shape
+    pos_emb = _chk(pos_emb.detach(), "pos_emb")
+    if pos_emb.dim() != 2 or pos_emb.shape[1] != H:
+        raise ValueError("pos_emb must be [max_pos,H]")
+    type_emb = _chk(type_emb.detach(), "type_emb")
+    if type_emb.dim() != 2 or type_emb.shape[1] != H or type_emb.shape[0] < 1:
+        raise ValueError("type_emb must be [>=1,H]")
+    ln_g, ln_b = _chk(ln_g.detach(), "ln_g", shape=(H,)), _chk(ln_b.detach(), "ln_b", shape=(H,))
+    L = len(layers)
+    if L:
+        I = int(layers[0]["W_i"].shape[0])
+    elif I is None:
+        I = 4 * H
+    shapes = {"W_qkv": (3 * H, H), "b_qkv": (3 * H,), "W_o": (H, H), "b_o": (H,), "ln1_g": (H,), "ln1_b": (H,),
+              "W_i": (I, H), "b_i": (I,), "W_f": (H, I), "b_f": (H,), "ln2_g": (H,), "ln2_b": (H,)}
+    keep, arr = [], (_lib.BertLayer * max(L, 1))()
+    for l, layer in enumerate(layers):
+        for name in BERT_LAYER_FIELDS:
+            t = _chk(layer[name].detach(), "layers[%d].%s" % (l, name), shape=shapes[name])
+            keep.append(t)
+            setattr(arr[l], name, t.data_ptr())
+    dev = ids.device
+    out = _buf((B, T, H), torch.float32, dev, "bert_encode: out")
+    nws = int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)) if L else 0
+    ws = _buf((max(nws, 1),), torch.uint8, dev, "bert_encode: workspace")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(), pos_emb.shape[0],
+                                          type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), float(eps), L, arr, B, T, H,
+                                          heads, I, out.data_ptr(), ws.data_ptr(), ws.numel(), _math(math), _stream()),
+                   "gnnrag_bert_encode")
+    return out
+
+
 REL_TEXT_MAX_T, REL_TEXT_MAX_K, REL_TEXT_MAX_D = 256, 4096, 4096     # GNNRAG_REL_TEXT_MAX_* (include/gnnrag.h)
 
 

@@ -781,6 +781,38 @@ int gnnrag_instructions_backward(const float* hidden, const float* node, const f
                                  float* db_cq, float* dw_ca, float* db_ca, int32_t B, int32_t T, int32_t D,
                                  int32_t n_steps, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
 
+/* ---- Frozen BERT-class question encoder, inference only (additive to ABI 16) --------------------
+ * What BERTInstruction.encode_question reads from `self.node_encoder(query_text)[0]` (gnn/modules/question_encoding/
+ * bert_encoder.py:94): transformers' BertModel on input ids alone - absolute positions 0 .. T-1, token type 0, NO
+ * attention mask (pad tokens are attended like any other token), erf GELU, post-LayerNorm blocks; no pooler.
+ *   x = LN(word_emb[id] + pos_emb[t] + type_emb[0]);  per layer:
+ *   qkv = x W_qkv^T + b_qkv;  ctx = softmax(q k^T / sqrt(dh)) v per head;  x = LN(ctx W_o^T + b_o + x);
+ *   x = LN(gelu(x W_i^T + b_i) W_f^T + b_f + x),  gelu(u) = 0.5 u (1 + erf(u / sqrt 2))
+ * LN: biased variance, two passes, ln_eps inside the root.  ids [B,T] int64; word_emb [vocab,H], pos_emb [max_pos,H],
+ * type_emb [>= 1,H] (row 0 is read), ln_g / ln_b [H]; out [B,T,H], fully written.  An id outside [0, vocab) reads no
+ * memory: its output row is NaN (through every layer; with L > 0 all rows of that question are NaN, no other question's).
+ * layers: HOST array of L structs of device pointers, read during the call (as gnnrag_layer_params is).  W_qkv
+ * [3H,H] / b_qkv [3H]: the query, key and value weights stacked in that order; W_o [H,H], W_i [I,H], W_f [H,I].  L = 0 is
+ * legal: out is the embedding LayerNorm, layers and ws are not read.
+ * The four dense products of a layer are gnnrag_linear calls (math: GNNRAG_MATH_*), a layer is 8 launches.  fp32
+ * throughout, no atomics, every reduction in an order the shape fixes, no allocation, nothing waits for the stream, safe
+ * under capture: a second call gives the same bits and a question's rows do not depend on B.
+ * GNNRAG_E_UNSUPPORTED before anything is launched (the shape rules are answered first, whatever the pointers are):
+ * H % heads != 0, H / heads not in {32, 64}, T > 128, T > max_pos, H % 4 != 0, ws_bytes below
+ * gnnrag_bert_workspace_bytes(B, T, H, I) (L > 0), a pointer that is not 16-byte aligned (ids: 8).  A NULL pointer or a
+ * size <= 0 is GNNRAG_E_BADARG.
+ * gnnrag_bert_attention is the attention step alone: qkv [B T, 3 heads dh] packed as above, ctx [B T, heads dh]. */
+typedef struct gnnrag_bert_layer { const float *W_qkv, *b_qkv, *W_o, *b_o, *ln1_g, *ln1_b,
+                                               *W_i, *b_i, *W_f, *b_f, *ln2_g, *ln2_b; } gnnrag_bert_layer;
+size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I);
+int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
+                          gnnrag_stream_t stream);
+int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb, int32_t max_pos,
+                       const float* type_emb, const float* ln_g, const float* ln_b, float ln_eps,
+                       int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads,
+                       int32_t I, float* out /* [B,T,H] */, void* ws, size_t ws_bytes, int32_t math,
+                       gnnrag_stream_t stream);
+
 /* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
  * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):
  * question_emb over the frozen LM token states of the relation vocabulary, then AttnEncoder

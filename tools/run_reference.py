@@ -159,6 +159,8 @@ def main():
 
     def _init_instruction(self, *a, **kw):
         _ev_init1(self, *a, **kw)
+        # --lm sbert / bert: the frozen BertModel's forward on the library (GNNRAG_HIP_LM, read at every call; =0 switches it off)
+        install.patch_lm_encoder(self.model)
         install.patch_instruction(self.model)
 
     evaluate.Evaluator.__init__ = _init_instruction

@@ -1,0 +1,212 @@
+#!/usr/bin/env python
+"""The frozen BERT-class question encoder with ``GNNRAG_HIP_LM`` off (transformers' own forward) and on
+(``patch_lm_encoder``: ``gnnrag_bert_encode``, 8 launches per layer), each setting in a process of its own, started fresh:
+
+    python tools/time_bert_encoder.py [--iters 20] [--warm 5] [--rounds 2] [--out profiles/bert_encoder_time.jsonl]
+    python tools/time_bert_encoder.py --kernel [--libs 256=,64=gnn-rag_amd/lib/exp_bertatt64.so,...]
+
+* the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
+  tests/bert_oracle.py - the real all-MiniLM-L6-v2 weights are not needed for a timing) in eval mode, ``enc(ids)[0]`` on a
+  NEW id tensor every iteration; (B, T) = (1, 12), (8, 20), (64, 20).  ``perf_counter`` around the call = host enqueue time
+  (the device is idle before, nothing waits inside), HIP events around it = stream time.  Median of ``--iters`` after
+  ``--warm``; ``--rounds`` repeats the off / on pair: the spread between two runs of one leg is the noise the rule for the
+  default is read against;
+* the per-kernel split of the HIP leg (switch on only): 20 calls captured into one graph and replayed - the whole encode,
+  the embedding LayerNorm alone (L = 0), one layer's attention and its four dense products alone; what remains per layer is
+  the two LayerNorms and the GELU;
+* a whole evaluation forward of a ``BERTInstruction`` ReaRev model is NOT measured here: the reference's ``--lm sbert``
+  loader tokenises its data with the hub's tokenizer, which cannot be built offline (recorded as unmeasured).
+
+``--kernel``: ``gnnrag_bert_attention`` alone, 20 calls per graph, per library given in ``--libs`` as ``label=path``
+(``GNNRAG_LIB``; empty path = the built library): how the workgroup size (``-DGNNRAG_BERT_ATT_THREADS``,
+``build.build_variant``) was chosen."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(1, 12), (8, 20), (64, 20)]
+L, VOCAB, MAX_POS = 6, 30522, 512
+TAG = "GNNRAG_BERT "
+CALLS = 20
+
+
+def _median(xs):
+    xs = sorted(xs)
+    n = len(xs)
+    return xs[n // 2] if n % 2 else 0.5 * (xs[n // 2 - 1] + xs[n // 2])
+
+
+def _measure(torch, fn, inputs, warm):
+    host, dev = [], []
+    for it, x in enumerate(inputs):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        t0 = time.perf_counter()
+        fn(x)
+        t1 = time.perf_counter()
+        e1.record()
+        e1.synchronize()
+        if it >= warm:
+            host.append((t1 - t0) * 1e3)
+            dev.append(e0.elapsed_time(e1))
+    return _median(host), _median(dev), min(host), min(dev)
+
+
+def _graph_us(torch, fn, a):
+    """Device time of one fn() call in microseconds: CALLS calls in one graph, replayed."""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(CALLS):
+            fn()
+    ms = []
+    for it in range(a.warm + a.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        e1.synchronize()
+        if it >= a.warm:
+            ms.append(e0.elapsed_time(e1) / CALLS)
+    return _median(ms) * 1e3
+
+
+def _setup():
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import torch
+    import gnnrag_amd  # noqa: F401
+    import bert_oracle as bo
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/time_bert_encoder.py needs a GPU")
+    return torch, bo, torch.device("cuda", 0)
+
+
+class _Holder:
+    def __init__(self, enc):
+        self.node_encoder = enc
+
+
+def child_encode(a):
+    torch, bo, dev = _setup()
+    import numpy as np
+    from gnnrag_amd import ops
+    from gnnrag_amd.modules.question_encoding.lm_encoder import enabled, patch_lm_encoder
+    m32, _ = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)
+    enc = m32.to(dev).eval()
+    for p in enc.parameters():
+        p.requires_grad_(False)
+    patch_lm_encoder(_Holder(enc))
+    patch = enc._gnnrag_lm_patch
+    for B, T in SHAPES:
+        ids0 = torch.from_numpy(np.random.RandomState(B).randint(0, VOCAB, (B, T))).long().to(dev)
+        ids = [ids0.clone() for _ in range(a.warm + a.iters)]
+        out = []
+
+        def encode(x):
+            with torch.no_grad():
+                out[:] = [enc(x)[0]]
+
+        before = patch.hip_calls
+        host, ev, host_min, ev_min = _measure(torch, encode, ids, a.warm)
+        rec = {"what": "encode", "switch": "on" if enabled() else "off", "B": B, "T": T, "L": L, "H": 384, "I": 1536,
+               "host_ms": host, "event_ms": ev, "host_ms_min": host_min, "event_ms_min": ev_min, "iters": a.iters,
+               "warm": a.warm, "hip_calls_per_encode": (patch.hip_calls - before) / len(ids),
+               "checksum": float(out[0].double().square().sum()), "device": torch.cuda.get_device_name(0)}
+        print(TAG + json.dumps(rec), flush=True)
+        if not enabled():
+            continue
+        # the split of the HIP leg
+        P = bo.layer_params(enc)
+        layers = patch.layers()
+        top = (P["word_emb"], P["pos_emb"], P["type_emb"], P["ln_g"], P["ln_b"], P["eps"])
+        full = _graph_us(torch, lambda: ops.bert_encode(ids0, *top, layers, 12, I=1536), a)
+        emb = _graph_us(torch, lambda: ops.bert_encode(ids0, *top, [], 12, I=1536), a)
+        lay, M = layers[0], B * T
+        x = torch.randn(M, 384, device=dev)
+        f = torch.randn(M, 1536, device=dev)
+        qkv = torch.randn(M, 1152, device=dev)
+        split = {"qkv": _graph_us(torch, lambda: ops.linear(x, lay["W_qkv"], lay["b_qkv"]), a),
+                 "attention": _graph_us(torch, lambda: ops.bert_attention(qkv, B, T, 12, 32), a),
+                 "out_proj": _graph_us(torch, lambda: ops.linear(x, lay["W_o"], lay["b_o"], add=x), a),
+                 "ffn_in": _graph_us(torch, lambda: ops.linear(x, lay["W_i"], lay["b_i"]), a),
+                 "ffn_out": _graph_us(torch, lambda: ops.linear(f, lay["W_f"], lay["b_f"], add=x), a)}
+        split["two_layernorms_and_gelu"] = (full - emb) / L - sum(split.values())
+        rec = {"what": "split", "B": B, "T": T, "L": L, "encode_us": full, "embed_ln_us": emb,
+               "per_layer_us": split, "calls_per_graph": CALLS, "iters": a.iters,
+               "device": torch.cuda.get_device_name(0)}
+        print(TAG + json.dumps(rec), flush=True)
+    print(TAG + json.dumps({"what": "forward", "unmeasured": "a BERTInstruction ReaRev forward needs the hub's tokenizer "
+                            "in the reference's data loader; it cannot be built offline"}), flush=True)
+
+
+def child_kernel(a):
+    torch, bo, dev = _setup()
+    from gnnrag_amd import ops
+    for B, T in SHAPES + [(64, 128)]:
+        for heads, dh in ((12, 32), (12, 64)):
+            qkv = torch.randn(B * T, 3 * heads * dh, device=dev)
+            out = []
+            us = _graph_us(torch, lambda: out.__setitem__(slice(None), [ops.bert_attention(qkv, B, T, heads, dh)]), a)
+            rec = {"what": "kernel", "threads": a.label, "B": B, "T": T, "heads": heads, "dh": dh, "us_per_call": us,
+                   "calls_per_graph": CALLS, "iters": a.iters, "checksum": float(out[0].double().sum()),
+                   "device": torch.cuda.get_device_name(0)}
+            print(TAG + json.dumps(rec), flush=True)
+
+
+def _spawn(argv, env_extra, lines, limit):
+    """A fresh child process under its own time limit (nothing replaces the program of a process that holds the GPU)."""
+    env = dict(os.environ)
+    env.update(env_extra)
+    r = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__)] + argv, env=env,
+                       capture_output=True, text=True)
+    got = [json.loads(l[len(TAG):]) for l in r.stdout.splitlines() if l.startswith(TAG)]
+    if r.returncode != 0:
+        raise SystemExit("child %s failed (%d):\n%s" % (argv, r.returncode, (r.stdout + r.stderr)[-3000:]))
+    for rec in got:
+        print(json.dumps(rec), flush=True)
+    lines.extend(got)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warm", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--libs", default="256=")
+    ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "bert_encoder_time.jsonl"))
+    ap.add_argument("--child", choices=["encode", "kernel"])
+    ap.add_argument("--label", default="")
+    a = ap.parse_args()
+    if a.child:
+        return {"encode": child_encode, "kernel": child_kernel}[a.child](a)
+    common = ["--iters", str(a.iters), "--warm", str(a.warm)]
+    lines = []
+    if a.kernel:
+        for spec in a.libs.split(","):
+            label, _, path = spec.partition("=")
+            env = {"GNNRAG_LIB": os.path.abspath(os.path.join(REPO, path))} if path else {}
+            _spawn(["--child", "kernel", "--label", label] + common, env, lines, a.limit)
+    else:
+        for rnd in range(a.rounds):
+            for switch in ("0", "1"):
+                before = len(lines)
+                _spawn(["--child", "encode"] + common, {"GNNRAG_HIP_LM": switch}, lines, a.limit)
+                for rec in lines[before:]:
+                    rec["round"] = rnd
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "a") as f:
+        for rec in lines:
+            f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()
