@@ -182,6 +182,11 @@ SIGNATURES = {
     "gnnrag_bert_attention": (C.c_int, [_VP] + [C.c_int32] * 4 + [_VP, _VP]),
     "gnnrag_bert_encode": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float, C.c_int32,
                                      C.POINTER(BertLayer)] + [C.c_int32] * 5 + [_VP, _VP, C.c_size_t, C.c_int32, _VP]),
+    # the same with RoBERTa / MPNet positions, no token-type term and MPNet's relative attention bias
+    "gnnrag_bert_attention_bias": (C.c_int, [_VP] + [C.c_int32] * 4 + [_VP, _VP, _VP]),
+    "gnnrag_bert_encode_ex": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
+                                        C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
+                              [_VP, _VP, C.c_size_t, C.c_int32, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

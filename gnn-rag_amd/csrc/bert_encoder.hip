@@ -11,6 +11,13 @@
 //     f   = gelu(x W_i^T + b_i)                  [B T, I]     gnnrag_linear, k_bert_gelu
 //     x   = LN(f W_f^T + b_f + x)                             gnnrag_linear (add = x), k_bert_add_ln
 //
+// RobertaModel and MPNetModel (--lm roberta / relbert / sbert2) are the same block with two differences, both taken by
+// gnnrag_bert_encode_ex:
+//   * positions from the ids (pad_id >= 0): pos = pad_id + #{t' <= t : id[t'] != pad_id} for a non-pad token, pad_id for a
+//     pad (transformers' create_position_ids_from_input_ids); MPNet has no token-type term (type_emb NULL);
+//   * MPNet adds a relative-position bias to the scaled scores of every layer: s(i, j) += rel_bias[head][j - i + T - 1],
+//     one table [heads, 2T-1] for all layers (k_bert_attention<DH, true>).
+//
 // Eight launches per layer.  fp32 throughout, no atomics, every reduction in an order the shape alone fixes (a wave's
 // __shfl_xor tree, keys in ascending order), nothing allocated, nothing waits for the stream: safe under capture, a second
 // call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
@@ -68,11 +75,17 @@ __device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__
   }
 }
 
-// x[row] = LN(word_emb[id] + pos_emb[row % T] + type_emb[0]); an id outside [0, vocab) reads nothing: its row is NaN
+// x[row] = LN(word_emb[id] + pos_emb[pos] + type_emb[0]); an id outside [0, vocab) reads nothing: its row is NaN.
+// IDPOS = false: pos = row % T.  IDPOS = true (pad_id >= 0): the wave counts the non-pad ids among ids[b, 0 .. t] itself
+// (two ids per lane, T <= 128, a ballot and a popcount; it reads its own question's ids only) and pos = pad_id + count for
+// a non-pad token, pad_id for a pad; an id outside the vocabulary counts as non-pad.  A position outside [0, max_pos)
+// reads nothing either: its row is NaN (the entry point's shape rule excludes it; this is the kernel's own bound).
+// TYPE = false: no token-type term, type_emb is not read.
+template <bool IDPOS, bool TYPE>
 __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_t* __restrict__ ids,
                                                                     const float* __restrict__ word_emb, int vocab,
-                                                                    const float* __restrict__ pos_emb,
-                                                                    const float* __restrict__ type_emb,
+                                                                    const float* __restrict__ pos_emb, int max_pos,
+                                                                    const float* __restrict__ type_emb, int pad_id,
                                                                     const float* __restrict__ g,
                                                                     const float* __restrict__ bt, float eps, int M, int T,
                                                                     int H4, float* __restrict__ out) {
@@ -81,15 +94,27 @@ __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_
   if (row >= M) return;
   float* dst = out + (size_t)row * H4 * 4;
   const int64_t id = ids[row];
-  if (id < 0 || id >= (int64_t)vocab) {
+  int pos = row % T;
+  if (IDPOS) {
+    const int64_t* q = ids + (size_t)(row - pos);       // this question's ids; lanes read q[0 .. pos] only
+    const bool n0 = lane <= pos && q[lane] != (int64_t)pad_id;
+    const bool n1 = lane + 64 <= pos && q[lane + 64] != (int64_t)pad_id;
+    const int count = __popcll(__ballot(n0)) + __popcll(__ballot(n1));
+    pos = id != (int64_t)pad_id ? pad_id + count : pad_id;
+  }
+  if (id < 0 || id >= (int64_t)vocab || pos < 0 || pos >= max_pos) {
     const float nan = __uint_as_float(0x7fc00000u);
     for (int i = lane; i < H4; i += 64) ((f32x4*)dst)[i] = (f32x4){nan, nan, nan, nan};
     return;
   }
   const f32x4* w = (const f32x4*)(word_emb + (size_t)id * H4 * 4);
-  const f32x4* p = (const f32x4*)(pos_emb + (size_t)(row % T) * H4 * 4);
-  const f32x4* ty = (const f32x4*)type_emb;
-  bert_ln_row([&](int i) { return (w[i] + ty[i]) + p[i]; }, g, bt, eps, H4, lane, dst);
+  const f32x4* p = (const f32x4*)(pos_emb + (size_t)pos * H4 * 4);
+  if (TYPE) {
+    const f32x4* ty = (const f32x4*)type_emb;
+    bert_ln_row([&](int i) { return (w[i] + ty[i]) + p[i]; }, g, bt, eps, H4, lane, dst);
+  } else {
+    bert_ln_row([&](int i) { return w[i] + p[i]; }, g, bt, eps, H4, lane, dst);
+  }
 }
 
 // out[row] = LN(in[row]); in already holds dense(x) + bias + residual.  out == in is allowed (no __restrict__ on the two).
@@ -118,12 +143,24 @@ __global__ __launch_bounds__(256) void k_bert_gelu(float* __restrict__ x, size_t
   if (tid < n - n4 * 4) x[n4 * 4 + tid] = bert_gelu(x[n4 * 4 + tid]);
 }
 
+// The value unchanged, behind a barrier the optimiser does not look through: what is computed before it is compiled as if
+// nothing followed.  k_bert_attention<DH, true> puts the scaled score through it before the bias is added, so that the dot
+// product in front of it compiles to the instructions of k_bert_attention<DH, false> (the compiler mixes fused and
+// unfused multiply-adds there by its own cost model) and an all-zero table gives that kernel's bits.
+__device__ __forceinline__ float bert_opaque(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
 // One workgroup per (question, head).  LDS: the head's K and V slices [T, DH] with a row stride of DH + 1 floats (odd: the
 // 32 lanes of a ds_read_b32 group that read k[lane][d] fall on 32 different banks), then per wave the query row [DH] and
 // its T probabilities.  A wave owns a query row: lanes are keys (lane and lane + 64), the maximum and the sum of the row
 // come from the fixed wave tree, then lanes run over d and add p[j] v[j][d] for j = 0 .. T - 1 in order.  No mask.
-template <int DH>
-__global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict__ qkv, int T, int heads,
+// BIAS: the head's row of rel_bias [heads, 2T-1] sits in LDS behind V (2T floats reserved) and the score of (t, j) is
+// (q . k) scale + bias[j - t + T - 1]; without it rel_bias is not read and the LDS layout is the one above.
+template <int DH, bool BIAS>
+__global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict__ qkv,
+                                                         const float* __restrict__ rel_bias, int T, int heads,
                                                          float* __restrict__ ctx) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LD = DH + 1;
@@ -132,7 +169,8 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
   const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
   float* ks = smem;                                   // [T, LD]
   float* vs = ks + T * LD;                            // [T, LD]
-  float* qs = vs + T * LD + wave * (DH + kBertMaxT);  // [DH]   this wave's query row
+  float* bs = vs + T * LD;                            // [2T - 1] the head's bias row (BIAS only)
+  float* qs = bs + (BIAS ? 2 * T : 0) + wave * (DH + kBertMaxT);  // [DH]   this wave's query row
   float* ps = qs + DH;                                // [kBertMaxT]  its probabilities
 
   const float* base = qkv + (size_t)b * T * 3 * H + h * DH;
@@ -146,6 +184,10 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
       ks[j * LD + c + e] = kv[e];
       vs[j * LD + c + e] = vv[e];
     }
+  }
+  if (BIAS) {
+    const float* br = rel_bias + (size_t)h * (2 * T - 1);
+    for (int i = tid; i < 2 * T - 1; i += nthr) bs[i] = br[i];
   }
   __syncthreads();
 
@@ -170,6 +212,10 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
       for (int d = 0; d < DH; ++d) a += qs[d] * k[d];
       s1 = a * scale;
     }
+    if (BIAS) {  // in blocks of their own, behind the barrier: the two blocks above are those of the kernel without a bias
+      if (j0 < T) s0 = bert_opaque(s0) + bs[j0 - t + T - 1];
+      if (j1 < T) s1 = bert_opaque(s1) + bs[j1 - t + T - 1];
+    }
     const float m = bert_wave_max(fmaxf(s0, s1));
     const float e0 = j0 < T ? expf(s0 - m) : 0.f, e1 = j1 < T ? expf(s1 - m) : 0.f;
     const float sum = bert_wave_sum(e0 + e1);
@@ -187,32 +233,36 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
   }
 }
 
-static inline size_t bert_att_lds_bytes(int T, int dh, int threads) {
-  return ((size_t)2 * T * (dh + 1) + (size_t)(threads / 64) * (dh + kBertMaxT)) * sizeof(float);
+static inline size_t bert_att_lds_bytes(int T, int dh, int threads, bool bias) {
+  return ((size_t)2 * T * (dh + 1) + (bias ? (size_t)2 * T : 0) + (size_t)(threads / 64) * (dh + kBertMaxT)) *
+         sizeof(float);
 }
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-static int bert_attention_launch(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
-                                 hipStream_t stream) {
+template <int DH, bool BIAS>
+static int bert_attention_launch_as(const float* qkv, const float* rel_bias, int32_t B, int32_t T, int32_t heads,
+                                    float* ctx, hipStream_t stream) {
   const int threads = GNNRAG_BERT_ATT_THREADS;
-  const size_t lds = bert_att_lds_bytes(T, dh, threads);
-  const dim3 grid((unsigned)((int64_t)B * heads));
-  if (dh == 32) {
-    if (lds > 64 * 1024) {
-      static DeviceMask raised{0};
-      GNNRAG_RC(raise_lds_cap(k_bert_attention<32>, raised));
-    }
-    hipLaunchKernelGGL(k_bert_attention<32>, grid, dim3(threads), lds, stream, qkv, T, heads, ctx);
-  } else {
-    if (lds > 64 * 1024) {
-      static DeviceMask raised{0};
-      GNNRAG_RC(raise_lds_cap(k_bert_attention<64>, raised));
-    }
-    hipLaunchKernelGGL(k_bert_attention<64>, grid, dim3(threads), lds, stream, qkv, T, heads, ctx);
+  const size_t lds = bert_att_lds_bytes(T, DH, threads, BIAS);
+  if (lds > 64 * 1024) {
+    static DeviceMask raised{0};
+    GNNRAG_RC(raise_lds_cap(k_bert_attention<DH, BIAS>, raised));
   }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_attention<DH, BIAS>), dim3((unsigned)((int64_t)B * heads)), dim3(threads), lds,
+                     stream, qkv, rel_bias, T, heads, ctx);
   GNNRAG_LAUNCH_CHECK();
   return 0;
+}
+
+// rel_bias NULL: no bias (the kernel never sees the pointer)
+static int bert_attention_launch(const float* qkv, const float* rel_bias, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                                 float* ctx, hipStream_t stream) {
+  if (dh == 32)
+    return rel_bias ? bert_attention_launch_as<32, true>(qkv, rel_bias, B, T, heads, ctx, stream)
+                    : bert_attention_launch_as<32, false>(qkv, nullptr, B, T, heads, ctx, stream);
+  return rel_bias ? bert_attention_launch_as<64, true>(qkv, rel_bias, B, T, heads, ctx, stream)
+                  : bert_attention_launch_as<64, false>(qkv, nullptr, B, T, heads, ctx, stream);
 }
 
 static inline bool bert_att_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {
@@ -249,33 +299,41 @@ extern "C" size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, i
   return bert_ws((int64_t)B * T, H, I).total;
 }
 
-extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
-                                     gnnrag_stream_t stream) {
+extern "C" int gnnrag_bert_attention_bias(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                                          const float* rel_bias, float* ctx, gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
   if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
   if (!qkv || !ctx) return GNNRAG_E_BADARG;
-  if (!aligned16(qkv) || !aligned16(ctx)) return GNNRAG_E_UNSUPPORTED;
-  return bert_attention_launch(qkv, B, T, heads, dh, ctx, (hipStream_t)stream);
+  if (!aligned16(qkv) || !aligned16(ctx) || !aligned16(rel_bias)) return GNNRAG_E_UNSUPPORTED;
+  return bert_attention_launch(qkv, rel_bias, B, T, heads, dh, ctx, (hipStream_t)stream);
 }
 
-extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
-                                  int32_t max_pos, const float* type_emb, const float* ln_g, const float* ln_b,
-                                  float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
-                                  int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
-                                  gnnrag_stream_t stream) {
+extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
+                                     gnnrag_stream_t stream) {
+  return gnnrag_bert_attention_bias(qkv, B, T, heads, dh, nullptr, ctx, stream);
+}
+
+// both entry points; need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type term"
+static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                           int32_t max_pos, const float* type_emb, bool need_type, int32_t pad_id, const float* rel_bias,
+                           const float* ln_g, const float* ln_b, float ln_eps, int32_t L, const gnnrag_bert_layer* layers,
+                           int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes,
+                           int32_t math, gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L < 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
   if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
   // the shape rules first: they are answered whatever the pointers are
   if (H % heads != 0 || H % 4 != 0 || T > kBertMaxT || T > max_pos) return GNNRAG_E_UNSUPPORTED;
+  // positions from the ids: a full row reaches position T + pad_id, which must be a row of pos_emb
+  if (pad_id >= 0 && (int64_t)T + pad_id > (int64_t)max_pos - 1) return GNNRAG_E_UNSUPPORTED;
   const int32_t dh = H / heads;
   if (!bert_att_shape_ok(B, T, heads, dh) || (int64_t)B * T >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
   const int64_t M = (int64_t)B * T;
   const BertWs w = bert_ws(M, H, I);
   if (L > 0 && ws_bytes < w.total) return GNNRAG_E_UNSUPPORTED;
-  if (!ids || !word_emb || !pos_emb || !type_emb || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
+  if (!ids || !word_emb || !pos_emb || (need_type && !type_emb) || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
     return GNNRAG_E_BADARG;
-  if (!aligned16(word_emb) || !aligned16(pos_emb) || !aligned16(type_emb) || !aligned16(ln_g) || !aligned16(ln_b) ||
-      !aligned16(out) || ((uintptr_t)ids & 7) || (L > 0 && !aligned16(ws)))
+  if (!aligned16(word_emb) || !aligned16(pos_emb) || !aligned16(type_emb) || !aligned16(rel_bias) || !aligned16(ln_g) ||
+      !aligned16(ln_b) || !aligned16(out) || ((uintptr_t)ids & 7) || (L > 0 && !aligned16(ws)))
     return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) {
     const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
@@ -290,8 +348,19 @@ extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int
   hipStream_t st = (hipStream_t)stream;
   const int H4 = H / 4;
   const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
-  hipLaunchKernelGGL(k_bert_embed_ln, ln_grid, ln_block, 0, st, ids, word_emb, vocab, pos_emb, type_emb, ln_g, ln_b,
-                     ln_eps, (int)M, T, H4, out);
+#define GNNRAG_EMBED_LN(IDPOS, TYPE)                                                                                 \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE>), ln_grid, ln_block, 0, st, ids, word_emb, vocab,  \
+                     pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out)
+  if (pad_id >= 0 && type_emb) {
+    GNNRAG_EMBED_LN(true, true);
+  } else if (pad_id >= 0) {
+    GNNRAG_EMBED_LN(true, false);
+  } else if (type_emb) {
+    GNNRAG_EMBED_LN(false, true);
+  } else {
+    GNNRAG_EMBED_LN(false, false);
+  }
+#undef GNNRAG_EMBED_LN
   GNNRAG_LAUNCH_CHECK();
   if (L == 0) return 0;
 
@@ -305,7 +374,7 @@ extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int
   for (int l = 0; l < L; ++l) {
     const gnnrag_bert_layer& p = layers[l];
     GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
-    GNNRAG_RC(bert_attention_launch(qkv, B, T, heads, dh, ctx, st));
+    GNNRAG_RC(bert_attention_launch(qkv, rel_bias, B, T, heads, dh, ctx, st));
     GNNRAG_RC(gnnrag_linear(ctx, M, H, p.W_o, p.b_o, out, M, 0, sum, H, math, stream));
     hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, p.ln1_g, p.ln1_b, ln_eps, (int)M, H4, out);
     GNNRAG_LAUNCH_CHECK();
@@ -317,4 +386,23 @@ extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int
     GNNRAG_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                  int32_t max_pos, const float* type_emb, const float* ln_g, const float* ln_b,
+                                  float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
+                                  int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
+                                  gnnrag_stream_t stream) {
+  return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, true, -1, nullptr, ln_g, ln_b, ln_eps, L, layers,
+                         B, T, H, heads, I, out, ws, ws_bytes, math, stream);
+}
+
+extern "C" int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                     int32_t max_pos, const float* type_emb, int32_t pad_id, const float* rel_bias,
+                                     const float* ln_g, const float* ln_b, float ln_eps, int32_t L,
+                                     const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads,
+                                     int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
+                                     gnnrag_stream_t stream) {
+  return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
+                         layers, B, T, H, heads, I, out, ws, ws_bytes, math, stream);
 }

@@ -1,21 +1,32 @@
-"""The frozen BERT-class question encoder of ``--lm sbert`` / ``bert`` / ``simcse`` on the MI355X.
+"""The frozen question encoder of ``--lm sbert`` / ``bert`` / ``simcse`` (transformers' ``BertModel``), ``--lm roberta`` /
+``relbert`` (``RobertaModel``) and ``--lm sbert2`` (``MPNetModel``) on the MI355X.
 
 The reference's ``BERTInstruction.encode_question`` (``gnn/modules/question_encoding/bert_encoder.py:94``) calls
-``self.node_encoder(query_text)[0]``: a transformers ``BertModel`` on the input ids alone - no attention mask, so pad tokens
+``self.node_encoder(query_text)[0]``: the transformers model on the input ids alone - no attention mask, so pad tokens
 are attended like any other token - twice per forward (``rearev.py:138`` and ``:192``).  In transformers that is 13-15
-launches per layer; ``ops.bert_encode`` runs it in 8 (``csrc/bert_encoder.hip``).
+launches per layer; ``ops.bert_encode`` runs it in 8 (``csrc/bert_encoder.hip``).  The three classes are one post-LayerNorm,
+erf-GELU block; what differs is read per class (``_ARCH``):
+
+* ``RobertaModel`` and ``MPNetModel`` take a token's position from the ids (``pad_id = embeddings.padding_idx``: a pad sits
+  at ``pad_id``, the n-th non-pad token at ``pad_id + n``), ``BertModel`` counts ``0 .. T-1``;
+* ``MPNetModel`` has no token-type embedding, names its projections ``attention.attn.q/k/v/o`` and adds
+  ``relative_attention_bias.weight[bucket(j - i)]`` to the scaled scores of every layer: the table ``[heads, 2T-1]`` is
+  built here with transformers' own ``MPNetEncoder.relative_position_bucket`` and kept per ``T``.
 
 ``patch_lm_encoder(instr)`` wraps ``instr.node_encoder.forward`` ON THE INSTANCE by a bound method of a state object (the
 pattern of ``instruction.patch_instruction``: a ``copy.deepcopy`` of the model gets a wrapper of its own).  Parameters,
 ``state_dict`` keys and ``.to()`` are untouched.  A call is taken when ALL of these hold, else the original forward runs
 unchanged:
 
-* ``GNNRAG_HIP_LM`` is not ``0`` (read at every call; the default is on by the rule and the numbers of DESIGN.md section 8
-  f-6; ``GNNRAG_HIP_LM=0`` leaves transformers' forward in charge of every call);
-* the encoder's type is exactly transformers' ``BertModel``, with absolute positions, ``hidden_act == "gelu"``, not a decoder
-  (RoBERTa, MPNet and T5 encoders keep their own forward);
+* the switch is on for the class (read at every call): ``GNNRAG_HIP_LM=0`` is off for every class, any other value is on
+  for every class, unset is on for the classes in ``DEFAULT_ON`` - those whose measurement met the rule of DESIGN.md
+  section 8 f-6;
+* the encoder's type is exactly transformers' ``BertModel``, ``RobertaModel`` or ``MPNetModel`` (no subclass), with
+  absolute position embeddings, ``hidden_act == "gelu"``, not a decoder; a RoBERTa / MPNet encoder has a ``padding_idx``,
+  an MPNet encoder 32 relative-attention buckets (T5 encoders keep their own forward);
 * the only argument is a 2-D int64 CUDA ``input_ids`` (an ``attention_mask``, ``token_type_ids``, ... fall through);
-* all parameters are contiguous fp32 CUDA tensors and the kernels take the shape (``ops.bert_encode_supported``);
+* all parameters are contiguous fp32 CUDA tensors and the kernels take the shape (``ops.bert_encode_supported``; with
+  positions from the ids also ``T + pad_id <= max_position_embeddings - 1``, where transformers itself would raise);
 * nothing needs a gradient: grad mode is off, or no LM parameter requires grad;
 * dropout is inert: the module is in eval mode, or both dropout probabilities are 0 (``Trainer_KBQA`` runs a frozen LM in
   training mode with dropout 0.1: those calls fall through).
@@ -23,7 +34,7 @@ unchanged:
 An eligible call returns a ``BaseModelOutput`` whose ``[0]`` is ``last_hidden_state``; the pooler is not computed (the
 reference never reads it).  The packed query / key / value weight and bias of every layer are kept on the state object,
 keyed by ``(data_ptr, _version)`` of their six source tensors (as ``install.cache_rel_features`` keys its cache): an
-in-place parameter update or a ``.to()`` refreshes them.
+in-place parameter update or a ``.to()`` refreshes them; MPNet's bias tables are keyed the same way.
 
 ``transformers`` is imported only inside :func:`patch_lm_encoder` and the eligible call: this package imports without it.
 """
@@ -35,16 +46,41 @@ import torch
 
 from ... import ops
 
-DEFAULT = "1"        # GNNRAG_HIP_LM when unset (the rule and the measurement)
+DEFAULT = "1"        # GNNRAG_HIP_LM for BertModel when unset (the rule and the measurement)
+# classes that are on when GNNRAG_HIP_LM is unset; the others need GNNRAG_HIP_LM=1.  RobertaModel and MPNetModel were
+# measured at the 768-wide, 12-layer shape: 3-4 x less host time, but more stream time than transformers at B = 1 and
+# B = 64 (DESIGN.md section 8 f-6 keeps the numbers), so by the rule they stay off
+DEFAULT_ON = ("BertModel",)
+REL_BUCKETS = 32                # MPNetEncoder.compute_position_bias passes its default, whatever the configuration says
+
+# what differs between the classes: where positions come from, the token-type term, the attention bias, the names
+_ARCH = {
+    "BertModel": dict(id_positions=False, token_type=True, rel_bias=False),
+    "RobertaModel": dict(id_positions=True, token_type=True, rel_bias=False),
+    "MPNetModel": dict(id_positions=True, token_type=False, rel_bias=True),
+}
 
 
-def enabled() -> bool:
-    """Whether the patched forward uses the library (read at every call: the switch can change in-process)."""
-    return os.environ.get("GNNRAG_HIP_LM", DEFAULT) != "0"
+def enabled(arch: str = "BertModel") -> bool:
+    """Whether the patched forward of an encoder of class ``arch`` uses the library (read at every call: the switch can
+    change in-process)."""
+    v = os.environ.get("GNNRAG_HIP_LM")
+    if v is None:
+        return arch in DEFAULT_ON and DEFAULT != "0"
+    return v != "0"
 
 
 def _f32_cuda_contig(t) -> bool:
     return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+
+
+def rel_bias_table(encoder, T: int) -> torch.Tensor:
+    """``[heads, 2T-1]``: entry ``[h, d + T - 1]`` is what ``MPNetEncoder.compute_position_bias`` adds to the score of
+    query i and key j = i + d of head h.  The buckets come from transformers' own function, on the CPU as it runs it."""
+    d = torch.arange(-(T - 1), T, dtype=torch.long)
+    bucket = type(encoder).relative_position_bucket(d, num_buckets=REL_BUCKETS)
+    w = encoder.relative_attention_bias.weight.detach()
+    return w[bucket.to(w.device)].t().contiguous()
 
 
 class _LmPatch:
@@ -53,20 +89,35 @@ class _LmPatch:
 
     def __init__(self, enc):
         self.enc = enc
+        self.arch = type(enc).__name__
         self.orig_forward = enc.forward
         self.key, self.packed = None, None      # the packed W_qkv / b_qkv of every layer and what they were made from
+        self.bias_key, self.bias = None, {}     # MPNet: T -> the bias table, and the weight they were made from
         self.hip_calls = 0                      # eligible calls served by the library (tests, tools)
 
     # -- eligibility ----------------------------------------------------------------------------------------------
+    def pad_id(self):
+        """The padding id positions are counted from (RoBERTa, MPNet), else None."""
+        if not _ARCH[self.arch]["id_positions"]:
+            return None
+        pad = getattr(self.enc.embeddings, "padding_idx", None)
+        return int(pad) if isinstance(pad, int) and not isinstance(pad, bool) else -1
+
     def refusal(self, args, kwargs):
         """None when the call runs on the library, else the first rule (of the module docstring) it does not meet."""
-        enc, cfg = self.enc, self.enc.config
-        if not enabled():
+        enc, cfg, arch = self.enc, self.enc.config, _ARCH[self.arch]
+        if not enabled(self.arch):
             return "GNNRAG_HIP_LM is off"
         if (getattr(cfg, "position_embedding_type", None) not in (None, "absolute") or
                 getattr(cfg, "hidden_act", None) != "gelu" or getattr(cfg, "is_decoder", False) or
                 getattr(cfg, "add_cross_attention", False)):
             return "not an absolute-position, gelu, encoder-only configuration"
+        pad = self.pad_id()
+        if pad is not None and pad < 0:
+            return "no padding_idx to count positions from"
+        if arch["rel_bias"] and (int(getattr(cfg, "relative_attention_num_buckets", 0)) != REL_BUCKETS or
+                                 enc.encoder.relative_attention_bias.weight.shape[0] != REL_BUCKETS):
+            return "a relative attention bias of other than 32 buckets"
         ids = args[0] if args else kwargs.get("input_ids")
         if len(args) + len(kwargs) != 1 or not isinstance(ids, torch.Tensor):
             return "arguments other than input_ids"
@@ -78,7 +129,7 @@ class _LmPatch:
         if enc.training and (float(cfg.hidden_dropout_prob) != 0.0 or float(cfg.attention_probs_dropout_prob) != 0.0):
             return "dropout is active"
         if not ops.bert_encode_supported(int(ids.shape[1]), int(cfg.hidden_size), int(cfg.num_attention_heads),
-                                         int(cfg.intermediate_size), int(cfg.max_position_embeddings)):
+                                         int(cfg.intermediate_size), int(cfg.max_position_embeddings), pad_id=pad):
             return "a shape the kernels do not take"
         if not ids.is_cuda:
             return "input_ids is not a CUDA tensor"
@@ -87,11 +138,18 @@ class _LmPatch:
         return None
 
     # -- parameters -----------------------------------------------------------------------------------------------
+    def _projections(self, layer):
+        """(query, key, value, output projection, the LayerNorm behind it) of one layer."""
+        a = layer.attention
+        if self.arch == "MPNetModel":
+            return a.attn.q, a.attn.k, a.attn.v, a.attn.o, a.LayerNorm
+        return a.self.query, a.self.key, a.self.value, a.output.dense, a.output.LayerNorm
+
     def _qkv_sources(self):
         out = []
         for layer in self.enc.encoder.layer:
-            s = layer.attention.self
-            out += [s.query.weight, s.key.weight, s.value.weight, s.query.bias, s.key.bias, s.value.bias]
+            q, k, v, _, _ = self._projections(layer)
+            out += [q.weight, k.weight, v.weight, q.bias, k.bias, v.bias]
         return out
 
     def packed_qkv(self):
@@ -108,12 +166,26 @@ class _LmPatch:
     def layers(self):
         out = []
         for layer, (W_qkv, b_qkv) in zip(self.enc.encoder.layer, self.packed_qkv()):
-            ao, it, fo = layer.attention.output, layer.intermediate.dense, layer.output
-            out.append({"W_qkv": W_qkv, "b_qkv": b_qkv, "W_o": ao.dense.weight, "b_o": ao.dense.bias,
-                        "ln1_g": ao.LayerNorm.weight, "ln1_b": ao.LayerNorm.bias, "W_i": it.weight, "b_i": it.bias,
+            _, _, _, o, ln1 = self._projections(layer)
+            it, fo = layer.intermediate.dense, layer.output
+            out.append({"W_qkv": W_qkv, "b_qkv": b_qkv, "W_o": o.weight, "b_o": o.bias,
+                        "ln1_g": ln1.weight, "ln1_b": ln1.bias, "W_i": it.weight, "b_i": it.bias,
                         "W_f": fo.dense.weight, "b_f": fo.dense.bias, "ln2_g": fo.LayerNorm.weight,
                         "ln2_b": fo.LayerNorm.bias})
         return out
+
+    def rel_bias(self, T):
+        """MPNet's bias table for ``T`` tokens (None for the other classes), kept until the weight changes."""
+        if not _ARCH[self.arch]["rel_bias"]:
+            return None
+        w = self.enc.encoder.relative_attention_bias.weight
+        key = (w.data_ptr(), w._version)
+        if self.bias_key != key:
+            self.bias_key, self.bias = key, {}
+        if T not in self.bias:
+            with torch.no_grad():
+                self.bias[T] = rel_bias_table(self.enc.encoder, T)
+        return self.bias[T]
 
     # -- the wrapper ----------------------------------------------------------------------------------------------
     def forward(self, *args, **kwargs):
@@ -123,29 +195,32 @@ class _LmPatch:
         enc = self.enc
         ids = args[0] if args else kwargs["input_ids"]
         emb, cfg = enc.embeddings, enc.config
+        type_emb = emb.token_type_embeddings.weight if _ARCH[self.arch]["token_type"] else None
         with torch.no_grad():
-            hidden = ops.bert_encode(ids, emb.word_embeddings.weight, emb.position_embeddings.weight,
-                                     emb.token_type_embeddings.weight, emb.LayerNorm.weight, emb.LayerNorm.bias,
-                                     float(cfg.layer_norm_eps), self.layers(), int(cfg.num_attention_heads),
-                                     I=int(cfg.intermediate_size))
+            hidden = ops.bert_encode(ids, emb.word_embeddings.weight, emb.position_embeddings.weight, type_emb,
+                                     emb.LayerNorm.weight, emb.LayerNorm.bias, float(cfg.layer_norm_eps), self.layers(),
+                                     int(cfg.num_attention_heads), I=int(cfg.intermediate_size), pad_id=self.pad_id(),
+                                     rel_bias=self.rel_bias(int(ids.shape[1])))
         self.hip_calls += 1
         return BaseModelOutput(last_hidden_state=hidden)
 
 
 def patch_lm_encoder(instr):
-    """Wraps ``instr.node_encoder.forward`` when the encoder is exactly transformers' ``BertModel`` (see the module
-    docstring).  Idempotent; anything else - no ``node_encoder``, another encoder class, no transformers - is returned as it
-    is."""
+    """Wraps ``instr.node_encoder.forward`` when the encoder is exactly transformers' ``BertModel``, ``RobertaModel`` or
+    ``MPNetModel`` (see the module docstring).  Idempotent; anything else - no ``node_encoder``, another encoder class, a
+    subclass, no transformers - is returned as it is."""
     enc = getattr(instr, "node_encoder", None)
     if enc is None or getattr(enc, "_gnnrag_lm_patch", None) is not None:
         return instr
-    if type(enc).__name__ != "BertModel" or not type(enc).__module__.startswith("transformers."):
+    name = type(enc).__name__
+    if name not in _ARCH or not type(enc).__module__.startswith("transformers."):
         return instr                            # an nn.LSTM / HipLSTM encoder: transformers is not even imported
     try:
-        from transformers import BertModel
-    except ImportError:
+        import transformers
+        cls = getattr(transformers, name)
+    except (ImportError, AttributeError):
         return instr
-    if type(enc) is not BertModel:
+    if type(enc) is not cls:
         return instr
     p = _LmPatch(enc)
     # plain instance attributes (nn.Module.__setattr__ keeps non-module, non-parameter values in __dict__): no

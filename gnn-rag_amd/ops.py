@@ -1595,32 +1595,57 @@ BERT_MAX_T = 128                                # keys of one question: two per 
 BERT_LAYER_FIELDS = tuple(n for n, _ in _lib.BertLayer._fields_)
 
 
-def bert_encode_supported(T: int, H: int, heads: int, I: int, max_pos: int) -> bool:
-    """Whether ``gnnrag_bert_encode`` takes the shape (the header's rules)."""
+def bert_encode_supported(T: int, H: int, heads: int, I: int, max_pos: int, pad_id: Optional[int] = None) -> bool:
+    """Whether ``gnnrag_bert_encode`` / ``gnnrag_bert_encode_ex`` takes the shape (the header's rules).  ``pad_id``: the
+    padding id of an encoder whose positions come from the ids (RoBERTa, MPNet): a full row reaches position
+    ``T + pad_id``, which must be a row of the position table."""
+    if pad_id is not None and (pad_id < 0 or T + pad_id > max_pos - 1):
+        return False
     return (0 < T <= min(BERT_MAX_T, max_pos) and H > 0 and I > 0 and heads > 0 and H % heads == 0 and H % 4 == 0 and
             H // heads in (32, 64))
 
 
-def bert_attention(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int) -> torch.Tensor:
+def _bert_pad_id(pad_id) -> int:
+    if pad_id is None:
+        return -1
+    if int(pad_id) < 0:
+        raise ValueError("pad_id must be None (positions 0 .. T-1) or >= 0")
+    return int(pad_id)
+
+
+def bert_attention(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int,
+                   rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``gnnrag_bert_attention``: qkv [B*T, 3*heads*dh] (query, key, value blocks of a row in that order) ->
-    ctx [B*T, heads*dh] = softmax(q k^T / sqrt(dh)) v per (question, head), no mask."""
+    ctx [B*T, heads*dh] = softmax(q k^T / sqrt(dh)) v per (question, head), no mask.  ``rel_bias`` [heads, 2T-1]
+    (``gnnrag_bert_attention_bias``): ``rel_bias[h, j - i + T - 1]`` is added to the scaled score of query i and key j."""
     lib = _lib.load()
     H = heads * dh
     qkv = _chk(qkv, "qkv", shape=(B * T, 3 * H))
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
     ctx = _buf((B * T, H), torch.float32, qkv.device, "bert_attention: ctx")
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.gnnrag_bert_attention(qkv.data_ptr(), B, T, heads, dh, ctx.data_ptr(), _stream()),
-                   "gnnrag_bert_attention")
+        if rel_bias is None:
+            _lib.check(lib.gnnrag_bert_attention(qkv.data_ptr(), B, T, heads, dh, ctx.data_ptr(), _stream()),
+                       "gnnrag_bert_attention")
+        else:
+            _lib.check(lib.gnnrag_bert_attention_bias(qkv.data_ptr(), B, T, heads, dh, rel_bias.data_ptr(), ctx.data_ptr(),
+                                                      _stream()), "gnnrag_bert_attention_bias")
     return ctx
 
 
 def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int, I: Optional[int] = None,
-                math: Optional[int] = None) -> torch.Tensor:
+                math: Optional[int] = None, *, pad_id: Optional[int] = None,
+                rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``gnnrag_bert_encode``: ids [B,T] int64 -> the last hidden state [B,T,H] of a BERT-class encoder (no mask, no
     pooler).  ``layers``: a list of dicts with the keys ``BERT_LAYER_FIELDS`` (W_qkv [3H,H] the query / key / value weights
     stacked, b_qkv [3H], W_o, b_o, ln1_g, ln1_b, W_i [I,H], b_i, W_f [H,I], b_f, ln2_g, ln2_b); an empty list returns the
     embedding LayerNorm (``I`` then sizes nothing and defaults to 4 H).  A shape outside the library's set raises
-    ``GnnragError`` (GNNRAG_E_UNSUPPORTED)."""
+    ``GnnragError`` (GNNRAG_E_UNSUPPORTED).
+
+    ``type_emb=None`` (no token-type term), ``pad_id`` (positions from the ids, as RoBERTa and MPNet count them) and
+    ``rel_bias`` [heads, 2T-1] (MPNet's relative attention bias, every layer) go through ``gnnrag_bert_encode_ex``; with
+    the defaults the call is the one it has always been."""
     lib = _lib.load()
     ids = _chk(ids, "ids", dtype=torch.int64)
     if ids.dim() != 2:
@@ -1631,9 +1656,13 @@ def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers
     pos_emb = _chk(pos_emb.detach(), "pos_emb")
     if pos_emb.dim() != 2 or pos_emb.shape[1] != H:
         raise ValueError("pos_emb must be [max_pos,H]")
-    type_emb = _chk(type_emb.detach(), "type_emb")
-    if type_emb.dim() != 2 or type_emb.shape[1] != H or type_emb.shape[0] < 1:
-        raise ValueError("type_emb must be [>=1,H]")
+    if type_emb is not None:
+        type_emb = _chk(type_emb.detach(), "type_emb")
+        if type_emb.dim() != 2 or type_emb.shape[1] != H or type_emb.shape[0] < 1:
+            raise ValueError("type_emb must be [>=1,H]")
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
+    pad = _bert_pad_id(pad_id)
     ln_g, ln_b = _chk(ln_g.detach(), "ln_g", shape=(H,)), _chk(ln_b.detach(), "ln_b", shape=(H,))
     L = len(layers)
     if L:
@@ -1653,10 +1682,17 @@ def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers
     nws = int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)) if L else 0
     ws = _buf((max(nws, 1),), torch.uint8, dev, "bert_encode: workspace")
     with torch.cuda.device(dev):
-        _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(), pos_emb.shape[0],
-                                          type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(), float(eps), L, arr, B, T, H,
-                                          heads, I, out.data_ptr(), ws.data_ptr(), ws.numel(), _math(math), _stream()),
-                   "gnnrag_bert_encode")
+        if type_emb is not None and pad < 0 and rel_bias is None:
+            _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
+                                              pos_emb.shape[0], type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(),
+                                              float(eps), L, arr, B, T, H, heads, I, out.data_ptr(), ws.data_ptr(),
+                                              ws.numel(), _math(math), _stream()), "gnnrag_bert_encode")
+        else:
+            _lib.check(lib.gnnrag_bert_encode_ex(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
+                                                 pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
+                                                 ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I, out.data_ptr(),
+                                                 ws.data_ptr(), ws.numel(), _math(math), _stream()),
+                       "gnnrag_bert_encode_ex")
     return out
 
 

@@ -801,7 +801,24 @@ int gnnrag_instructions_backward(const float* hidden, const float* node, const f
  * H % heads != 0, H / heads not in {32, 64}, T > 128, T > max_pos, H % 4 != 0, ws_bytes below
  * gnnrag_bert_workspace_bytes(B, T, H, I) (L > 0), a pointer that is not 16-byte aligned (ids: 8).  A NULL pointer or a
  * size <= 0 is GNNRAG_E_BADARG.
- * gnnrag_bert_attention is the attention step alone: qkv [B T, 3 heads dh] packed as above, ctx [B T, heads dh]. */
+ * gnnrag_bert_attention is the attention step alone: qkv [B T, 3 heads dh] packed as above, ctx [B T, heads dh].
+ *
+ * gnnrag_bert_encode_ex / gnnrag_bert_attention_bias (additive to ABI 16): the same block as RobertaModel and MPNetModel
+ * run it on input ids alone (--lm roberta / relbert / sbert2), by three more inputs; with type_emb given, pad_id < 0 and
+ * rel_bias NULL they are gnnrag_bert_encode / gnnrag_bert_attention, bit for bit.
+ *   type_emb NULL: no token-type term (MPNet); not read.
+ *   pad_id >= 0:   positions come from the ids (transformers' create_position_ids_from_input_ids): a token that is not
+ *                  pad_id sits at pad_id + (number of non-pad ids among ids[b, 0 .. t]), a pad at pad_id.  Pads are still
+ *                  attended (no mask).  An id outside [0, vocab) counts as non-pad for the rows after it (its own row is
+ *                  NaN as above).  A wave counts its own question's ids only: no dependence on B.  A position outside
+ *                  [0, max_pos) reads nothing (its row is NaN); the shape rule below excludes it.
+ *   rel_bias:      [heads, 2T-1] or NULL.  The score of query i and key j of a head is (q_i . k_j) / sqrt(dh) +
+ *                  rel_bias[head][j - i + T - 1], in every layer (MPNet's relative_attention_bias gathered at the
+ *                  bucket of j - i).  Not read when L = 0.
+ * One more GNNRAG_E_UNSUPPORTED rule, answered with the shape rules: pad_id >= 0 and T + pad_id > max_pos - 1 (a full row
+ * reaches position T + pad_id; transformers raises there too).  A rel_bias that is not 16-byte aligned is UNSUPPORTED.
+ * Workspace, launches per layer, capture safety, "no allocation" and "nothing waits" are as above.  Attention masks, T5
+ * (RMS norm, unscaled scores, its own bias rule), dropout and gradients remain outside. */
 typedef struct gnnrag_bert_layer { const float *W_qkv, *b_qkv, *W_o, *b_o, *ln1_g, *ln1_b,
                                                *W_i, *b_i, *W_f, *b_f, *ln2_g, *ln2_b; } gnnrag_bert_layer;
 size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I);
@@ -812,6 +829,14 @@ int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab,
                        int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads,
                        int32_t I, float* out /* [B,T,H] */, void* ws, size_t ws_bytes, int32_t math,
                        gnnrag_stream_t stream);
+int gnnrag_bert_attention_bias(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                               const float* rel_bias /* [heads,2T-1] or NULL */, float* ctx, gnnrag_stream_t stream);
+int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb, int32_t max_pos,
+                          const float* type_emb /* or NULL */, int32_t pad_id /* < 0: positions 0 .. T-1 */,
+                          const float* rel_bias /* [heads,2T-1] or NULL */, const float* ln_g, const float* ln_b,
+                          float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
+                          int32_t heads, int32_t I, float* out /* [B,T,H] */, void* ws, size_t ws_bytes, int32_t math,
+                          gnnrag_stream_t stream);
 
 /* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
  * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):

@@ -2,7 +2,8 @@
 """The frozen BERT-class question encoder with ``GNNRAG_HIP_LM`` off (transformers' own forward) and on
 (``patch_lm_encoder``: ``gnnrag_bert_encode``, 8 launches per layer), each setting in a process of its own, started fresh:
 
-    python tools/time_bert_encoder.py [--iters 20] [--warm 5] [--rounds 2] [--out profiles/bert_encoder_time.jsonl]
+    python tools/time_bert_encoder.py [--arch bert|roberta|mpnet] [--iters 20] [--warm 5] [--rounds 2]
+                                      [--out profiles/bert_encoder_time.jsonl]
     python tools/time_bert_encoder.py --kernel [--libs 256=,64=gnn-rag_amd/lib/exp_bertatt64.so,...]
 
 * the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
@@ -11,6 +12,9 @@
   (the device is idle before, nothing waits inside), HIP events around it = stream time.  Median of ``--iters`` after
   ``--warm``; ``--rounds`` repeats the off / on pair: the spread between two runs of one leg is the noise the rule for the
   default is read against (DESIGN.md section 8 f-6);
+* ``--arch roberta`` / ``mpnet``: a ``RobertaModel`` / ``MPNetModel`` of the roberta-base / all-mpnet-base-v2 shape (hidden
+  768, 12 heads, intermediate 3072, 12 layers, 514 positions; random weights from tests/lm_variants_oracle.py), ids with
+  pads in them, the same three (B, T) and the same two legs (``GNNRAG_HIP_LM=0`` / ``=1``); no per-kernel split;
 * the per-kernel split of the HIP leg (switch on only): 20 calls captured into one graph and replayed - the whole encode,
   the embedding LayerNorm alone (L = 0), one layer's attention and its four dense products alone; what remains per layer is
   the two LayerNorms and the GELU;
@@ -30,6 +34,9 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(1, 12), (8, 20), (64, 20)]
 L, VOCAB, MAX_POS = 6, 30522, 512
+BASE = dict(H=768, heads=12, I=3072)               # roberta-base, all-mpnet-base-v2: 12 layers, 514 positions
+ARCHS = {"bert": "BertModel", "roberta": "RobertaModel", "mpnet": "MPNetModel"}
+BASE_L, BASE_VOCAB, BASE_MAX_POS = 12, {"roberta": 50265, "mpnet": 30527}, 514
 TAG = "GNNRAG_BERT "
 CALLS = 20
 
@@ -98,14 +105,30 @@ def child_encode(a):
     import numpy as np
     from gnnrag_amd import ops
     from gnnrag_amd.modules.question_encoding.lm_encoder import enabled, patch_lm_encoder
-    m32, _ = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)
+    on = enabled(ARCHS[a.arch])
+    if a.arch == "bert":
+        shape, n_layers, vocab = bo.MINILM, L, VOCAB
+        m32 = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)[0]
+    else:
+        import lm_variants_oracle as lo
+        shape, n_layers, vocab = BASE, BASE_L, BASE_VOCAB[a.arch]
+        model = lo.model_class(a.arch)(lo.config(a.arch, L=BASE_L, vocab=vocab, max_pos=BASE_MAX_POS, **BASE))
+        rs = np.random.RandomState(1)
+        with torch.no_grad():                   # lo.make_model without its float64 copy (125 M parameters)
+            for name, p in model.named_parameters():
+                w = rs.standard_normal(tuple(p.shape)) * (0.05 if p.dim() >= 2 else 0.1)
+                p.copy_(torch.from_numpy((1.0 + w if name.endswith("LayerNorm.weight") else w).astype(np.float32)))
+        m32 = model
     enc = m32.to(dev).eval()
     for p in enc.parameters():
         p.requires_grad_(False)
     patch_lm_encoder(_Holder(enc))
     patch = enc._gnnrag_lm_patch
     for B, T in SHAPES:
-        ids0 = torch.from_numpy(np.random.RandomState(B).randint(0, VOCAB, (B, T))).long().to(dev)
+        ids0 = np.random.RandomState(B).randint(0 if a.arch == "bert" else 2, vocab, (B, T))
+        if a.arch != "bert":
+            ids0[1::2, T // 2:] = 1             # every second question padded from the middle (pad id 1)
+        ids0 = torch.from_numpy(ids0).long().to(dev)
         ids = [ids0.clone() for _ in range(a.warm + a.iters)]
         out = []
 
@@ -115,12 +138,13 @@ def child_encode(a):
 
         before = patch.hip_calls
         host, ev, host_min, ev_min = _measure(torch, encode, ids, a.warm)
-        rec = {"what": "encode", "switch": "on" if enabled() else "off", "B": B, "T": T, "L": L, "H": 384, "I": 1536,
+        rec = {"what": "encode", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
+               "H": shape["H"], "I": shape["I"],
                "host_ms": host, "event_ms": ev, "host_ms_min": host_min, "event_ms_min": ev_min, "iters": a.iters,
                "warm": a.warm, "hip_calls_per_encode": (patch.hip_calls - before) / len(ids),
                "checksum": float(out[0].double().square().sum()), "device": torch.cuda.get_device_name(0)}
         print(TAG + json.dumps(rec), flush=True)
-        if not enabled():
+        if not on or a.arch != "bert":
             continue
         # the split of the HIP leg
         P = bo.layer_params(enc)
@@ -179,6 +203,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warm", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--arch", choices=sorted(ARCHS), default="bert")
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--libs", default="256=")
     ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
@@ -188,7 +213,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return {"encode": child_encode, "kernel": child_kernel}[a.child](a)
-    common = ["--iters", str(a.iters), "--warm", str(a.warm)]
+    common = ["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch]
     lines = []
     if a.kernel:
         for spec in a.libs.split(","):
