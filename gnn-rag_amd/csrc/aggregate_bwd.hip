@@ -123,12 +123,6 @@ __device__ __forceinline__ float prior_grad_range(const BwdArgs& a, const float*
   return acc;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // one wave per source node; blockIdx.y = question (its instructions are staged in LDS once)
 template <bool V4, bool FUSED = false>
 __global__ __launch_bounds__(256) void k_bwd_prior(const BwdArgs a) {
@@ -795,8 +789,7 @@ extern "C" int gnnrag_aggregate_backward(const gnnrag_csr* csr, const gnnrag_rel
   a.g_ins = g_ins;
   a.g_T[0] = g_T_fwd;
   a.g_T[1] = g_T_inv;
-  const bool v4 = D % 4 == 0 && ((uintptr_t)g_agg & 15) == 0 && ((uintptr_t)T_fwd & 15) == 0 &&
-                  ((uintptr_t)T_inv & 15) == 0 && ((uintptr_t)ins & 15) == 0;
+  const bool v4 = D % 4 == 0 && aligned16(g_agg, T_fwd, T_inv, ins);
   const dim3 pgrid((csr->N + 3) / 4, csr->B);
   const size_t plds = (size_t)I * D * sizeof(float);
   if (v4) hipLaunchKernelGGL(k_bwd_prior<true>, pgrid, dim3(256), plds, stream, a);
@@ -846,7 +839,7 @@ extern "C" int gnnrag_aggregate_fused_backward(const gnnrag_csr* csr, const gnnr
                                                void* workspace, size_t workspace_bytes, gnnrag_stream_t stream_) {
   if (!csr || !relorder || !dist || !P || !g_nbr || !g_dist || !g_P || D <= 0 || csr->rel_total < 0) return GNNRAG_E_BADARG;
   if (relorder->F != csr->F || relorder->rel_total != csr->rel_total) return GNNRAG_E_BADARG;
-  if (!gather_ok(relorder, D, 1) || ((((uintptr_t)P | (uintptr_t)g_nbr | (uintptr_t)g_P) & 15) != 0)) return GNNRAG_E_UNSUPPORTED;
+  if (!gather_ok(relorder, D, 1) || !aligned16(P, g_nbr, g_P)) return GNNRAG_E_UNSUPPORTED;
   if (!workspace || workspace_bytes < gnnrag_backward_workspace_bytes(csr, relorder, D, 1)) return GNNRAG_E_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   BwdArgs a;

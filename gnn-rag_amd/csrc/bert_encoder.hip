@@ -33,18 +33,6 @@ namespace gnnrag {
 constexpr int kBertMaxT = 128;       // keys per question: two per lane
 constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
 
-__device__ __forceinline__ float bert_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float bert_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // LayerNorm of one row by one wave: biased variance, two passes (mean, then sum (x - mean)^2); `load(i)` returns the
 // i-th float4 of the row (called three times per element: the row is L2 / L1 resident).  dst may be the row `load` reads:
 // a lane writes only the elements it has read itself, after both reductions.
@@ -57,14 +45,14 @@ __device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__
     const f32x4 v = load(i);
     s += (v[0] + v[1]) + (v[2] + v[3]);
   }
-  const float mean = bert_wave_sum(s) * inv_h;
+  const float mean = wave_sum(s) * inv_h;
   float q = 0.f;
   for (int i = lane; i < H4; i += 64) {
     const f32x4 v = load(i);
     const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
     q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
   }
-  const float rstd = 1.f / sqrtf(bert_wave_sum(q) * inv_h + eps);
+  const float rstd = 1.f / sqrtf(wave_sum(q) * inv_h + eps);
   for (int i = lane; i < H4; i += 64) {
     const f32x4 v = load(i);
     const f32x4 gg = ((const f32x4*)g)[i], bb = ((const f32x4*)bt)[i];
@@ -216,9 +204,9 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
       if (j0 < T) s0 = bert_opaque(s0) + bs[j0 - t + T - 1];
       if (j1 < T) s1 = bert_opaque(s1) + bs[j1 - t + T - 1];
     }
-    const float m = bert_wave_max(fmaxf(s0, s1));
+    const float m = wave_max(fmaxf(s0, s1));
     const float e0 = j0 < T ? expf(s0 - m) : 0.f, e1 = j1 < T ? expf(s1 - m) : 0.f;
-    const float sum = bert_wave_sum(e0 + e1);
+    const float sum = wave_sum(e0 + e1);
     if (j0 < T) ps[j0] = e0 / sum;
     if (j1 < T) ps[j1] = e1 / sum;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -237,8 +225,6 @@ static inline size_t bert_att_lds_bytes(int T, int dh, int threads, bool bias) {
   return ((size_t)2 * T * (dh + 1) + (bias ? (size_t)2 * T : 0) + (size_t)(threads / 64) * (dh + kBertMaxT)) *
          sizeof(float);
 }
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <int DH, bool BIAS>
 static int bert_attention_launch_as(const float* qkv, const float* rel_bias, int32_t B, int32_t T, int32_t heads,
@@ -277,16 +263,12 @@ struct BertWs {
 
 static inline BertWs bert_ws(int64_t M, int64_t H, int64_t I) {
   BertWs w;
-  size_t o = 0;
-  w.qkv = o;
-  o += align_up((size_t)M * 3 * H * sizeof(float), 256);
-  w.ctx = o;
-  o += align_up((size_t)M * H * sizeof(float), 256);
-  w.sum = o;
-  o += align_up((size_t)M * H * sizeof(float), 256);
-  w.ffn = o;
-  o += align_up((size_t)M * I * sizeof(float), 256);
-  w.total = o;
+  Carve cv;
+  w.qkv = cv.take((size_t)M * 3 * H * sizeof(float));
+  w.ctx = cv.take((size_t)M * H * sizeof(float));
+  w.sum = cv.take((size_t)M * H * sizeof(float));
+  w.ffn = cv.take((size_t)M * I * sizeof(float));
+  w.total = cv.off;
   return w;
 }
 
@@ -304,7 +286,7 @@ extern "C" int gnnrag_bert_attention_bias(const float* qkv, int32_t B, int32_t T
   if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
   if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
   if (!qkv || !ctx) return GNNRAG_E_BADARG;
-  if (!aligned16(qkv) || !aligned16(ctx) || !aligned16(rel_bias)) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(qkv, ctx, rel_bias)) return GNNRAG_E_UNSUPPORTED;
   return bert_attention_launch(qkv, rel_bias, B, T, heads, dh, ctx, (hipStream_t)stream);
 }
 
@@ -332,8 +314,8 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   if (L > 0 && ws_bytes < w.total) return GNNRAG_E_UNSUPPORTED;
   if (!ids || !word_emb || !pos_emb || (need_type && !type_emb) || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
     return GNNRAG_E_BADARG;
-  if (!aligned16(word_emb) || !aligned16(pos_emb) || !aligned16(type_emb) || !aligned16(rel_bias) || !aligned16(ln_g) ||
-      !aligned16(ln_b) || !aligned16(out) || ((uintptr_t)ids & 7) || (L > 0 && !aligned16(ws)))
+  if (!aligned16(word_emb, pos_emb, type_emb, rel_bias, ln_g, ln_b, out) || ((uintptr_t)ids & 7) ||
+      (L > 0 && !aligned16(ws)))
     return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) {
     const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,

@@ -34,36 +34,31 @@ struct CsrLayout {
 
 static CsrLayout csr_layout(int64_t F, int32_t B, int32_t N, int32_t R1, int has_w_gnn, int has_w_rel) {
   CsrLayout L;
-  size_t off = 0;
+  Carve cv;
   const size_t BN = (size_t)B * (size_t)N;
   const size_t Fp = (size_t)(F > 0 ? F : 1);
   L.heavy_cap = (int32_t)(Fp / kHeavyDeg + 1);
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  for (int d = 0; d < 2; ++d) L.row_ptr[d] = take((BN + 1) * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.edge[d] = take(Fp * 2 * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.perm[d] = take(Fp * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.w_gnn[d] = has_w_gnn ? take(Fp * sizeof(float)) : 0;
-  for (int d = 0; d < 2; ++d) L.w_rel[d] = has_w_rel ? take(Fp * sizeof(float)) : 0;
-  for (int d = 0; d < 2; ++d) L.heavy[d] = take((size_t)L.heavy_cap * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.chunk_off[d] = take(((size_t)L.heavy_cap + 1) * sizeof(int32_t));
-  L.n_heavy = take(8 * sizeof(int32_t));   // n_heavy[2], n_chunks[2], rel_total, rel_max
-  L.big_cnt = take((size_t)B * sizeof(int32_t));
-  L.big_nodes = take(BN * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.edge_l[d] = take(Fp * 2 * sizeof(int32_t));
-  L.rel_off = take(((size_t)B + 1) * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.row_ptr[d] = cv.take((BN + 1) * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.edge[d] = cv.take(Fp * 2 * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.perm[d] = cv.take(Fp * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.w_gnn[d] = has_w_gnn ? cv.take(Fp * sizeof(float)) : 0;
+  for (int d = 0; d < 2; ++d) L.w_rel[d] = has_w_rel ? cv.take(Fp * sizeof(float)) : 0;
+  for (int d = 0; d < 2; ++d) L.heavy[d] = cv.take((size_t)L.heavy_cap * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.chunk_off[d] = cv.take(((size_t)L.heavy_cap + 1) * sizeof(int32_t));
+  L.n_heavy = cv.take(8 * sizeof(int32_t));   // n_heavy[2], n_chunks[2], rel_total, rel_max
+  L.big_cnt = cv.take((size_t)B * sizeof(int32_t));
+  L.big_nodes = cv.take(BN * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.edge_l[d] = cv.take(Fp * 2 * sizeof(int32_t));
+  L.rel_off = cv.take(((size_t)B + 1) * sizeof(int32_t));
   const size_t BR = (size_t)B * (size_t)R1;
-  L.rel_rows = take((BR < Fp ? BR : Fp) * 2 * sizeof(int32_t));   // every compact row has >= 1 fact
-  L.edge_m = take(2 * Fp * 2 * sizeof(int32_t));
-  L.m_from = take(2 * Fp * sizeof(int32_t));
-  L.m_dst = take(2 * Fp * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.hub_q_off[d] = take(((size_t)B + 1) * sizeof(int32_t));
-  for (int d = 0; d < 2; ++d) L.hub_wbase[d] = take(((size_t)B + 1) * sizeof(int32_t));
-  L.hub_qcnt = take((size_t)B * sizeof(int32_t));
-  L.total = off;
+  L.rel_rows = cv.take((BR < Fp ? BR : Fp) * 2 * sizeof(int32_t));   // every compact row has >= 1 fact
+  L.edge_m = cv.take(2 * Fp * 2 * sizeof(int32_t));
+  L.m_from = cv.take(2 * Fp * sizeof(int32_t));
+  L.m_dst = cv.take(2 * Fp * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.hub_q_off[d] = cv.take(((size_t)B + 1) * sizeof(int32_t));
+  for (int d = 0; d < 2; ++d) L.hub_wbase[d] = cv.take(((size_t)B + 1) * sizeof(int32_t));
+  L.hub_qcnt = cv.take((size_t)B * sizeof(int32_t));
+  L.total = cv.off;
   return L;
 }
 
@@ -150,23 +145,18 @@ struct HubSortScratch {
 static HubSortScratch hub_sort_scratch(int64_t F, int32_t R1, int32_t heavy_cap) {
   HubSortScratch H;
   const size_t Fp = (size_t)(F > 0 ? F : 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
+  Carve cv;
   if (R1 <= kHubSortMinR1) {
     H.key_in = H.key_out = H.perm2 = H.seg = H.temp = H.total = 0;
     return H;
   }
-  H.key_in = take(Fp * sizeof(uint32_t));
-  H.key_out = take(Fp * sizeof(uint32_t));
-  H.perm2 = take(Fp * sizeof(int32_t));
-  H.seg = take((size_t)2 * heavy_cap * sizeof(int32_t));
+  H.key_in = cv.take(Fp * sizeof(uint32_t));
+  H.key_out = cv.take(Fp * sizeof(uint32_t));
+  H.perm2 = cv.take(Fp * sizeof(int32_t));
+  H.seg = cv.take((size_t)2 * heavy_cap * sizeof(int32_t));
   const unsigned hb = hub_key_bits(R1, heavy_cap);
-  H.temp = take(hb <= 32 ? pair_sort_temp_bytes(F, hb) : seg_sort_temp_bytes(F, heavy_cap, key_bits((size_t)R1)));
-  H.total = off;
+  H.temp = cv.take(hb <= 32 ? pair_sort_temp_bytes(F, hb) : seg_sort_temp_bytes(F, heavy_cap, key_bits((size_t)R1)));
+  H.total = cv.off;
   return H;
 }
 
@@ -697,17 +687,16 @@ struct RelLayout { size_t ht, perm, w, row_ptr, chunk_ptr, total_cnt, total; };
 
 static RelLayout rel_layout(const gnnrag_csr* csr, int has_w) {
   RelLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+  Carve cv;
   const size_t Fp = (size_t)(csr->F > 0 ? csr->F : 1);
   const size_t R = (size_t)(csr->rel_total > 0 ? csr->rel_total : 0);
-  L.ht = take(Fp * 2 * sizeof(int32_t));
-  L.perm = take(Fp * sizeof(int32_t));
-  L.w = has_w ? take(Fp * sizeof(float)) : 0;
-  L.row_ptr = take((R + 1) * sizeof(int32_t));
-  L.chunk_ptr = take((R + 1) * sizeof(int32_t));
-  L.total_cnt = take(sizeof(int32_t));
-  L.total = off;
+  L.ht = cv.take(Fp * 2 * sizeof(int32_t));
+  L.perm = cv.take(Fp * sizeof(int32_t));
+  L.w = has_w ? cv.take(Fp * sizeof(float)) : 0;
+  L.row_ptr = cv.take((R + 1) * sizeof(int32_t));
+  L.chunk_ptr = cv.take((R + 1) * sizeof(int32_t));
+  L.total_cnt = cv.take(sizeof(int32_t));
+  L.total = cv.off;
   return L;
 }
 

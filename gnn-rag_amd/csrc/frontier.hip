@@ -36,18 +36,17 @@ struct FrontierWs {                        // offsets into the caller's frontier
 
 static FrontierWs frontier_ws(const gnnrag_csr* csr) {
   FrontierWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+  Carve cv;
   const size_t BN = (size_t)csr->B * csr->N;
   const size_t RT = (size_t)(csr->rel_total > 0 ? csr->rel_total : 1);
-  w.counts = take((size_t)2 * csr->B * sizeof(int32_t));      // [B][2]: listed nodes / relation rows of each question
-  w.row_flag = take(BN + 64);              // one byte per node (+ padding: the update kernels read 4 flags at once)
-  w.rows = take(BN * sizeof(int32_t));
-  w.tflag = take(RT + 64);
-  w.trows = take(RT * sizeof(int32_t));
-  w.seeds = take((size_t)csr->B * kFrAltSeeds * sizeof(int32_t));   // a question's seeds in ascending order ...
-  w.seedinfo = take((size_t)2 * csr->B * sizeof(int32_t));          // ... their number (-1: more than listed) and facts
-  w.total = off;
+  w.counts = cv.take((size_t)2 * csr->B * sizeof(int32_t));      // [B][2]: listed nodes / relation rows of each question
+  w.row_flag = cv.take(BN + 64);              // one byte per node (+ padding: the update kernels read 4 flags at once)
+  w.rows = cv.take(BN * sizeof(int32_t));
+  w.tflag = cv.take(RT + 64);
+  w.trows = cv.take(RT * sizeof(int32_t));
+  w.seeds = cv.take((size_t)csr->B * kFrAltSeeds * sizeof(int32_t));   // a question's seeds in ascending order ...
+  w.seedinfo = cv.take((size_t)2 * csr->B * sizeof(int32_t));          // ... their number (-1: more than listed) and facts
+  w.total = cv.off;
   return w;
 }
 
@@ -447,16 +446,11 @@ const uint8_t* gnnrag::frontier_row_flags(const gnnrag_csr* csr, const void* fws
 
 // (the two frontier entry points below issue 16-byte accesses: misaligned operands are refused here, the layer driver
 // then takes the regular fused path)
-static bool fr_aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
-                         const void* e = nullptr) {
-  return ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0);
-}
-
 extern "C" int gnnrag_relation_tables_frontier(const gnnrag_csr* csr, const void* fws, const float* T_fwd,
                                                const float* T_inv, const float* ins, const float* W, float* P,
                                                int32_t D, int32_t I, gnnrag_stream_t stream) {
   if (!csr || !fws || !T_fwd || !T_inv || !ins || !W || !P || I <= 0) return GNNRAG_E_BADARG;
-  if (!gnnrag_frontier_supported(csr, D) || !fr_aligned16(T_fwd, T_inv, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
+  if (!gnnrag_frontier_supported(csr, D) || !aligned16(T_fwd, T_inv, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
   if (csr->rel_total == 0) return 0;
   const FrontierWs w = frontier_ws(csr);
   const char* base = (const char*)fws;
@@ -478,7 +472,7 @@ extern "C" int gnnrag_relation_tables_frontier(const gnnrag_csr* csr, const void
 extern "C" int gnnrag_aggregate_fused_frontier(const gnnrag_csr* csr, const void* fws, const float* dist,
                                                const float* P, float* out, int32_t D, gnnrag_stream_t stream) {
   if (!csr || !fws || !dist || !P || !out) return GNNRAG_E_BADARG;
-  if (!gnnrag_frontier_supported(csr, D) || !fr_aligned16(P, out) || csr->N <= 0) return GNNRAG_E_UNSUPPORTED;
+  if (!gnnrag_frontier_supported(csr, D) || !aligned16(P, out) || csr->N <= 0) return GNNRAG_E_UNSUPPORTED;
   const FrontierWs w = frontier_ws(csr);
   const char* base = (const char*)fws;
   WalkFrArgs a;
@@ -530,7 +524,7 @@ int gnnrag::tables_small_launch(const gnnrag_csr* csr, const float* T_fwd, const
                                 const float* W, float* P, int32_t D, int32_t I, hipStream_t stream) {
   if (D % 4 || D > 256 || csr->rel_total <= 0) return GNNRAG_E_UNSUPPORTED;
   if (2.0 * 2 * csr->rel_total * (double)I * D * D > 1.5e8) return GNNRAG_E_UNSUPPORTED;      // a job for the GEMM kernels
-  if ((((uintptr_t)T_fwd | (uintptr_t)T_inv | (uintptr_t)ins | (uintptr_t)W) & 15) != 0) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(T_fwd, T_inv, ins, W)) return GNNRAG_E_UNSUPPORTED;
   TabFrArgs a;
   a.T[0] = T_fwd; a.T[1] = T_inv; a.ins = ins; a.W = W;
   a.rel_rows = (const int2*)csr->rel_rows;

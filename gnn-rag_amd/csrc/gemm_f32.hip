@@ -420,6 +420,7 @@ void k_gemm_f32(GemmArgs g) {
             if (EPI == EPI_UPDATE) part = v[0] * ws4[0] + v[1] * ws4[1] + v[2] * ws4[2] + v[3] * ws4[3];
           }
           if constexpr (EPI == EPI_UPDATE) {
+            // wave_sum's tree, spelled out: the call leaves this kernel's bits alone but moves its register allocation
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
             const float mrow = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mk), rr));
@@ -790,12 +791,10 @@ __global__ __launch_bounds__(256) void k_score_rows(const float* __restrict__ h,
   if (row >= M) return;
   float s = 0.f;
   for (int c = lane; c < D; c += 64) s += h[(size_t)row * D + c] * w_s[c];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  s = wave_sum(s);
   if (lane == 0) score[row] = (s + b_s[0]) + (1.0f - mask[row]) * kVeryNeg;
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 
 // ---- skinny problems (M up to a few thousand rows, e.g. the [R1,D] relation transforms) ------

@@ -114,7 +114,7 @@ extern "C" int gnnrag_gemm_tn(const float* A, const float* B, int64_t M, int32_t
                               void* workspace, size_t workspace_bytes, gnnrag_stream_t stream) {
   if (!A || !B || !C || M < 0 || N1 <= 0 || N2 <= 0) return GNNRAG_E_BADARG;
   if ((N1 & 3) || (N2 & 3) || M >= ((int64_t)1 << 40)) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)workspace) & 15) != 0) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(A, B, C, workspace)) return GNNRAG_E_UNSUPPORTED;
   if (M == 0) {
     GNNRAG_HIP(hipMemsetAsync(C, 0, (size_t)N1 * N2 * sizeof(float), (hipStream_t)stream));
     return 0;

@@ -34,6 +34,22 @@ constexpr float kVeryNeg = -100000000000.0f;  // reasongnn.py:9 (VERY_NEG_NUMBER
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// true when every pointer given is 16-byte aligned (a null pointer counts as aligned)
+template <typename... P>
+static inline bool aligned16(const P*... p) {
+  return ((... | (uintptr_t)p) & 15) == 0;
+}
+
+// carves a workspace into 256-byte aligned regions: take() returns the region's offset, `off` ends as the total
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off += align_up(bytes, 256);
+    return o;
+  }
+};
+
 // Idempotent per-device caches of launch attributes (they never change a result).  One bit / slot per
 // device ordinal; devices >= 64 simply repeat the (idempotent) runtime call.
 typedef std::atomic<unsigned long long> DeviceMask;
@@ -116,6 +132,44 @@ __device__ __forceinline__ Split3 split3(f32x4 x) {
 }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// The library's reduction trees: one fixed summation order each, so the same bits every time.
+// All 64 lanes of a wave get the result of the xor tree (offsets 32, 16, .. 1).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// the workgroup's sum in one fixed order: xor tree inside a wave, then the 16 waves in order; every thread gets it.
+// Requires a workgroup of exactly 1024 threads, all of them calling, and red[16] in LDS (bcast: one LDS float).
+__device__ __forceinline__ float block_sum(float s, float* red, float* bcast) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  s = wave_sum(s);
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 16; ++k) t += red[k];
+    *bcast = t;
+  }
+  __syncthreads();
+  const float r = *bcast;
+  __syncthreads();                       // red / bcast may be reused
+  return r;
+}
 #endif
 
 // relation tables in the bf16x3 math mode on a W-resident kernel (tables_b3.hip); returns GNNRAG_E_UNSUPPORTED when
@@ -158,7 +212,29 @@ int update_b3_launch(const float* h, const float* nbr, const float* W, const flo
                      const float* mask, float* h_out, float* score, int64_t BN, int32_t D, int32_t ldw,
                      hipStream_t stream);
 
-// dst [cols, rows] = src [rows, cols]^T (lstm.hip: the transposed weight copies of the LSTM forward and backward)
-int lstm_transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t stream);
+// The small dense auxiliaries of dense_aux.hip.
+// dst [cols, rows] = src [rows, cols]^T
+int transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t stream);
+
+// dst [rows, cols] = the first cols columns of the first rows rows of src [., ld]
+int unpad_launch(const float* src, float* dst, int rows, int cols, int ld, hipStream_t stream);
+
+// Column sums of up to GNNRAG_MAX_INS + 2 row blocks in one launch: dst[j][c] = sum over the rows[j] rows of
+// src[j][., c] (leading dimension ld[j]), c < cols.  Rows in 8 slices of (rows + 7) / 8, a slice in ascending rows, the
+// slices added in slice order.
+struct ColsumJobs {
+  const float* src[GNNRAG_MAX_INS + 2];
+  float* dst[GNNRAG_MAX_INS + 2];
+  int64_t rows[GNNRAG_MAX_INS + 2];
+  int32_t ld[GNNRAG_MAX_INS + 2];
+  int32_t cols;
+};
+int colsum_launch(const ColsumJobs& jobs, int n_jobs, hipStream_t stream);
+
+// dst [N1, N2] = the first N1 rows and N2 columns of A^T B, A [M, N1p], B [M, N2p] (the operands zero-padded to what
+// gnnrag_gemm_tn takes): straight into dst where nothing is padded and dst is 16-byte aligned, else into cpad
+// [N1p, N2p] and copied.  tn_ws: gnnrag_gemm_tn_workspace_bytes(M, N1p, N2p) bytes.
+int gemm_tn_unpadded(const float* A, const float* B, int64_t M, int32_t N1p, int32_t N2p, int32_t N1, int32_t N2,
+                     float* dst, float* cpad, void* tn_ws, size_t tn_bytes, hipStream_t stream);
 
 }  // namespace gnnrag

@@ -44,12 +44,6 @@ struct InsTrain {                    // what the training form adds (all NULL / 
   float* reserve;                    // [n, B, 2 D]   q_s, then cq
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <bool TRAIN, bool MASKS>
 __global__ __launch_bounds__(1024) void k_instructions(const float* __restrict__ hidden, const float* __restrict__ node,
                                                        const float* __restrict__ mask, const float* __restrict__ r_in,
@@ -174,8 +168,7 @@ __global__ __launch_bounds__(1024) void k_instructions(const float* __restrict__
     // softmax over the T tokens: every wave derives the same maximum and the same sum (same order), no hand-over
     float m = -INFINITY;
     for (int t = lane; t < T; t += 64) m = fmaxf(m, lg[t]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = wave_max(m);
     float sum = 0.f;
     for (int t = lane; t < T; t += 64) sum += expf(lg[t] - m);
     sum = wave_sum(sum);

@@ -63,12 +63,6 @@ struct InsBwdArgs {
   int32_t B, T, D, Dp, n;
 };
 
-__device__ __forceinline__ float ins_bwd_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(1024) void k_ins_bwd(const InsBwdArgs g) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int T = g.T, D = g.D, Dp = g.Dp, B = g.B, TD = T * D;
@@ -144,14 +138,14 @@ __global__ __launch_bounds__(1024) void k_ins_bwd(const InsBwdArgs g) {
       const float* h = hid + t * D;
       float acc = 0.f;
       for (int d = lane; d < D; d += 64) acc += drp[d] * h[d];
-      acc = ins_bwd_wave_sum(acc);
+      acc = wave_sum(acc);
       if (lane == 0) dav[t] = acc + (g.g_attn ? g.g_attn[row * T + t] : 0.f);
     }
     __syncthreads();
     // dca_t = a_t (da_t - sum_u a_u da_u): every wave derives the same inner sum (same order), no hand-over
     float inner = 0.f;
     for (int t = lane; t < T; t += 64) inner += av[t] * dav[t];
-    inner = ins_bwd_wave_sum(inner);
+    inner = wave_sum(inner);
     for (int t = tid; t < T; t += nthr) dca[t] = av[t] * (dav[t] - inner);
     __syncthreads();
     // dh: element i belongs to thread i mod nthr in every step
@@ -225,47 +219,6 @@ __global__ __launch_bounds__(1024) void k_ins_bwd(const InsBwdArgs g) {
   }
 }
 
-// column sums of up to GNNRAG_MAX_INS + 2 row blocks in one launch (blockIdx.y = the job): 32 columns x 8 row slices per
-// workgroup, a slice in ascending rows, the slices added in slice order
-struct InsColsumJobs {
-  const float* src[GNNRAG_MAX_INS + 2];
-  float* dst[GNNRAG_MAX_INS + 2];
-  int32_t rows[GNNRAG_MAX_INS + 2], ld[GNNRAG_MAX_INS + 2];
-  int32_t cols;
-};
-
-__global__ __launch_bounds__(256) void k_ins_colsum(const InsColsumJobs jobs) {
-  __shared__ float sm[8][32];
-  const int job = blockIdx.y;
-  const float* __restrict__ src = jobs.src[job];
-  float* dst = jobs.dst[job];
-  const int M = jobs.rows[job], ld = jobs.ld[job];
-  const int cx = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  const int per = (M + 7) / 8;
-  const int m0 = sl * per, m1 = m0 + per < M ? m0 + per : M;
-  float acc = 0.f;
-  if (c < jobs.cols)
-    for (int m = m0; m < m1; ++m) acc += src[(size_t)m * ld + c];
-  sm[sl][cx] = acc;
-  __syncthreads();
-  if (sl == 0 && c < jobs.cols) {
-    float v = sm[0][cx];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) v += sm[i][cx];
-    dst[c] = v;
-  }
-}
-
-// dst [rows, cols] = the first cols columns of the first rows rows of src [., ld]
-__global__ __launch_bounds__(256) void k_ins_unpad(const float* __restrict__ src, float* __restrict__ dst, int rows,
-                                                   int cols, int ld) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * cols) return;
-  const int r = i / cols, c = i - r * cols;
-  dst[i] = src[(size_t)r * ld + c];
-}
-
 struct InsBwdLayout {
   size_t dcq, dq, ns, z, cqu, cpad, tn, tn_bytes, total;
   int32_t Dp;
@@ -275,18 +228,18 @@ static InsBwdLayout ins_bwd_layout(int32_t B, int32_t D, int32_t n) {
   InsBwdLayout l;
   const size_t M = (size_t)n * B;
   l.Dp = (D + 3) / 4 * 4;
-  size_t off = 0;
-  l.dcq = off; off += align_up(M * l.Dp * sizeof(float), 256);
-  l.dq = off; off += align_up(M * l.Dp * sizeof(float), 256);
-  l.ns = off; off += align_up(M * l.Dp * sizeof(float), 256);
-  l.z = off; off += align_up(M * 4 * D * sizeof(float), 256);
-  l.cqu = off; off += align_up(M * D * sizeof(float), 256);
-  l.cpad = off; off += align_up((size_t)l.Dp * 4 * D * sizeof(float), 256);       // >= Dp * Dp
+  Carve cv;
+  l.dcq = cv.take(M * l.Dp * sizeof(float));
+  l.dq = cv.take(M * l.Dp * sizeof(float));
+  l.ns = cv.take(M * l.Dp * sizeof(float));
+  l.z = cv.take(M * 4 * D * sizeof(float));
+  l.cqu = cv.take(M * D * sizeof(float));
+  l.cpad = cv.take((size_t)l.Dp * 4 * D * sizeof(float));                          // >= Dp * Dp
   const size_t t1 = gnnrag_gemm_tn_workspace_bytes((int64_t)M, l.Dp, 4 * D);
   const size_t t2 = gnnrag_gemm_tn_workspace_bytes((int64_t)B, l.Dp, l.Dp);
   l.tn_bytes = t1 > t2 ? t1 : t2;
-  l.tn = off; off += align_up(l.tn_bytes, 256);
-  l.total = off;
+  l.tn = cv.take(l.tn_bytes);
+  l.total = cv.off;
   return l;
 }
 
@@ -319,7 +272,7 @@ extern "C" int gnnrag_instructions_backward(const float* hidden, const float* no
   if (!ins_bwd_shape_ok(B, T, D, n_steps)) return GNNRAG_E_UNSUPPORTED;
   for (int s = 0; s < n_steps; ++s)
     if (!W_q[s]) return GNNRAG_E_BADARG;
-  if (((uintptr_t)workspace & 15) != 0) return GNNRAG_E_UNSUPPORTED;              // gemm_tn
+  if (!aligned16(workspace)) return GNNRAG_E_UNSUPPORTED;                         // gemm_tn
   if (!reserve || reserve_bytes < gnnrag_instructions_reserve_bytes(B, T, D, n_steps)) return GNNRAG_E_WORKSPACE;
   const InsBwdLayout l = ins_bwd_layout(B, D, n_steps);
   if (!workspace || workspace_bytes < l.total) return GNNRAG_E_WORKSPACE;
@@ -345,41 +298,25 @@ extern "C" int gnnrag_instructions_backward(const float* hidden, const float* no
   GNNRAG_LAUNCH_CHECK();
 
   float* cpad = (float*)(ws + l.cpad);
-  if (dW_cq) {
-    if (Dp == D && ((uintptr_t)dW_cq & 15) == 0) {
-      GNNRAG_RC(gnnrag_gemm_tn(a.w_dcq, a.w_z, M, Dp, 4 * D, dW_cq, ws + l.tn, l.tn_bytes, stream_));
-    } else {
-      GNNRAG_RC(gnnrag_gemm_tn(a.w_dcq, a.w_z, M, Dp, 4 * D, cpad, ws + l.tn, l.tn_bytes, stream_));
-      hipLaunchKernelGGL(k_ins_unpad, dim3((D * 4 * D + 255) / 256), dim3(256), 0, stream, cpad, dW_cq, D, 4 * D, 4 * D);
-      GNNRAG_LAUNCH_CHECK();
-    }
-  }
+  if (dW_cq)
+    GNNRAG_RC(gemm_tn_unpadded(a.w_dcq, a.w_z, M, Dp, 4 * D, D, 4 * D, dW_cq, cpad, ws + l.tn, l.tn_bytes, stream));
   for (int s = 0; dW_q && s < n_steps; ++s) {
     if (!dW_q[s]) continue;
     const float* dq = a.w_dq + (size_t)s * B * Dp;
     const float* ns = a.w_ns + (size_t)s * B * Dp;
-    if (Dp == D && ((uintptr_t)dW_q[s] & 15) == 0) {
-      GNNRAG_RC(gnnrag_gemm_tn(dq, ns, B, Dp, Dp, dW_q[s], ws + l.tn, l.tn_bytes, stream_));
-    } else {
-      GNNRAG_RC(gnnrag_gemm_tn(dq, ns, B, Dp, Dp, cpad, ws + l.tn, l.tn_bytes, stream_));
-      hipLaunchKernelGGL(k_ins_unpad, dim3((D * D + 255) / 256), dim3(256), 0, stream, cpad, dW_q[s], D, D, Dp);
-      GNNRAG_LAUNCH_CHECK();
-    }
+    GNNRAG_RC(gemm_tn_unpadded(dq, ns, B, Dp, Dp, D, D, dW_q[s], cpad, ws + l.tn, l.tn_bytes, stream));
   }
-  InsColsumJobs jobs;
+  ColsumJobs jobs;
   memset(&jobs, 0, sizeof(jobs));
   jobs.cols = D;
   int nj = 0;
-  if (db_cq) { jobs.src[nj] = a.w_dcq; jobs.dst[nj] = db_cq; jobs.rows[nj] = (int32_t)M; jobs.ld[nj] = Dp; ++nj; }
-  if (dw_ca) { jobs.src[nj] = a.w_cqu; jobs.dst[nj] = dw_ca; jobs.rows[nj] = (int32_t)M; jobs.ld[nj] = D; ++nj; }
+  if (db_cq) { jobs.src[nj] = a.w_dcq; jobs.dst[nj] = db_cq; jobs.rows[nj] = M; jobs.ld[nj] = Dp; ++nj; }
+  if (dw_ca) { jobs.src[nj] = a.w_cqu; jobs.dst[nj] = dw_ca; jobs.rows[nj] = M; jobs.ld[nj] = D; ++nj; }
   for (int s = 0; db_q && s < n_steps; ++s) {
     if (!db_q[s]) continue;
     jobs.src[nj] = a.w_dq + (size_t)s * B * Dp; jobs.dst[nj] = db_q[s]; jobs.rows[nj] = B; jobs.ld[nj] = Dp; ++nj;
   }
-  if (nj) {
-    hipLaunchKernelGGL(k_ins_colsum, dim3((D + 31) / 32, nj), dim3(256), 0, stream, jobs);
-    GNNRAG_LAUNCH_CHECK();
-  }
+  if (nj) GNNRAG_RC(colsum_launch(jobs, nj, stream));
   if (db_ca) GNNRAG_HIP(hipMemsetAsync(db_ca, 0, sizeof(float), stream));
   return 0;
 }

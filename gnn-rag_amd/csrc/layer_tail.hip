@@ -13,7 +13,7 @@
 //                row, as one float4 where D % 4 == 0 and every base is 16-byte aligned (keep: 4-byte), else element by
 //                element with the SAME ownership - both forms add a row's products in the same order and give the same
 //                bits.  The row sum goes over a fixed __shfl_xor tree.  Grid capped and grid-strided.
-//   k_lt_gs      one workgroup per question: sigma in one fixed order (thread-strided sums, xor tree, the waves in order),
+//   k_lt_gs      one workgroup per question: sigma in one fixed order (thread-strided sums, then block_sum),
 //                then gs [B, N] to the workspace.
 //   k_lt_bwd     the same row walk; writes EVERY element of g_pre.  A lane keeps the dw sums of its columns in registers
 //                over all rows its wave walks, the workgroup's waves combine through LDS in wave order and the workgroup
@@ -29,12 +29,6 @@ constexpr int kLtWaves = 4;              // waves (= rows in flight) per workgro
 constexpr int kLtFwdGrid = 2048;         // 256 CUs x 8 workgroups: the cap of the forward's grid
 constexpr int kLtBwdGrid = 1024;         // the backward's cap = the most partial rows k_lt_dw_sum adds
 constexpr int kLtSlices = 16;            // slices of the partial rows in k_lt_dw_sum
-
-__device__ __forceinline__ float lt_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // columns 4 c .. 4 c + 3 of a row of D floats; beyond D: zeros
 template <bool VEC>
@@ -105,7 +99,7 @@ __global__ __launch_bounds__(kLtWaves * 64) void k_lt_fwd(const float* __restric
       }
       lt_st4<VEC>(h_out + base, c, D, v);
     }
-    acc = lt_wave_sum(acc);
+    acc = wave_sum(acc);
     // the fp32 sum the reference writes (no contraction): a padded node's score is kVeryNeg for any |s| < 4096
     if (lane == 0)
       score[r] = __fadd_rn(__fadd_rn(__fmul_rn(acc, scale), bs), __fmul_rn(__fsub_rn(1.f, mask[r]), kVeryNeg));
@@ -120,19 +114,9 @@ __global__ __launch_bounds__(1024) void k_lt_gs(const float* __restrict__ dist, 
   const size_t off = (size_t)blockIdx.x * N;
   const float* __restrict__ p = dist + off;
   const float* __restrict__ g = g_dist + off;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float s = 0.f;
   for (int i = threadIdx.x; i < N; i += 1024) s = fmaf(p[i], g[i], s);
-  s = lt_wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < 16; ++k) t += red[k];
-    bcast = t;
-  }
-  __syncthreads();
-  const float sigma = bcast;
+  const float sigma = block_sum(s, red, &bcast);
   for (int i = threadIdx.x; i < N; i += 1024) gs[off + i] = p[i] * (g[i] - sigma);
 }
 
@@ -224,8 +208,6 @@ __global__ __launch_bounds__(kLtSlices * 64) void k_lt_dw_sum(const float* __res
   }
 }
 
-static inline bool lt_al(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static inline int lt_grid(int64_t rows, int cap) {
   const int64_t blocks = (rows + kLtWaves - 1) / kLtWaves;
   return (int)(blocks < cap ? blocks : cap);
@@ -240,10 +222,10 @@ static LtBwdLayout lt_bwd_layout(int32_t B, int32_t N, int32_t D) {
   LtBwdLayout l;
   const int64_t rows = (int64_t)B * N;
   l.grid = lt_grid(rows, kLtBwdGrid);
-  size_t off = 0;
-  l.gs = off; off += align_up((size_t)rows * sizeof(float), 256);
-  l.part = off; off += align_up((size_t)l.grid * D * sizeof(float), 256);
-  l.total = off;
+  Carve cv;
+  l.gs = cv.take((size_t)rows * sizeof(float));
+  l.part = cv.take((size_t)l.grid * D * sizeof(float));
+  l.total = cv.off;
   return l;
 }
 
@@ -277,8 +259,7 @@ extern "C" int gnnrag_layer_tail_train(const float* pre_a, const float* pre_b, c
   hipStream_t stream = (hipStream_t)stream_;
   const int64_t rows = (int64_t)B * N;
   const int grid = lt_grid(rows, kLtFwdGrid);
-  const bool vec = (D & 3) == 0 && lt_al(pre_a, 16) && lt_al(pre_b, 16) && lt_al(w_score, 16) && lt_al(h_out, 16) &&
-                   lt_al(keep, 4);
+  const bool vec = (D & 3) == 0 && aligned16(pre_a, pre_b, w_score, h_out) && ((uintptr_t)keep & 3) == 0;
   if (vec)
     hipLaunchKernelGGL(k_lt_fwd<true>, dim3(grid), dim3(kLtWaves * 64), 0, stream, pre_a, pre_b, keep, scale, w_score,
                        b_score, mask, rows, D, h_out, score);
@@ -312,8 +293,7 @@ extern "C" int gnnrag_layer_tail_backward(const float* h, const float* dist, con
     hipLaunchKernelGGL(k_lt_gs, dim3(B), dim3(1024), 0, stream, dist, g_dist, N, gs);
     GNNRAG_LAUNCH_CHECK();
   }
-  const bool vec = (D & 3) == 0 && lt_al(h, 16) && lt_al(g_h, 16) && lt_al(w_score, 16) && lt_al(g_pre, 16) &&
-                   lt_al(keep, 4);
+  const bool vec = (D & 3) == 0 && aligned16(h, g_h, w_score, g_pre) && ((uintptr_t)keep & 3) == 0;
   const int C = (D + 3) / 4;
   if (C <= 64) lt_bwd_launch<1>(vec, l.grid, stream, h, keep, scale, w_score, g_h, gs, rows, D, g_pre, part, db_score);
   else if (C <= 128) lt_bwd_launch<2>(vec, l.grid, stream, h, keep, scale, w_score, g_h, gs, rows, D, g_pre, part, db_score);

@@ -36,29 +36,6 @@ struct LstmArgs {
   int32_t B, T, E, H;
 };
 
-// dst[k][j] = src[j][k]  (src [rows][cols])
-__global__ __launch_bounds__(256) void k_lstm_transpose(const float* __restrict__ src, float* __restrict__ dst, int rows,
-                                                        int cols) {
-  __shared__ float tile[32][33];
-  const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  for (int i = ty; i < 32; i += 8) {
-    const int r = by + i, c = bx + tx;
-    tile[i][tx] = (r < rows && c < cols) ? src[(size_t)r * cols + c] : 0.f;
-  }
-  __syncthreads();
-  for (int i = ty; i < 32; i += 8) {
-    const int c = bx + i, r = by + tx;
-    if (c < cols && r < rows) dst[(size_t)c * rows + r] = tile[tx][i];
-  }
-}
-
-int lstm_transpose_launch(const float* src, float* dst, int rows, int cols, hipStream_t stream) {
-  hipLaunchKernelGGL(k_lstm_transpose, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, stream, src, dst, rows, cols);
-  GNNRAG_LAUNCH_CHECK();
-  return 0;
-}
-
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
 
 constexpr int kLstmTC = 4;      // tokens whose input projections share one pass over W_ih
@@ -182,8 +159,8 @@ static int lstm_launch(const float* x, const float* w_ih, const float* w_hh, con
   const int G = 4 * H;
   float* wih_t = (float*)workspace;
   float* whh_t = wih_t + (size_t)E * G;
-  GNNRAG_RC(lstm_transpose_launch(w_ih, wih_t, G, E, stream));
-  GNNRAG_RC(lstm_transpose_launch(w_hh, whh_t, G, H, stream));
+  GNNRAG_RC(transpose_launch(w_ih, wih_t, G, E, stream));
+  GNNRAG_RC(transpose_launch(w_hh, whh_t, G, H, stream));
   LstmArgs a;
   a.x = x; a.wih_t = wih_t; a.whh_t = whh_t; a.b_ih = b_ih; a.b_hh = b_hh; a.h0 = h0; a.c0 = c0;
   a.out = out; a.hn = h_n; a.cn = c_n; a.B = B; a.T = T; a.E = E; a.H = H;

@@ -102,37 +102,6 @@ __global__ __launch_bounds__(1024) void k_lstm_bwd(const LstmBwdArgs a) {
   }
 }
 
-// db[c] = sum over the M rows of dG[., c]: 32 columns x 8 row slices per workgroup, a slice in ascending rows, the
-// slices added in slice order
-__global__ __launch_bounds__(256) void k_lstm_colsum(const float* __restrict__ dG, float* __restrict__ db, int64_t M,
-                                                     int G) {
-  __shared__ float s[8][32];
-  const int cx = threadIdx.x & 31, sl = threadIdx.x >> 5;
-  const int c = blockIdx.x * 32 + cx;
-  const int64_t per = (M + 7) / 8;
-  const int64_t m0 = sl * per, m1 = m0 + per < M ? m0 + per : M;
-  float acc = 0.f;
-  if (c < G)
-    for (int64_t m = m0; m < m1; ++m) acc += dG[m * G + c];
-  s[sl][cx] = acc;
-  __syncthreads();
-  if (sl == 0 && c < G) {
-    float v = s[0][cx];
-#pragma unroll
-    for (int i = 1; i < 8; ++i) v += s[i][cx];
-    db[c] = v;
-  }
-}
-
-// dst [rows, cols] = the first cols columns of src [rows, ld]
-__global__ __launch_bounds__(256) void k_lstm_unpad(const float* __restrict__ src, float* __restrict__ dst, int rows,
-                                                    int cols, int ld) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= rows * cols) return;
-  const int r = i / cols, c = i - r * cols;
-  dst[i] = src[(size_t)r * ld + c];
-}
-
 struct LstmBwdLayout {
   size_t dG, hp, wih_t, cpad, tn, tn_bytes, total;
   int32_t Hp;
@@ -142,16 +111,16 @@ static LstmBwdLayout lstm_bwd_layout(int32_t B, int32_t T, int32_t E, int32_t H)
   LstmBwdLayout l;
   const size_t M = (size_t)B * T, G = 4 * (size_t)H;
   l.Hp = (H + 3) / 4 * 4;
-  size_t off = 0;
-  l.dG = off; off += align_up(M * G * sizeof(float), 256);
-  l.hp = off; off += align_up(M * l.Hp * sizeof(float), 256);
-  l.wih_t = off; off += align_up((size_t)E * G * sizeof(float), 256);
-  l.cpad = off; off += align_up(G * l.Hp * sizeof(float), 256);
+  Carve cv;
+  l.dG = cv.take(M * G * sizeof(float));
+  l.hp = cv.take(M * l.Hp * sizeof(float));
+  l.wih_t = cv.take((size_t)E * G * sizeof(float));
+  l.cpad = cv.take(G * l.Hp * sizeof(float));
   const size_t t1 = gnnrag_gemm_tn_workspace_bytes((int64_t)M, (int32_t)G, E);
   const size_t t2 = gnnrag_gemm_tn_workspace_bytes((int64_t)M, (int32_t)G, l.Hp);
   l.tn_bytes = t1 > t2 ? t1 : t2;
-  l.tn = off; off += align_up(l.tn_bytes, 256);
-  l.total = off;
+  l.tn = cv.take(l.tn_bytes);
+  l.total = cv.off;
   return l;
 }
 
@@ -171,7 +140,7 @@ extern "C" int gnnrag_lstm_backward(const float* x, const float* w_ih, const flo
                                     int32_t H, void* workspace, size_t workspace_bytes, gnnrag_stream_t stream_) {
   if (!x || !w_ih || !w_hh || !out || !dw_ih || !dw_hh || B <= 0 || T <= 0 || E <= 0 || H <= 0) return GNNRAG_E_BADARG;
   if (4 * H > 1024 || (E & 3)) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)x | (uintptr_t)dw_ih | (uintptr_t)workspace) & 15) != 0) return GNNRAG_E_UNSUPPORTED;   // gemm_tn
+  if (!aligned16(x, dw_ih, workspace)) return GNNRAG_E_UNSUPPORTED;   // gemm_tn
   if (!reserve || reserve_bytes < gnnrag_lstm_reserve_bytes(B, T, H)) return GNNRAG_E_WORKSPACE;
   const LstmBwdLayout l = lstm_bwd_layout(B, T, E, H);
   if (!workspace || workspace_bytes < l.total) return GNNRAG_E_WORKSPACE;
@@ -191,20 +160,16 @@ extern "C" int gnnrag_lstm_backward(const float* x, const float* w_ih, const flo
   hipLaunchKernelGGL(k_lstm_bwd, dim3(B), dim3((G + 63) / 64 * 64), 0, stream, a);
   GNNRAG_LAUNCH_CHECK();
   GNNRAG_RC(gnnrag_gemm_tn(dG, x, M, G, E, dw_ih, ws + l.tn, l.tn_bytes, stream_));
-  if (l.Hp == H && ((uintptr_t)dw_hh & 15) == 0) {
-    GNNRAG_RC(gnnrag_gemm_tn(dG, hp, M, G, H, dw_hh, ws + l.tn, l.tn_bytes, stream_));
-  } else {
-    GNNRAG_RC(gnnrag_gemm_tn(dG, hp, M, G, l.Hp, cpad, ws + l.tn, l.tn_bytes, stream_));
-    hipLaunchKernelGGL(k_lstm_unpad, dim3((G * H + 255) / 256), dim3(256), 0, stream, cpad, dw_hh, G, H, l.Hp);
-    GNNRAG_LAUNCH_CHECK();
-  }
+  GNNRAG_RC(gemm_tn_unpadded(dG, hp, M, G, l.Hp, G, H, dw_hh, cpad, ws + l.tn, l.tn_bytes, stream));
   if (dx) {
-    GNNRAG_RC(lstm_transpose_launch(w_ih, wih_t, G, E, stream));
+    GNNRAG_RC(transpose_launch(w_ih, wih_t, G, E, stream));
     GNNRAG_RC(gnnrag_linear(dG, M, G, wih_t, nullptr, nullptr, 0, 0, dx, E, GNNRAG_MATH_FP32, stream_));
   }
   if (db) {
-    hipLaunchKernelGGL(k_lstm_colsum, dim3((G + 31) / 32), dim3(256), 0, stream, dG, db, M, G);
-    GNNRAG_LAUNCH_CHECK();
+    ColsumJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    jobs.src[0] = dG; jobs.dst[0] = db; jobs.rows[0] = M; jobs.ld[0] = G; jobs.cols = G;
+    GNNRAG_RC(colsum_launch(jobs, 1, stream));
   }
   return 0;
 }

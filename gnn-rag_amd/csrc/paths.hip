@@ -95,22 +95,17 @@ struct UgScratch {
 static UgScratch ug_scratch_layout(int64_t F, int32_t B, int32_t N) {
   UgScratch L;
   const size_t n = 2 * (size_t)(F > 0 ? F : 1);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += align_up(bytes, 256);
-    return at;
-  };
-  L.key_in = take(n * 8);
-  L.key_out = take(n * 8);
-  L.val_in = take(n * 4);
-  L.val_out = take(n * 4);
-  L.flag = take(n * 4);
-  L.scan = take(n * 4);
+  Carve cv;
+  L.key_in = cv.take(n * 8);
+  L.key_out = cv.take(n * 8);
+  L.val_in = cv.take(n * 4);
+  L.val_out = cv.take(n * 4);
+  L.flag = cv.take(n * 4);
+  L.scan = cv.take(n * 4);
   const size_t a = ug_sort_temp_bytes(n, 32 + node_bits((size_t)B * (size_t)N)), b = ug_scan_temp_bytes(n);
   L.temp_bytes = a > b ? a : b;
-  L.temp = take(L.temp_bytes);
-  L.total = off;
+  L.temp = cv.take(L.temp_bytes);
+  L.total = cv.off;
   return L;
 }
 
@@ -435,16 +430,11 @@ struct PathWs {
 
 static PathWs path_ws_layout(int32_t B, int32_t N, int32_t S, int32_t C) {
   PathWs L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += align_up(bytes, 256);
-    return at;
-  };
-  L.cnt = take((size_t)B * S * C * 4);
-  L.lev = take((size_t)B * S * N);
-  L.sig = take((size_t)B * S * N * 4);
-  L.total = off;
+  Carve cv;
+  L.cnt = cv.take((size_t)B * S * C * 4);
+  L.lev = cv.take((size_t)B * S * N);
+  L.sig = cv.take((size_t)B * S * N * 4);
+  L.total = cv.off;
   return L;
 }
 

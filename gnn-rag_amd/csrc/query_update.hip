@@ -92,6 +92,7 @@ __device__ __forceinline__ void query_reform_body(const float* __restrict__ q, c
       ar1 += wr1[k] * f;
       ag1 += wg1[k] * f;
     }
+    // wave_sum's tree, the four sums interleaved: four calls give the same bits but another instruction schedule
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       ar0 += __shfl_xor(ar0, o, 64);

@@ -180,11 +180,11 @@ struct QrBwdLayout {
 static QrBwdLayout qr_bwd_layout(int32_t B, int32_t D, int32_t n) {
   QrBwdLayout l;
   const size_t M = (size_t)n * B;
-  size_t off = 0;
-  l.da = off; off += align_up(M * 2 * D * sizeof(float), 256);
-  l.f = off; off += align_up(M * 3 * D * sizeof(float), 256);
-  l.dy = off; off += align_up(M * D * sizeof(float), 256);
-  l.total = off;
+  Carve cv;
+  l.da = cv.take(M * 2 * D * sizeof(float));
+  l.f = cv.take(M * 3 * D * sizeof(float));
+  l.dy = cv.take(M * D * sizeof(float));
+  l.total = cv.off;
   return l;
 }
 
@@ -251,7 +251,7 @@ extern "C" int gnnrag_query_reform_backward(const float* const* q, const float* 
   }
   if (d_ent) {
     const int64_t blocks = dent_blocks;
-    if ((D & 3) == 0 && ((uintptr_t)d_ent & 15) == 0) {
+    if ((D & 3) == 0 && aligned16(d_ent)) {
       hipLaunchKernelGGL(k_qr_dent<true>, dim3((unsigned)blocks), dim3(256), 0, stream, seed_info, a.w_dy, d_ent, rows, N,
                          D, B, n, w.active);
     } else {

@@ -40,12 +40,6 @@ constexpr float kRtMaskOff = 100000000.0f;       // query_update.py:59 (1e8: exa
 
 static_assert(kRtThreads % 64 == 0 && kRtThreads >= 128 && kRtThreads <= 1024, "GNNRAG_RT_THREADS");
 
-__device__ __forceinline__ float rt_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ float rt_dot4(f32x4 x, f32x4 w, float acc) {
   acc = fmaf(x[0], w[0], acc);
   acc = fmaf(x[1], w[1], acc);
@@ -108,18 +102,17 @@ __global__ __launch_bounds__(kRtThreads) void k_rt_pool(const RtPoolArgs p) {
       if (STAGE) xs[t * K4 + j] = v;
       acc = rt_dot4(v, uv[j], acc);
     }
-    acc = rt_wave_sum(acc);
+    acc = wave_sum(acc);
     // the fp32 difference the reference writes: a token keeps s, padding becomes s - 1e8 rounded (multiples of 8)
     if (lane == 0) sc[t] = __fsub_rn(__fadd_rn(acc, c), __fmul_rn(__fsub_rn(1.f, mk[t]), kRtMaskOff));
   }
   __syncthreads();
   float m = -INFINITY;
   for (int t = lane; t < T; t += 64) m = fmaxf(m, sc[t]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  m = wave_max(m);
   float sum = 0.f;
   for (int t = lane; t < T; t += 64) sum += expf(sc[t] - m);
-  sum = rt_wave_sum(sum);
+  sum = wave_sum(sum);
   __syncthreads();                               // every wave has read the scores
   for (int t = tid; t < T; t += kRtThreads) {
     const float al = expf(sc[t] - m) / sum;
@@ -174,7 +167,7 @@ __global__ __launch_bounds__(kRtThreads) void k_rt_bwd(const RtBwdArgs p) {
         if (STAGE) xs[t * K4 + j] = v;
         d = rt_dot4(v, dv[j], d);
       }
-      d = rt_wave_sum(d);
+      d = wave_sum(d);
       if (lane == 0) sd[t] = d;
     }
     __syncthreads();
@@ -204,6 +197,7 @@ __global__ __launch_bounds__(kRtThreads) void k_rt_bwd(const RtBwdArgs p) {
 }
 
 // du[k] = sum of the P partial sums in order: 16 contiguous slices, a slice in ascending p, the slices added in order
+// (not colsum_launch: that one cuts the rows into 8 slices, another summation order)
 __global__ __launch_bounds__(1024) void k_rt_du_reduce(const float* __restrict__ part, float* __restrict__ du, int P,
                                                        int K) {
   __shared__ float s[16][64];
@@ -241,6 +235,7 @@ __global__ __launch_bounds__(256) void k_rt_gcat(const float* __restrict__ g0, c
 
 // column sums of gcat, first level: workgroup (x, y) = 32 columns x the y-th of S row slices; inside, 8 sub-slices in
 // ascending rows, added in order -> cpart[y, Dp]
+// (not colsum_launch: the sub-slice length comes from the nominal slice height rows_per, not from the slice's own rows)
 __global__ __launch_bounds__(256) void k_rt_colsum(const float* __restrict__ gcat, float* __restrict__ cpart, int64_t M,
                                                    int Dp, int64_t rows_per) {
   __shared__ float s[8][32];
@@ -287,11 +282,11 @@ __global__ __launch_bounds__(256) void k_rt_finish(const float* __restrict__ tn,
   if (da) {
     float acc = 0.f;
     for (int k = lane; k < K; k += 64) acc = fmaf(W[(size_t)d * K + k], du[k], acc);
-    acc = rt_wave_sum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) da[d] = acc;
   }
   if (db) {
-    const float v = rt_wave_sum(lane < S ? cpart[(size_t)lane * Dp + d] : 0.f);
+    const float v = wave_sum(lane < S ? cpart[(size_t)lane * Dp + d] : 0.f);
     if (lane == 0) db[d] = v;
   }
 }
@@ -304,10 +299,10 @@ struct RtFwdLayout { size_t uc, xbar, total; };
 
 static RtFwdLayout rt_fwd_layout(int64_t R, int32_t K, int32_t n_dir) {
   RtFwdLayout l;
-  size_t off = 0;
-  l.uc = off; off += align_up(((size_t)K + 1) * sizeof(float), 256);
-  l.xbar = off; off += align_up((size_t)n_dir * R * K * sizeof(float), 256);
-  l.total = off;
+  Carve cv;
+  l.uc = cv.take(((size_t)K + 1) * sizeof(float));
+  l.xbar = cv.take((size_t)n_dir * R * K * sizeof(float));
+  l.total = cv.off;
   return l;
 }
 
@@ -320,17 +315,17 @@ static RtBwdLayout rt_bwd_layout(int64_t R, int32_t K, int32_t D, int32_t n_dir)
   RtBwdLayout l;
   const size_t M = (size_t)n_dir * R;
   l.Dp = (D + 3) / 4 * 4;
-  size_t off = 0;
-  l.wt = off; off += align_up((size_t)K * D * sizeof(float), 256);
-  l.dxbar = off; off += align_up(M * K * sizeof(float), 256);
-  l.gcat = off; off += align_up(M * l.Dp * sizeof(float), 256);
-  l.part = off; off += align_up((size_t)n_dir * kRtBwdGrid * K * sizeof(float), 256);
-  l.du = off; off += align_up((size_t)K * sizeof(float), 256);
-  l.tn_out = off; off += align_up((size_t)l.Dp * K * sizeof(float), 256);
+  Carve cv;
+  l.wt = cv.take((size_t)K * D * sizeof(float));
+  l.dxbar = cv.take(M * K * sizeof(float));
+  l.gcat = cv.take(M * l.Dp * sizeof(float));
+  l.part = cv.take((size_t)n_dir * kRtBwdGrid * K * sizeof(float));
+  l.du = cv.take((size_t)K * sizeof(float));
+  l.tn_out = cv.take((size_t)l.Dp * K * sizeof(float));
   l.tn_bytes = gnnrag_gemm_tn_workspace_bytes((int64_t)M, l.Dp, K);
-  l.tn = off; off += align_up(l.tn_bytes, 256);
-  l.cpart = off; off += align_up((size_t)kRtColSlices * l.Dp * sizeof(float), 256);
-  l.total = off;
+  l.tn = cv.take(l.tn_bytes);
+  l.cpart = cv.take((size_t)kRtColSlices * l.Dp * sizeof(float));
+  l.total = cv.off;
   return l;
 }
 
@@ -357,7 +352,7 @@ extern "C" int gnnrag_rel_text_pool(const float* X_fwd, const float* X_inv, cons
       K <= 0 || D <= 0)
     return GNNRAG_E_BADARG;
   if (!rt_shape_ok(R, T, K, D)) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)X_fwd | (uintptr_t)X_inv | (uintptr_t)xbar | (uintptr_t)ws) & 15) != 0) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(X_fwd, X_inv, xbar, ws)) return GNNRAG_E_UNSUPPORTED;
   const int n_dir = X_inv ? 2 : 1;
   const RtFwdLayout l = rt_fwd_layout(R, K, n_dir);
   if (!ws || ws_bytes < l.total) return GNNRAG_E_WORKSPACE;
@@ -397,8 +392,7 @@ extern "C" int gnnrag_rel_text_pool_backward(const float* X_fwd, const float* X_
   if (!X_fwd || !W || !a || !xbar || !alpha || (g_inv && !X_inv) || R <= 0 || T <= 0 || K <= 0 || D <= 0)
     return GNNRAG_E_BADARG;
   if (!rt_shape_ok(R, T, K, D)) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)X_fwd | (uintptr_t)X_inv | (uintptr_t)xbar | (uintptr_t)dW | (uintptr_t)ws) & 15) != 0)
-    return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(X_fwd, X_inv, xbar, dW, ws)) return GNNRAG_E_UNSUPPORTED;
   const int n_dir = X_inv ? 2 : 1;
   const RtBwdLayout l = rt_bwd_layout(R, K, D, n_dir);
   if (!ws || ws_bytes < l.total) return GNNRAG_E_WORKSPACE;
@@ -442,7 +436,7 @@ extern "C" int gnnrag_rel_text_pool_backward(const float* X_fwd, const float* X_
     GNNRAG_LAUNCH_CHECK();
   }
   if (need_du) {
-    GNNRAG_RC(lstm_transpose_launch(W, wt, D, K, stream));
+    GNNRAG_RC(transpose_launch(W, wt, D, K, stream));
     if (n_act == 2) {
       GNNRAG_RC(gnnrag_linear_pair(g_fwd, g_inv, R, D, wt, nullptr, nullptr, nullptr, 0, dxbar, dxbar + RK, K,
                                    GNNRAG_MATH_FP32, stream_));

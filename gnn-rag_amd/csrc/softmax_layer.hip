@@ -30,6 +30,7 @@ __global__ __launch_bounds__(1024) void k_masked_softmax(const float* __restrict
   } else {
     for (int i = threadIdx.x; i < N; i += 1024) m = fmaxf(m, s[i]);
   }
+  // wave_max's tree, spelled out: the call leaves the bits alone but moves the register allocation of ITEMS = 8
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
   if (lane == 0) red[wave] = m;
@@ -53,8 +54,7 @@ __global__ __launch_bounds__(1024) void k_masked_softmax(const float* __restrict
   } else {
     for (int i = threadIdx.x; i < N; i += 1024) sum += expf(s[i] - m);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  sum = wave_sum(sum);
   if (lane == 0) red[wave] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -103,8 +103,7 @@ __global__ __launch_bounds__(1024) void k_softmax_pairs(const float* __restrict_
     v[k] = i < N ? s[i] : -INFINITY;
     m = fmaxf(m, v[k]);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  m = wave_max(m);
   if (lane == 0) red[wave] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -121,8 +120,7 @@ __global__ __launch_bounds__(1024) void k_softmax_pairs(const float* __restrict_
     v[k] = expf(v[k] - m);
     sum += v[k];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
+  sum = wave_sum(sum);
   if (lane == 0) red[wave] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -201,26 +199,25 @@ static bool path_ok(int32_t path) {
 
 static LayerWs layer_ws(const gnnrag_csr* csr, int32_t D, int32_t I) {
   LayerWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+  Carve cv;
   const size_t BN = (size_t)csr->B * csr->N;
-  w.T_fwd = take((size_t)2 * csr->R1 * D * sizeof(float));          // [2][R1][D]: forward, inverse
+  w.T_fwd = cv.take((size_t)2 * csr->R1 * D * sizeof(float));          // [2][R1][D]: forward, inverse
   w.T_inv = w.T_fwd + (size_t)csr->R1 * D * sizeof(float);
   // bf16 planes of relu(+-T) for the V form of the relation tables (one layer), where that kernel's shapes apply
-  w.planes = take(tables_vq_shape_ok(D, I) ? tables_vq_planes_bytes(csr->R1) : 0);
+  w.planes = cv.take(tables_vq_shape_ok(D, I) ? tables_vq_planes_bytes(csr->R1) : 0);
   // the two paths never run in the same call: their big buffers share one region
   const size_t a_bytes = BN * 2 * I * D * sizeof(float);
   const size_t p_bytes = align_up((size_t)2 * (csr->rel_total > 0 ? csr->rel_total : 1) * D * sizeof(float), 256);
   const size_t n_bytes = (BN + 1) * D * sizeof(float);              // + the zero row frontier layers read for rows off the frontier
-  const size_t big = take(a_bytes > p_bytes + n_bytes ? a_bytes : p_bytes + n_bytes);
+  const size_t big = cv.take(a_bytes > p_bytes + n_bytes ? a_bytes : p_bytes + n_bytes);
   w.agg = big;
   w.P = big;
   w.nbr = big + p_bytes;
   w.partial_bytes = gnnrag_aggregate_workspace_bytes(csr, D, I);
-  w.partial = take(w.partial_bytes);
+  w.partial = cv.take(w.partial_bytes);
   w.fws_bytes = gnnrag_frontier_workspace_bytes(csr);
-  w.fws = take(w.fws_bytes);
-  w.total = off;
+  w.fws = cv.take(w.fws_bytes);
+  w.total = cv.off;
   return w;
 }
 
@@ -317,8 +314,7 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     const bool one_dir = only >= 0 && gnnrag_aggregate_fused_variant(csr, D) != GNNRAG_WALK_L2_GATHER;
     // the frontier kernels issue 16-byte loads / stores on ins, W, T, P (workspace) and the node rows: a misaligned view
     // takes the regular fused path below, whose launchers check alignment themselves
-    const bool fr_aligned = ((((uintptr_t)ins | (uintptr_t)W_e2e | (uintptr_t)T_fwd | (uintptr_t)T_inv | (uintptr_t)P |
-                               (uintptr_t)nbr | (uintptr_t)dist) & 15) == 0) && csr->N > 0;
+    const bool fr_aligned = aligned16(ins, W_e2e, T_fwd, T_inv, P, nbr, dist) && csr->N > 0;
     const bool frontier_form = seed_prior && only < 0 && fr_aligned && gnnrag_frontier_supported(csr, D) && csr->rel_total > 0;
     if (frontier_form) {
       // The caller says `dist` is a seed distribution (first layer of a ReaRev iteration, rearev.py:208): only the

@@ -898,7 +898,7 @@ int update_b3_launch_f(const float* h, const float* nbr, const uint8_t* add_flag
                        const float* w_s, const float* b_s, const float* mask, float* h_out, float* score, int64_t BN,
                        int32_t D, int32_t ldw, hipStream_t stream, bool score_zeroed) {
   if (!update_b3_shape_ok(BN, D, ldw)) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)h | (uintptr_t)nbr | (uintptr_t)W | (uintptr_t)h_out) & 15) != 0) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(h, nbr, W, h_out)) return GNNRAG_E_UNSUPPORTED;
   UpdB3Args a;
   memset(&a, 0, sizeof(a));
   a.A = h; a.W = W; a.bias = b; a.add = nbr; a.w_s = w_s; a.b_s = b_s; a.mask = mask; a.C = h_out; a.score = score;
@@ -942,7 +942,7 @@ int tables_vq_launch(const gnnrag_csr* csr, const void* planes, const float* ins
 int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
                        int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream) {
   if (!tables_vq_shape_ok(D, I) || csr->rel_total < 1024 || only_dir > 1) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)planes | (uintptr_t)ins | (uintptr_t)W | (uintptr_t)P) & 15) != 0) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(planes, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
   VqArgs a;
   memset(&a, 0, sizeof(a));
   a.planes = (const unsigned char*)planes; a.ins = ins; a.W = W; a.P = P;
@@ -981,8 +981,7 @@ int tables_b3_launch(const gnnrag_csr* csr, const float* T_fwd, const float* T_i
   // shapes of the kernel: D a multiple of 8 (a lane's 8 consecutive k), at most 2 x 7 column tiles, 4-byte offsets
   // that keep float4 accesses aligned, enough rows to fill the chip
   if (D % 8 || (D + 31) / 32 != kTabNKB || (D + 15) / 16 != 13 || csr->rel_total < 1024) return GNNRAG_E_UNSUPPORTED;
-  if ((((uintptr_t)T_fwd | (uintptr_t)T_inv | (uintptr_t)ins | (uintptr_t)W | (uintptr_t)P) & 15) != 0)
-    return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(T_fwd, T_inv, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
   TabArgs a;
   memset(&a, 0, sizeof(a));
   a.T[0] = T_fwd; a.T[1] = T_inv; a.ins = ins; a.W = W; a.P = P;

@@ -5,8 +5,8 @@
 //   len_b = sum_n teacher (0 -> 1)     t = teacher / len_b     l_b = label_valid_b sum_n (t > 0 ? t (log t - log(pred + 1e-8)) : 0)
 //   loss  = (sum_b l_b) / B            d_pred = -g label_valid_b t / (pred + 1e-8) / B
 //
-//   k_kl_fwd   one workgroup per question: len_b, then l_b, each in one fixed order (thread-strided sums, xor tree, the
-//              waves in order: the pattern of k_lt_gs).  len_b goes to the caller's reserve, l_b to the workspace.
+//   k_kl_fwd   one workgroup per question: len_b, then l_b, each in one fixed order (thread-strided sums, then
+//              block_sum).  len_b goes to the caller's reserve, l_b to the workspace.
 //   k_kl_sum   one thread adds the l_b in ascending b and divides by B.
 //   k_kl_bwd   one streaming pass; a thread owns the columns 4 c .. 4 c + 3 of a row, as one float4 where N % 4 == 0 and the
 //              bases are 16-byte aligned, else element by element: the same values either way.  EVERY element is written.
@@ -28,35 +28,6 @@ constexpr int kKlBwdThreads = 256;
 constexpr int kKlBwdGrid = 2048;         // 256 CUs x 8 workgroups: the cap of the backward's grid (grid-strided beyond)
 constexpr float kKlEps = 1e-8f;          // base_model.py:197
 
-__device__ __forceinline__ float tt_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ int tt_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the workgroup's sum in one fixed order: xor tree inside a wave, then the 16 waves in order; every thread gets it
-__device__ __forceinline__ float tt_block_sum(float s, float* red, float* bcast) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  s = tt_wave_sum(s);
-  if (lane == 0) red[wave] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < 16; ++k) t += red[k];
-    *bcast = t;
-  }
-  __syncthreads();
-  const float r = *bcast;
-  __syncthreads();                       // red / bcast may be reused
-  return r;
-}
-
 __global__ __launch_bounds__(1024) void k_kl_fwd(const float* __restrict__ pred, const float* __restrict__ teacher,
                                                  const float* __restrict__ label_valid, int N, float* __restrict__ len_out,
                                                  float* __restrict__ l_out) {
@@ -67,14 +38,14 @@ __global__ __launch_bounds__(1024) void k_kl_fwd(const float* __restrict__ pred,
   const float* __restrict__ t = teacher + off;
   float s = 0.f;
   for (int i = threadIdx.x; i < N; i += 1024) s += t[i];
-  float len = tt_block_sum(s, red, &bcast);
+  float len = block_sum(s, red, &bcast);
   if (len == 0.f) len = 1.f;                                               // base_model.py:195
   float acc = 0.f;
   for (int i = threadIdx.x; i < N; i += 1024) {
     const float th = __fdiv_rn(t[i], len);
     if (th > 0.f) acc += th * (logf(th) - logf(p[i] + kKlEps));            // KLDivLoss: a zero target contributes 0
   }
-  const float l = tt_block_sum(acc, red, &bcast);
+  const float l = block_sum(acc, red, &bcast);
   if (threadIdx.x == 0) {
     len_out[blockIdx.x] = len;
     l_out[blockIdx.x] = label_valid[blockIdx.x] * l;
@@ -185,8 +156,8 @@ __global__ __launch_bounds__(1024) void k_train_metrics(const float* __restrict_
       best_i = oi;
     }
   }
-  n_ans = tt_wave_sum_i(n_ans);
-  kept = tt_wave_sum_i(kept);
+  n_ans = wave_sum(n_ans);
+  kept = wave_sum(kept);
   if (lane == 0) {
     s_val[wave] = best;
     s_idx[wave] = best_i;
@@ -212,7 +183,7 @@ __global__ __launch_bounds__(1024) void k_train_metrics(const float* __restrict_
   int cor = 0;
   for (int j = tid; j < n_ret; j += 1024)
     if (ans[topp_key_slot(keys[j])] > 0.f) ++cor;                          // :230: the slot's own answer flag
-  cor = tt_wave_sum_i(cor);
+  cor = wave_sum(cor);
   if (lane == 0) s_cor[wave] = cor;
   __syncthreads();
   if (tid == 0) {
@@ -249,8 +220,6 @@ __global__ __launch_bounds__(1024) void k_train_metrics(const float* __restrict_
   }
 }
 
-static inline bool tt_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace gnnrag
 
 using namespace gnnrag;
@@ -281,7 +250,7 @@ extern "C" int gnnrag_kl_loss_backward(const float* g_loss, const float* pred, c
   const int64_t total = (int64_t)B * ((N + 3) / 4);
   const int64_t blocks = (total + kKlBwdThreads - 1) / kKlBwdThreads;
   const int grid = (int)(blocks < kKlBwdGrid ? blocks : kKlBwdGrid);
-  const bool vec = (N & 3) == 0 && tt_al16(pred) && tt_al16(teacher) && tt_al16(d_pred);
+  const bool vec = (N & 3) == 0 && aligned16(pred, teacher, d_pred);
   if (vec)
     hipLaunchKernelGGL(k_kl_bwd<true>, dim3(grid), dim3(kKlBwdThreads), 0, stream, g_loss, pred, teacher, label_valid,
                        reserve, B, N, d_pred);
