@@ -187,6 +187,13 @@ SIGNATURES = {
     "gnnrag_bert_encode_ex": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
                                         C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
                               [_VP, _VP, C.c_size_t, C.c_int32, _VP]),
+    # the same encoder in training mode: the caller's dropout masks fused into the forward (additive to ABI 16)
+    "gnnrag_bert_keep_hidden_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_bert_keep_att_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_bert_attention_drop": (C.c_int, [_VP] + [C.c_int32] * 4 + [_VP, _VP, C.c_float, _VP, _VP]),
+    "gnnrag_bert_encode_train": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
+                                           C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
+                                 [_VP, C.c_float, _VP, C.c_float, _VP, _VP, C.c_size_t, C.c_int32, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),

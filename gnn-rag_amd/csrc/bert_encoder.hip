@@ -18,6 +18,17 @@
 //   * MPNet adds a relative-position bias to the scaled scores of every layer: s(i, j) += rel_bias[head][j - i + T - 1],
 //     one table [heads, 2T-1] for all layers (k_bert_attention<DH, true>).
 //
+// Training-mode forward (gnnrag_bert_encode_train): the encoder is frozen, so there is no backward, but transformers draws
+// dropout at four sites when the module is in training mode.  The caller brings the keep bytes (one per element, != 0
+// keeps) and each site is fused into the launch that already produces the value:
+//   embedding output           k_bert_embed_ln<.., DROP>     LN(...) * (keep ? scale : 0)
+//   attention probabilities    k_bert_attention<.., DROP>    p_j * (keep ? scale : 0) behind the row's sum: not renormalised
+//   W_o and W_f outputs        k_bert_drop_add_ln            LN(d * (keep ? scale : 0) + x); the product is a gnnrag_linear
+//                                                            WITHOUT the residual (it is added behind the dropout)
+// The product with 0 (not a select) keeps a non-finite value NaN as transformers' x * mask does.  DROP is a compile-time
+// switch: the `DROP = false` instantiations take the two arguments last and never load them - their instructions are those
+// of the kernels before the switch existed.
+//
 // Eight launches per layer.  fp32 throughout, no atomics, every reduction in an order the shape alone fixes (a wave's
 // __shfl_xor tree, keys in ascending order), nothing allocated, nothing waits for the stream: safe under capture, a second
 // call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
@@ -33,12 +44,21 @@ namespace gnnrag {
 constexpr int kBertMaxT = 128;       // keys per question: two per lane
 constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
 
+// the multipliers of the 4 keep bytes in one 32-bit word (little endian: byte e belongs to element e)
+__device__ __forceinline__ f32x4 bert_keep4(uint32_t w, float scale) {
+  return (f32x4){(w & 0xffu) ? scale : 0.f, (w & 0xff00u) ? scale : 0.f, (w & 0xff0000u) ? scale : 0.f,
+                 (w & 0xff000000u) ? scale : 0.f};
+}
+
 // LayerNorm of one row by one wave: biased variance, two passes (mean, then sum (x - mean)^2); `load(i)` returns the
 // i-th float4 of the row (called three times per element: the row is L2 / L1 resident).  dst may be the row `load` reads:
 // a lane writes only the elements it has read itself, after both reductions.
-template <typename Load>
+// DROP: the result is multiplied by scale where the row's keep byte is not 0, by 0 elsewhere (keep: the row's H bytes,
+// 4-byte aligned; a lane reads the 4 bytes of its float4 as one word).
+template <bool DROP = false, typename Load>
 __device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__ g, const float* __restrict__ bt,
-                                            float eps, int H4, int lane, float* dst) {
+                                            float eps, int H4, int lane, float* dst,
+                                            const uint8_t* __restrict__ keep = nullptr, float scale = 0.f) {
   const float inv_h = 1.f / (float)(H4 * 4);
   float s = 0.f;
   for (int i = lane; i < H4; i += 64) {
@@ -59,6 +79,7 @@ __device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * rstd * gg[e] + bb[e];
+    if (DROP) o = o * bert_keep4(((const uint32_t*)keep)[i], scale);
     ((f32x4*)dst)[i] = o;
   }
 }
@@ -69,14 +90,16 @@ __device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__
 // a non-pad token, pad_id for a pad; an id outside the vocabulary counts as non-pad.  A position outside [0, max_pos)
 // reads nothing either: its row is NaN (the entry point's shape rule excludes it; this is the kernel's own bound).
 // TYPE = false: no token-type term, type_emb is not read.
-template <bool IDPOS, bool TYPE>
+// DROP: the LayerNorm result goes through the keep bytes of plane [M, H]; a NaN row stays NaN whatever they are.
+template <bool IDPOS, bool TYPE, bool DROP>
 __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_t* __restrict__ ids,
                                                                     const float* __restrict__ word_emb, int vocab,
                                                                     const float* __restrict__ pos_emb, int max_pos,
                                                                     const float* __restrict__ type_emb, int pad_id,
                                                                     const float* __restrict__ g,
                                                                     const float* __restrict__ bt, float eps, int M, int T,
-                                                                    int H4, float* __restrict__ out) {
+                                                                    int H4, float* __restrict__ out,
+                                                                    const uint8_t* __restrict__ keep, float scale) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
   if (row >= M) return;
@@ -97,11 +120,12 @@ __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_
   }
   const f32x4* w = (const f32x4*)(word_emb + (size_t)id * H4 * 4);
   const f32x4* p = (const f32x4*)(pos_emb + (size_t)pos * H4 * 4);
+  const uint8_t* kr = DROP ? keep + (size_t)row * H4 * 4 : nullptr;
   if (TYPE) {
     const f32x4* ty = (const f32x4*)type_emb;
-    bert_ln_row([&](int i) { return (w[i] + ty[i]) + p[i]; }, g, bt, eps, H4, lane, dst);
+    bert_ln_row<DROP>([&](int i) { return (w[i] + ty[i]) + p[i]; }, g, bt, eps, H4, lane, dst, kr, scale);
   } else {
-    bert_ln_row([&](int i) { return w[i] + p[i]; }, g, bt, eps, H4, lane, dst);
+    bert_ln_row<DROP>([&](int i) { return w[i] + p[i]; }, g, bt, eps, H4, lane, dst, kr, scale);
   }
 }
 
@@ -114,6 +138,23 @@ __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_add_ln(const float* i
   if (row >= M) return;
   const f32x4* src = (const f32x4*)(in + (size_t)row * H4 * 4);
   bert_ln_row([&](int i) { return src[i]; }, g, bt, eps, H4, lane, out + (size_t)row * H4 * 4);
+}
+
+// out[row] = LN(d[row] * (keep ? scale : 0) + out[row]): d = dense(x) + bias WITHOUT the residual, out holds the residual and
+// receives the result (a lane writes only the elements it has read itself, after both reductions; d is another buffer).
+// keep [M, H] bytes, 4-byte aligned.  A NaN in d or in the residual makes the row NaN whatever the keep bytes are.
+__global__ __launch_bounds__(64 * kBertLnRows) void k_bert_drop_add_ln(const float* __restrict__ d,
+                                                                       const uint8_t* __restrict__ keep, float scale,
+                                                                       const float* __restrict__ g,
+                                                                       const float* __restrict__ bt, float eps, int M,
+                                                                       int H4, float* out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const f32x4* src = (const f32x4*)(d + (size_t)row * H4 * 4);
+  const uint32_t* kr = (const uint32_t*)(keep + (size_t)row * H4 * 4);
+  float* dst = out + (size_t)row * H4 * 4;
+  bert_ln_row([&](int i) { return src[i] * bert_keep4(kr[i], scale) + ((const f32x4*)dst)[i]; }, g, bt, eps, H4, lane, dst);
 }
 
 __device__ __forceinline__ float bert_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
@@ -146,10 +187,14 @@ __device__ __forceinline__ float bert_opaque(float v) {
 // come from the fixed wave tree, then lanes run over d and add p[j] v[j][d] for j = 0 .. T - 1 in order.  No mask.
 // BIAS: the head's row of rel_bias [heads, 2T-1] sits in LDS behind V (2T floats reserved) and the score of (t, j) is
 // (q . k) scale + bias[j - t + T - 1]; without it rel_bias is not read and the LDS layout is the one above.
-template <int DH, bool BIAS>
+// DROP: keep [B, heads, T, T] bytes (query row t, key column j; any alignment).  After the row's maximum and sum the
+// probability of key j is multiplied by scale where keep[b, h, t, j] != 0 and by 0 elsewhere; the row is NOT renormalised
+// (transformers drops the probabilities behind the softmax).  A row whose keys are all dropped gives a zero context row.
+template <int DH, bool BIAS, bool DROP>
 __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict__ qkv,
                                                          const float* __restrict__ rel_bias, int T, int heads,
-                                                         float* __restrict__ ctx) {
+                                                         float* __restrict__ ctx, const uint8_t* __restrict__ keep,
+                                                         float keep_scale) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int LD = DH + 1;
   const int b = blockIdx.x / heads, h = blockIdx.x % heads;
@@ -207,8 +252,14 @@ __global__ __launch_bounds__(1024) void k_bert_attention(const float* __restrict
     const float m = wave_max(fmaxf(s0, s1));
     const float e0 = j0 < T ? expf(s0 - m) : 0.f, e1 = j1 < T ? expf(s1 - m) : 0.f;
     const float sum = wave_sum(e0 + e1);
-    if (j0 < T) ps[j0] = e0 / sum;
-    if (j1 < T) ps[j1] = e1 / sum;
+    if (DROP) {
+      const uint8_t* kr = keep + ((size_t)blockIdx.x * T + t) * T;     // blockIdx.x = b heads + h
+      if (j0 < T) ps[j0] = (e0 / sum) * (kr[j0] ? keep_scale : 0.f);
+      if (j1 < T) ps[j1] = (e1 / sum) * (kr[j1] ? keep_scale : 0.f);
+    } else {
+      if (j0 < T) ps[j0] = e0 / sum;
+      if (j1 < T) ps[j1] = e1 / sum;
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (lane < DH) {
@@ -226,29 +277,37 @@ static inline size_t bert_att_lds_bytes(int T, int dh, int threads, bool bias) {
          sizeof(float);
 }
 
-template <int DH, bool BIAS>
-static int bert_attention_launch_as(const float* qkv, const float* rel_bias, int32_t B, int32_t T, int32_t heads,
-                                    float* ctx, hipStream_t stream) {
+template <int DH, bool BIAS, bool DROP>
+static int bert_attention_launch_as(const float* qkv, const float* rel_bias, const uint8_t* keep, float keep_scale,
+                                    int32_t B, int32_t T, int32_t heads, float* ctx, hipStream_t stream) {
   const int threads = GNNRAG_BERT_ATT_THREADS;
   const size_t lds = bert_att_lds_bytes(T, DH, threads, BIAS);
+  const dim3 grid((unsigned)((int64_t)B * heads));
   if (lds > 64 * 1024) {
     static DeviceMask raised{0};
-    GNNRAG_RC(raise_lds_cap(k_bert_attention<DH, BIAS>, raised));
+    GNNRAG_RC(raise_lds_cap(k_bert_attention<DH, BIAS, DROP>, raised));
   }
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_attention<DH, BIAS>), dim3((unsigned)((int64_t)B * heads)), dim3(threads), lds,
-                     stream, qkv, rel_bias, T, heads, ctx);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_attention<DH, BIAS, DROP>), grid, dim3(threads), lds, stream, qkv, rel_bias, T,
+                     heads, ctx, keep, keep_scale);
   GNNRAG_LAUNCH_CHECK();
   return 0;
 }
 
-// rel_bias NULL: no bias (the kernel never sees the pointer)
-static int bert_attention_launch(const float* qkv, const float* rel_bias, int32_t B, int32_t T, int32_t heads, int32_t dh,
-                                 float* ctx, hipStream_t stream) {
-  if (dh == 32)
-    return rel_bias ? bert_attention_launch_as<32, true>(qkv, rel_bias, B, T, heads, ctx, stream)
-                    : bert_attention_launch_as<32, false>(qkv, nullptr, B, T, heads, ctx, stream);
-  return rel_bias ? bert_attention_launch_as<64, true>(qkv, rel_bias, B, T, heads, ctx, stream)
-                  : bert_attention_launch_as<64, false>(qkv, nullptr, B, T, heads, ctx, stream);
+template <int DH>
+static int bert_attention_launch_dh(const float* qkv, const float* rel_bias, const uint8_t* keep, float keep_scale, int32_t B,
+                                    int32_t T, int32_t heads, float* ctx, hipStream_t stream) {
+  if (keep)
+    return rel_bias ? bert_attention_launch_as<DH, true, true>(qkv, rel_bias, keep, keep_scale, B, T, heads, ctx, stream)
+                    : bert_attention_launch_as<DH, false, true>(qkv, nullptr, keep, keep_scale, B, T, heads, ctx, stream);
+  return rel_bias ? bert_attention_launch_as<DH, true, false>(qkv, rel_bias, nullptr, 0.f, B, T, heads, ctx, stream)
+                  : bert_attention_launch_as<DH, false, false>(qkv, nullptr, nullptr, 0.f, B, T, heads, ctx, stream);
+}
+
+// rel_bias NULL: no bias; keep NULL: no dropout (the kernel never sees a NULL pointer's argument)
+static int bert_attention_launch(const float* qkv, const float* rel_bias, const uint8_t* keep, float keep_scale, int32_t B,
+                                 int32_t T, int32_t heads, int32_t dh, float* ctx, hipStream_t stream) {
+  return dh == 32 ? bert_attention_launch_dh<32>(qkv, rel_bias, keep, keep_scale, B, T, heads, ctx, stream)
+                  : bert_attention_launch_dh<64>(qkv, rel_bias, keep, keep_scale, B, T, heads, ctx, stream);
 }
 
 static inline bool bert_att_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {
@@ -281,13 +340,32 @@ extern "C" size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, i
   return bert_ws((int64_t)B * T, H, I).total;
 }
 
-extern "C" int gnnrag_bert_attention_bias(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
-                                          const float* rel_bias, float* ctx, gnnrag_stream_t stream) {
+// the scale of a mask that is given: finite and > 0 (1 / (1 - p) of a p < 1)
+static inline bool bert_scale_ok(const uint8_t* keep, float scale) { return !keep || (std::isfinite(scale) && scale > 0.f); }
+
+extern "C" size_t gnnrag_bert_keep_hidden_bytes(int32_t L, int32_t B, int32_t T, int32_t H) {
+  if (L < 0 || B <= 0 || T <= 0 || H <= 0) return 0;      // L = 0 is legal: plane 0 alone
+  return (size_t)(1 + 2 * (int64_t)L) * B * T * H;
+}
+
+extern "C" size_t gnnrag_bert_keep_att_bytes(int32_t L, int32_t B, int32_t T, int32_t heads) {
+  if (L <= 0 || B <= 0 || T <= 0 || heads <= 0) return 0;
+  return (size_t)L * B * heads * T * T;
+}
+
+extern "C" int gnnrag_bert_attention_drop(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                                          const float* rel_bias, const uint8_t* keep, float scale, float* ctx,
+                                          gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
   if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
-  if (!qkv || !ctx) return GNNRAG_E_BADARG;
+  if (!qkv || !ctx || !bert_scale_ok(keep, scale)) return GNNRAG_E_BADARG;
   if (!aligned16(qkv, ctx, rel_bias)) return GNNRAG_E_UNSUPPORTED;
-  return bert_attention_launch(qkv, rel_bias, B, T, heads, dh, ctx, (hipStream_t)stream);
+  return bert_attention_launch(qkv, rel_bias, keep, scale, B, T, heads, dh, ctx, (hipStream_t)stream);
+}
+
+extern "C" int gnnrag_bert_attention_bias(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                                          const float* rel_bias, float* ctx, gnnrag_stream_t stream) {
+  return gnnrag_bert_attention_drop(qkv, B, T, heads, dh, rel_bias, nullptr, 0.f, ctx, stream);
 }
 
 extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh, float* ctx,
@@ -295,12 +373,15 @@ extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int
   return gnnrag_bert_attention_bias(qkv, B, T, heads, dh, nullptr, ctx, stream);
 }
 
-// both entry points; need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type term"
+// all entry points; need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type term".
+// keep_hidden / keep_att NULL: that dropout site keeps the inference sequence (its scale is not read); both NULL is the
+// inference call, launch for launch.
 static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
                            int32_t max_pos, const float* type_emb, bool need_type, int32_t pad_id, const float* rel_bias,
                            const float* ln_g, const float* ln_b, float ln_eps, int32_t L, const gnnrag_bert_layer* layers,
-                           int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes,
-                           int32_t math, gnnrag_stream_t stream) {
+                           int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I, const uint8_t* keep_hidden,
+                           float scale_hidden, const uint8_t* keep_att, float scale_att, float* out, void* ws,
+                           size_t ws_bytes, int32_t math, gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L < 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
   if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
   // the shape rules first: they are answered whatever the pointers are
@@ -314,8 +395,10 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   if (L > 0 && ws_bytes < w.total) return GNNRAG_E_UNSUPPORTED;
   if (!ids || !word_emb || !pos_emb || (need_type && !type_emb) || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
     return GNNRAG_E_BADARG;
+  if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
+  // keep_hidden is read a 32-bit word per float4; keep_att byte by byte (any alignment)
   if (!aligned16(word_emb, pos_emb, type_emb, rel_bias, ln_g, ln_b, out) || ((uintptr_t)ids & 7) ||
-      (L > 0 && !aligned16(ws)))
+      (L > 0 && !aligned16(ws)) || ((uintptr_t)keep_hidden & 3))
     return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) {
     const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
@@ -330,9 +413,15 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   hipStream_t st = (hipStream_t)stream;
   const int H4 = H / 4;
   const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
-#define GNNRAG_EMBED_LN(IDPOS, TYPE)                                                                                 \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE>), ln_grid, ln_block, 0, st, ids, word_emb, vocab,  \
-                     pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out)
+#define GNNRAG_EMBED_LN(IDPOS, TYPE)                                                                                    \
+  if (keep_hidden)                                                                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, true>), ln_grid, ln_block, 0, st, ids, word_emb,    \
+                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out, keep_hidden,  \
+                       scale_hidden);                                                                                   \
+  else                                                                                                                  \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, false>), ln_grid, ln_block, 0, st, ids, word_emb,   \
+                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out,               \
+                       (const uint8_t*)nullptr, 0.f)
   if (pad_id >= 0 && type_emb) {
     GNNRAG_EMBED_LN(true, true);
   } else if (pad_id >= 0) {
@@ -353,21 +442,48 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   const size_t n_ffn = (size_t)M * I;
   const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
   const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
+  const size_t plane = (size_t)M * H, att_plane = (size_t)B * heads * T * T;
+  // x = LN(dense(a) + b + x).  Inference: the residual rides in the product's epilogue.  With hidden dropout the product
+  // goes without it and the LayerNorm launch drops, adds the residual and normalises (plane: the site's keep bytes).
+  auto residual_block = [&](const float* a, int32_t K, const float* W, const float* b, const float* g, const float* bt,
+                            const uint8_t* keep) -> int {
+    if (keep) {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, nullptr, 0, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_drop_add_ln, ln_grid, ln_block, 0, st, sum, keep, scale_hidden, g, bt, ln_eps, (int)M, H4,
+                         out);
+    } else {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, out, M, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, g, bt, ln_eps, (int)M, H4, out);
+    }
+    GNNRAG_LAUNCH_CHECK();
+    return 0;
+  };
   for (int l = 0; l < L; ++l) {
     const gnnrag_bert_layer& p = layers[l];
     GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
-    GNNRAG_RC(bert_attention_launch(qkv, rel_bias, B, T, heads, dh, ctx, st));
-    GNNRAG_RC(gnnrag_linear(ctx, M, H, p.W_o, p.b_o, out, M, 0, sum, H, math, stream));
-    hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, p.ln1_g, p.ln1_b, ln_eps, (int)M, H4, out);
-    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(bert_attention_launch(qkv, rel_bias, keep_att ? keep_att + (size_t)l * att_plane : nullptr, scale_att, B, T,
+                                    heads, dh, ctx, st));
+    GNNRAG_RC(residual_block(ctx, H, p.W_o, p.b_o, p.ln1_g, p.ln1_b,
+                             keep_hidden ? keep_hidden + (size_t)(1 + 2 * l) * plane : nullptr));
     GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, ffn, I, math, stream));
     hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, ffn, n_ffn);
     GNNRAG_LAUNCH_CHECK();
-    GNNRAG_RC(gnnrag_linear(ffn, M, I, p.W_f, p.b_f, out, M, 0, sum, H, math, stream));
-    hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, p.ln2_g, p.ln2_b, ln_eps, (int)M, H4, out);
-    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(residual_block(ffn, I, p.W_f, p.b_f, p.ln2_g, p.ln2_b,
+                             keep_hidden ? keep_hidden + (size_t)(2 + 2 * l) * plane : nullptr));
   }
   return 0;
+}
+
+extern "C" int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                        int32_t max_pos, const float* type_emb, int32_t pad_id, const float* rel_bias,
+                                        const float* ln_g, const float* ln_b, float ln_eps, int32_t L,
+                                        const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads,
+                                        int32_t I, const uint8_t* keep_hidden, float scale_hidden, const uint8_t* keep_att,
+                                        float scale_att, float* out, void* ws, size_t ws_bytes, int32_t math,
+                                        gnnrag_stream_t stream) {
+  return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
+                         layers, B, T, H, heads, I, keep_hidden, scale_hidden, keep_att, scale_att, out, ws, ws_bytes, math,
+                         stream);
 }
 
 extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
@@ -376,7 +492,7 @@ extern "C" int gnnrag_bert_encode(const int64_t* ids, const float* word_emb, int
                                   int32_t heads, int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
                                   gnnrag_stream_t stream) {
   return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, true, -1, nullptr, ln_g, ln_b, ln_eps, L, layers,
-                         B, T, H, heads, I, out, ws, ws_bytes, math, stream);
+                         B, T, H, heads, I, nullptr, 0.f, nullptr, 0.f, out, ws, ws_bytes, math, stream);
 }
 
 extern "C" int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
@@ -386,5 +502,5 @@ extern "C" int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, 
                                      int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
                                      gnnrag_stream_t stream) {
   return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
-                         layers, B, T, H, heads, I, out, ws, ws_bytes, math, stream);
+                         layers, B, T, H, heads, I, nullptr, 0.f, nullptr, 0.f, out, ws, ws_bytes, math, stream);
 }

@@ -28,8 +28,16 @@ unchanged:
 * all parameters are contiguous fp32 CUDA tensors and the kernels take the shape (``ops.bert_encode_supported``; with
   positions from the ids also ``T + pad_id <= max_position_embeddings - 1``, where transformers itself would raise);
 * nothing needs a gradient: grad mode is off, or no LM parameter requires grad;
-* dropout is inert: the module is in eval mode, or both dropout probabilities are 0 (``Trainer_KBQA`` runs a frozen LM in
-  training mode with dropout 0.1: those calls fall through).
+* dropout is inert: the module is in eval mode, or both dropout probabilities are 0 - or the training-mode forward is
+  switched on (next paragraph).
+
+``Trainer_KBQA`` calls ``model.train()``, which puts the frozen LM into training mode with transformers' dropout 0.1:
+two encodes per step.  With ``GNNRAG_HIP_LM_TRAIN=1`` (read at every call; unset or ``0`` is off, and those calls fall
+through with "dropout is active") such a call runs on ``ops.bert_encode_train`` when the class's ``GNNRAG_HIP_LM`` rule is
+met, both probabilities are below 1 and every other rule above holds: :func:`draw_keep` draws the keep bytes of the four
+dropout sites from torch's generator of the device and the kernels multiply them in as ``float32(1 / (1 - p))``.  These are
+not ``F.dropout``'s draws: comparable loss curve, not equal draws.  Eval-mode calls and calls with both probabilities 0
+stay on the inference path, bit for bit.
 
 An eligible call returns a ``BaseModelOutput`` whose ``[0]`` is ``last_hidden_state``; the pooler is not computed (the
 reference never reads it).  The packed query / key / value weight and bias of every layer are kept on the state object,
@@ -51,6 +59,7 @@ DEFAULT = "1"        # GNNRAG_HIP_LM for BertModel when unset (DESIGN.md section
 # measured at the 768-wide, 12-layer shape: 3-4 x less host time, but more stream time than transformers at B = 1 and
 # B = 64 (DESIGN.md section 8 f-6 keeps the numbers), so by the rule they stay off
 DEFAULT_ON = ("BertModel",)
+TRAIN_DEFAULT = "0"  # GNNRAG_HIP_LM_TRAIN when unset: off (DESIGN.md section 8 f-6 has the rule for a later flip)
 REL_BUCKETS = 32                # MPNetEncoder.compute_position_bias passes its default, whatever the configuration says
 
 # what differs between the classes: where positions come from, the token-type term, the attention bias, the names
@@ -68,6 +77,36 @@ def enabled(arch: str = "BertModel") -> bool:
     if v is None:
         return arch in DEFAULT_ON and DEFAULT != "0"
     return v != "0"
+
+
+def train_enabled() -> bool:
+    """Whether a training-mode call with active dropout may use the library (``GNNRAG_HIP_LM_TRAIN``, read at every
+    call)."""
+    return os.environ.get("GNNRAG_HIP_LM_TRAIN", TRAIN_DEFAULT) not in ("0", "")
+
+
+def draw_keep(L: int, B: int, T: int, H: int, heads: int, p_hidden: float, p_att: float, device):
+    """The keep bytes of one training-mode encode: ``(keep_hidden, keep_att)`` of the shapes of ``ops.bert_keep_shapes``,
+    uint8, each byte 1 with probability ``1 - p`` (``bernoulli_`` on torch's generator of ``device``); ``None`` for a site
+    whose ``p`` is 0 (and for the attention site of an encoder without layers).  One draw launch when the two
+    probabilities are equal - the two buffers are views of one - two otherwise.  Comparable loss curve, not equal draws:
+    these are not the numbers ``F.dropout`` would have drawn."""
+    shape_h, shape_a = ops.bert_keep_shapes(L, B, T, H, heads)
+    n_h = shape_h[0] * shape_h[1] * shape_h[2] if p_hidden != 0.0 else 0
+    n_a = shape_a[0] * shape_a[1] * shape_a[2] * shape_a[3] * shape_a[4] if p_att != 0.0 else 0
+
+    def one(n, p):
+        return torch.empty(n, dtype=torch.uint8, device=device).bernoulli_(1.0 - float(p))
+
+    if n_h and n_a and float(p_hidden) == float(p_att):
+        both = one(n_h + n_a, p_hidden)         # the hidden planes first: they stay 4-byte aligned (H % 4 == 0)
+        return both[:n_h].view(shape_h), both[n_h:].view(shape_a)
+    return (one(n_h, p_hidden).view(shape_h) if n_h else None), (one(n_a, p_att).view(shape_a) if n_a else None)
+
+
+def _scale(p: float) -> float:
+    """float32(1 / (1 - p)): what the kernels multiply a kept element by."""
+    return float(torch.tensor(1.0 / (1.0 - float(p)), dtype=torch.float32))
 
 
 def _f32_cuda_contig(t) -> bool:
@@ -94,6 +133,7 @@ class _LmPatch:
         self.key, self.packed = None, None      # the packed W_qkv / b_qkv of every layer and what they were made from
         self.bias_key, self.bias = None, {}     # MPNet: T -> the bias table, and the weight they were made from
         self.hip_calls = 0                      # eligible calls served by the library (tests, tools)
+        self.hip_train_calls = 0                # those of them that ran the training-mode forward
 
     # -- eligibility ----------------------------------------------------------------------------------------------
     def pad_id(self):
@@ -102,6 +142,11 @@ class _LmPatch:
             return None
         pad = getattr(self.enc.embeddings, "padding_idx", None)
         return int(pad) if isinstance(pad, int) and not isinstance(pad, bool) else -1
+
+    def dropout_active(self) -> bool:
+        cfg = self.enc.config
+        return bool(self.enc.training and (float(cfg.hidden_dropout_prob) != 0.0 or
+                                           float(cfg.attention_probs_dropout_prob) != 0.0))
 
     def refusal(self, args, kwargs):
         """None when the call runs on the library, else the first rule (of the module docstring) it does not meet."""
@@ -126,8 +171,11 @@ class _LmPatch:
         params = list(enc.parameters())
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             return "a gradient is needed"
-        if enc.training and (float(cfg.hidden_dropout_prob) != 0.0 or float(cfg.attention_probs_dropout_prob) != 0.0):
-            return "dropout is active"
+        if self.dropout_active():
+            if not train_enabled():
+                return "dropout is active"
+            if not (float(cfg.hidden_dropout_prob) < 1.0 and float(cfg.attention_probs_dropout_prob) < 1.0):
+                return "a dropout probability of 1"
         if not ops.bert_encode_supported(int(ids.shape[1]), int(cfg.hidden_size), int(cfg.num_attention_heads),
                                          int(cfg.intermediate_size), int(cfg.max_position_embeddings), pad_id=pad):
             return "a shape the kernels do not take"
@@ -196,11 +244,19 @@ class _LmPatch:
         ids = args[0] if args else kwargs["input_ids"]
         emb, cfg = enc.embeddings, enc.config
         type_emb = emb.token_type_embeddings.weight if _ARCH[self.arch]["token_type"] else None
+        top = (ids, emb.word_embeddings.weight, emb.position_embeddings.weight, type_emb, emb.LayerNorm.weight,
+               emb.LayerNorm.bias, float(cfg.layer_norm_eps), self.layers(), int(cfg.num_attention_heads))
+        rest = dict(I=int(cfg.intermediate_size), pad_id=self.pad_id(), rel_bias=self.rel_bias(int(ids.shape[1])))
         with torch.no_grad():
-            hidden = ops.bert_encode(ids, emb.word_embeddings.weight, emb.position_embeddings.weight, type_emb,
-                                     emb.LayerNorm.weight, emb.LayerNorm.bias, float(cfg.layer_norm_eps), self.layers(),
-                                     int(cfg.num_attention_heads), I=int(cfg.intermediate_size), pad_id=self.pad_id(),
-                                     rel_bias=self.rel_bias(int(ids.shape[1])))
+            if self.dropout_active():
+                p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
+                B, T = int(ids.shape[0]), int(ids.shape[1])
+                keep_h, keep_a = draw_keep(len(top[7]), B, T, int(cfg.hidden_size), top[8], p_h, p_a, ids.device)
+                hidden = ops.bert_encode_train(*top, keep_hidden=keep_h, scale_hidden=_scale(p_h), keep_att=keep_a,
+                                               scale_att=_scale(p_a), **rest)
+                self.hip_train_calls += 1
+            else:
+                hidden = ops.bert_encode(*top, **rest)
         self.hip_calls += 1
         return BaseModelOutput(last_hidden_state=hidden)
 

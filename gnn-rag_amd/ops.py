@@ -1634,6 +1634,40 @@ def bert_attention(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int,
     return ctx
 
 
+def _keep_scale(scale: float, what: str) -> float:
+    s = float(scale)
+    if not (s > 0.0 and s != float("inf")):
+        raise ValueError("%s must be finite and > 0" % what)
+    return s
+
+
+def bert_keep_shapes(L: int, B: int, T: int, H: int, heads: int):
+    """The shapes of the two keep buffers of ``bert_encode_train``: ``keep_hidden`` (1 + 2L, B*T, H) - plane 0 the
+    embedding output, plane 1 + 2l layer l's attention output projection, plane 2 + 2l its FFN output projection - and
+    ``keep_att`` (L, B, heads, T, T) (query row, key column); uint8, != 0 keeps.  Their sizes are the library's
+    ``gnnrag_bert_keep_hidden_bytes`` / ``gnnrag_bert_keep_att_bytes``."""
+    return (1 + 2 * L, B * T, H), (L, B, heads, T, T)
+
+
+def bert_attention_drop(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int, keep: torch.Tensor, scale: float,
+                        rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gnnrag_bert_attention_drop``: ``bert_attention`` with dropout on the probabilities.  ``keep`` [B, heads, T, T]
+    uint8 (query row, key column): behind the softmax the probability of key j is multiplied by ``scale`` where the byte is
+    not 0 and by 0 elsewhere; the row is not renormalised (as transformers drops them)."""
+    lib = _lib.load()
+    H = heads * dh
+    qkv = _chk(qkv, "qkv", shape=(B * T, 3 * H))
+    keep = _chk(keep, "keep", dtype=torch.uint8, shape=(B, heads, T, T))
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
+    ctx = _buf((B * T, H), torch.float32, qkv.device, "bert_attention_drop: ctx")
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.gnnrag_bert_attention_drop(qkv.data_ptr(), B, T, heads, dh, _ptr(rel_bias), keep.data_ptr(),
+                                                  _keep_scale(scale, "scale"), ctx.data_ptr(), _stream()),
+                   "gnnrag_bert_attention_drop")
+    return ctx
+
+
 def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int, I: Optional[int] = None,
                 math: Optional[int] = None, *, pad_id: Optional[int] = None,
                 rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1646,6 +1680,25 @@ def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers
     ``type_emb=None`` (no token-type term), ``pad_id`` (positions from the ids, as RoBERTa and MPNet count them) and
     ``rel_bias`` [heads, 2T-1] (MPNet's relative attention bias, every layer) go through ``gnnrag_bert_encode_ex``; with
     the defaults the call is the one it has always been."""
+    return _bert_encode("bert_encode", None, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math,
+                        pad_id, rel_bias)
+
+
+def bert_encode_train(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int,
+                      I: Optional[int] = None, math: Optional[int] = None, *, pad_id: Optional[int] = None,
+                      rel_bias: Optional[torch.Tensor] = None, keep_hidden: Optional[torch.Tensor] = None,
+                      scale_hidden: float = 1.0, keep_att: Optional[torch.Tensor] = None,
+                      scale_att: float = 1.0) -> torch.Tensor:
+    """``gnnrag_bert_encode_train``: ``bert_encode`` as a module in training mode runs it - forward only, the encoder is
+    frozen.  ``keep_hidden`` / ``keep_att``: uint8 tensors of the shapes of ``bert_keep_shapes`` (!= 0 keeps; the caller
+    draws them), multiplied in as ``scale_*`` (1 / (1 - p)) at transformers' four dropout sites inside the launches that
+    produce the values.  ``None`` leaves that site as in inference; both ``None`` gives the bits of ``bert_encode``."""
+    return _bert_encode("bert_encode_train", (keep_hidden, scale_hidden, keep_att, scale_att), ids, word_emb, pos_emb,
+                        type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias)
+
+
+def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias):
+    """The shared body of ``bert_encode`` (``drop`` None) and ``bert_encode_train`` (``drop``: the two masks and scales)."""
     lib = _lib.load()
     ids = _chk(ids, "ids", dtype=torch.int64)
     if ids.dim() != 2:
@@ -1678,11 +1731,27 @@ def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers
             keep.append(t)
             setattr(arr[l], name, t.data_ptr())
     dev = ids.device
-    out = _buf((B, T, H), torch.float32, dev, "bert_encode: out")
+    if drop is not None:
+        keep_hidden, scale_hidden, keep_att, scale_att = drop
+        shape_hidden, shape_att = bert_keep_shapes(L, B, T, H, heads)
+        if keep_hidden is not None:
+            keep_hidden = _chk(keep_hidden, "keep_hidden", dtype=torch.uint8, shape=shape_hidden)
+            scale_hidden = _keep_scale(scale_hidden, "scale_hidden")
+        if keep_att is not None:
+            keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
+            scale_att = _keep_scale(scale_att, "scale_att")
+    out = _buf((B, T, H), torch.float32, dev, role + ": out")
     nws = int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)) if L else 0
-    ws = _buf((max(nws, 1),), torch.uint8, dev, "bert_encode: workspace")
+    ws = _buf((max(nws, 1),), torch.uint8, dev, role + ": workspace")
     with torch.cuda.device(dev):
-        if type_emb is not None and pad < 0 and rel_bias is None:
+        if drop is not None:
+            _lib.check(lib.gnnrag_bert_encode_train(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
+                                                    pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
+                                                    ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I,
+                                                    _ptr(keep_hidden), float(scale_hidden), _ptr(keep_att),
+                                                    float(scale_att), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    _math(math), _stream()), "gnnrag_bert_encode_train")
+        elif type_emb is not None and pad < 0 and rel_bias is None:
             _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
                                               pos_emb.shape[0], type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(),
                                               float(eps), L, arr, B, T, H, heads, I, out.data_ptr(), ws.data_ptr(),

@@ -818,7 +818,7 @@ int gnnrag_instructions_backward(const float* hidden, const float* node, const f
  * One more GNNRAG_E_UNSUPPORTED rule, answered with the shape rules: pad_id >= 0 and T + pad_id > max_pos - 1 (a full row
  * reaches position T + pad_id; transformers raises there too).  A rel_bias that is not 16-byte aligned is UNSUPPORTED.
  * Workspace, launches per layer, capture safety, "no allocation" and "nothing waits" are as above.  Attention masks, T5
- * (RMS norm, unscaled scores, its own bias rule), dropout and gradients remain outside. */
+ * (RMS norm, unscaled scores, its own bias rule) and gradients remain outside; dropout: gnnrag_bert_encode_train below. */
 typedef struct gnnrag_bert_layer { const float *W_qkv, *b_qkv, *W_o, *b_o, *ln1_g, *ln1_b,
                                                *W_i, *b_i, *W_f, *b_f, *ln2_g, *ln2_b; } gnnrag_bert_layer;
 size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I);
@@ -837,6 +837,45 @@ int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, int32_t voc
                           float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
                           int32_t heads, int32_t I, float* out /* [B,T,H] */, void* ws, size_t ws_bytes, int32_t math,
                           gnnrag_stream_t stream);
+
+/* ---- The same encoder in training mode: forward only (additive to ABI 16) -----------------------
+ * Trainer_KBQA calls model.train(), which puts the frozen LM into training mode too: transformers then applies dropout
+ * (hidden_dropout_prob, attention_probs_dropout_prob) at four sites of the forward.  The LM is frozen, so nothing needs a
+ * backward.  The caller draws the keep bytes (one uint8 per element, != 0 keeps; read-only, caller-owned) and every site is
+ * part of the launch that already produces the value - a layer stays 8 launches, the embedding 1:
+ *   embedding output:          x = LN(...) * m                          m = keep ? scale_hidden : 0
+ *   attention probabilities:   p_j = softmax_j(...) * (keep ? scale_att : 0); NOT renormalised; a row whose keys are all
+ *                              dropped gives a zero context row
+ *   W_o / W_f outputs:         x = LN((a W^T + b) * m + x)              the residual is added behind the dropout
+ * The product with 0 keeps a non-finite value NaN, as transformers' `x * mask` does: a row whose id or position is out of
+ * range is NaN in every element whatever its keep bytes are.
+ * keep_hidden: 1 + 2L planes of [B T, H] bytes, row-major.  Plane 0: the embedding output; plane 1 + 2l: layer l's attention
+ *              output projection; plane 2 + 2l: layer l's FFN output projection.  With L = 0 only plane 0 is read.
+ *              gnnrag_bert_keep_hidden_bytes(L, B, T, H) = (1 + 2L) B T H (0 for L < 0 or a size <= 0).
+ * keep_att:    [L, B, heads, T, T], query row i, key column j.  gnnrag_bert_keep_att_bytes(L, B, T, heads) = L B heads T T
+ *              (0 for any argument <= 0).
+ * keep_hidden NULL: no hidden dropout - those sites run the inference sequence (the residual in the product's epilogue) and
+ * scale_hidden is not read; keep_att NULL likewise.  Both NULL enqueues exactly what gnnrag_bert_encode_ex enqueues: equal
+ * bits.  The workspace is that of gnnrag_bert_workspace_bytes, unchanged.  No atomics, no allocation, nothing waits for the
+ * stream, safe under capture; the same masks give the same bits, and a question's rows depend on its own ids and its own
+ * slices of the masks only.
+ * Rules, in the order of gnnrag_bert_encode_ex: sizes (BADARG), the shape rules whatever the pointers are (UNSUPPORTED), NULL
+ * pointers (BADARG), then: a scale of a given mask that is not finite or not > 0 is GNNRAG_E_BADARG; a keep_hidden that is
+ * not 4-byte aligned is GNNRAG_E_UNSUPPORTED (a lane reads the 4 bytes of its float4 as one word); keep_att may have any
+ * alignment.
+ * gnnrag_bert_attention_drop is the attention step alone with one [B, heads, T, T] mask (keep NULL: gnnrag_bert_attention_bias). */
+size_t gnnrag_bert_keep_hidden_bytes(int32_t L, int32_t B, int32_t T, int32_t H);
+size_t gnnrag_bert_keep_att_bytes(int32_t L, int32_t B, int32_t T, int32_t heads);
+int gnnrag_bert_attention_drop(const float* qkv, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                               const float* rel_bias /* [heads,2T-1] or NULL */, const uint8_t* keep /* [B,heads,T,T] */,
+                               float scale, float* ctx, gnnrag_stream_t stream);
+int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                             int32_t max_pos, const float* type_emb /* or NULL */, int32_t pad_id, const float* rel_bias,
+                             const float* ln_g, const float* ln_b, float ln_eps, int32_t L,
+                             const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
+                             const uint8_t* keep_hidden /* or NULL */, float scale_hidden,
+                             const uint8_t* keep_att /* or NULL */, float scale_att, float* out /* [B,T,H] */, void* ws,
+                             size_t ws_bytes, int32_t math, gnnrag_stream_t stream);
 
 /* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
  * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):

@@ -5,6 +5,7 @@
     python tools/time_bert_encoder.py [--arch bert|roberta|mpnet] [--iters 20] [--warm 5] [--rounds 2]
                                       [--out profiles/bert_encoder_time.jsonl]
     python tools/time_bert_encoder.py --kernel [--libs 256=,64=gnn-rag_amd/lib/exp_bertatt64.so,...]
+    python tools/time_bert_encoder.py --train [--arch bert|roberta|mpnet]
 
 * the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
   tests/bert_oracle.py - the real all-MiniLM-L6-v2 weights are not needed for a timing) in eval mode, ``enc(ids)[0]`` on a
@@ -20,6 +21,11 @@
   the two LayerNorms and the GELU;
 * a whole evaluation forward of a ``BERTInstruction`` ReaRev model is NOT measured here: the reference's ``--lm sbert``
   loader tokenises its data with the hub's tokenizer, which cannot be built offline (recorded as unmeasured).
+
+``--train``: the same encoder in TRAINING mode at transformers' dropout 0.1, as ``Trainer_KBQA`` runs a frozen LM:
+``GNNRAG_HIP_LM=1`` in both legs, ``GNNRAG_HIP_LM_TRAIN`` off (transformers' own forward) and on (``draw_keep`` and
+``gnnrag_bert_encode_train``), each in a process of its own; the same shapes, host enqueue and stream time; no per-kernel
+split.  The draws differ between the legs (and between iterations), so there is no checksum to compare.
 
 ``--kernel``: ``gnnrag_bert_attention`` alone, 20 calls per graph, per library given in ``--libs`` as ``label=path``
 (``GNNRAG_LIB``; empty path = the built library): how the workgroup size (``-DGNNRAG_BERT_ATT_THREADS``,
@@ -104,8 +110,8 @@ def child_encode(a):
     torch, bo, dev = _setup()
     import numpy as np
     from gnnrag_amd import ops
-    from gnnrag_amd.modules.question_encoding.lm_encoder import enabled, patch_lm_encoder
-    on = enabled(ARCHS[a.arch])
+    from gnnrag_amd.modules.question_encoding.lm_encoder import enabled, patch_lm_encoder, train_enabled
+    on = train_enabled() if a.train else enabled(ARCHS[a.arch])
     if a.arch == "bert":
         shape, n_layers, vocab = bo.MINILM, L, VOCAB
         m32 = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)[0]
@@ -119,7 +125,7 @@ def child_encode(a):
                 w = rs.standard_normal(tuple(p.shape)) * (0.05 if p.dim() >= 2 else 0.1)
                 p.copy_(torch.from_numpy((1.0 + w if name.endswith("LayerNorm.weight") else w).astype(np.float32)))
         m32 = model
-    enc = m32.to(dev).eval()
+    enc = m32.to(dev).train(a.train)
     for p in enc.parameters():
         p.requires_grad_(False)
     patch_lm_encoder(_Holder(enc))
@@ -136,15 +142,18 @@ def child_encode(a):
             with torch.no_grad():
                 out[:] = [enc(x)[0]]
 
-        before = patch.hip_calls
+        before, before_train = patch.hip_calls, patch.hip_train_calls
         host, ev, host_min, ev_min = _measure(torch, encode, ids, a.warm)
-        rec = {"what": "encode", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
+        rec = {"what": "encode_train" if a.train else "encode", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
                "H": shape["H"], "I": shape["I"],
                "host_ms": host, "event_ms": ev, "host_ms_min": host_min, "event_ms_min": ev_min, "iters": a.iters,
                "warm": a.warm, "hip_calls_per_encode": (patch.hip_calls - before) / len(ids),
                "checksum": float(out[0].double().square().sum()), "device": torch.cuda.get_device_name(0)}
+        if a.train:
+            rec["dropout"] = float(enc.config.hidden_dropout_prob)
+            rec["hip_train_calls_per_encode"] = (patch.hip_train_calls - before_train) / len(ids)
         print(TAG + json.dumps(rec), flush=True)
-        if not on or a.arch != "bert":
+        if not on or a.arch != "bert" or a.train:
             continue
         # the split of the HIP leg
         P = bo.layer_params(enc)
@@ -205,6 +214,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--arch", choices=sorted(ARCHS), default="bert")
     ap.add_argument("--kernel", action="store_true")
+    ap.add_argument("--train", action="store_true", help="training mode at dropout 0.1: GNNRAG_HIP_LM_TRAIN off / on")
     ap.add_argument("--libs", default="256=")
     ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "bert_encoder_time.jsonl"))
@@ -213,7 +223,7 @@ def main():
     a = ap.parse_args()
     if a.child:
         return {"encode": child_encode, "kernel": child_kernel}[a.child](a)
-    common = ["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch]
+    common = ["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch] + (["--train"] if a.train else [])
     lines = []
     if a.kernel:
         for spec in a.libs.split(","):
@@ -224,7 +234,8 @@ def main():
         for rnd in range(a.rounds):
             for switch in ("0", "1"):
                 before = len(lines)
-                _spawn(["--child", "encode"] + common, {"GNNRAG_HIP_LM": switch}, lines, a.limit)
+                env = {"GNNRAG_HIP_LM": "1", "GNNRAG_HIP_LM_TRAIN": switch} if a.train else {"GNNRAG_HIP_LM": switch}
+                _spawn(["--child", "encode"] + common, env, lines, a.limit)
                 for rec in lines[before:]:
                     rec["round"] = rnd
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
