@@ -48,32 +48,38 @@ def _deps():
     return d
 
 
-def build_variant(name: str, defines: dict, verbose: bool = False) -> str:
-    """Experiment builds: lib/exp_<name>.so compiled with extra -D switches (tools/tune_variants.py)."""
-    os.makedirs(LIBDIR, exist_ok=True)
+def _compile_link(objdir: str, out: str, extra=(), tag: str = "", verbose: bool = False) -> None:
+    """One object per source under objdir (at most 8 hipcc at a time), linked into out."""
     hipcc = _hipcc()
-    objdir = os.path.join(LIBDIR, "obj_" + name)
     os.makedirs(objdir, exist_ok=True)
-    # "__flags__": extra compiler flags of the variant (e.g. ["-fno-slp-vectorize"]); everything else is a -D switch
-    extra = list(defines.get("__flags__", [])) + ["-D%s=%s" % kv for kv in defines.items() if not kv[0].startswith("__")]
 
     def cc(src):
         obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        r = subprocess.run([hipcc] + FLAGS + extra + ["-c", os.path.join(CSRC, src), "-o", obj],
-                           capture_output=True, text=True)
+        cmd = [hipcc] + FLAGS + list(extra) + ["-c", os.path.join(CSRC, src), "-o", obj]
+        r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError("hipcc failed for %s (%s):\n%s" % (src, name, r.stderr[-4000:]))
+            raise RuntimeError("hipcc failed for %s%s:\n%s\n%s" % (src, tag, " ".join(cmd), r.stderr[-8000:]))
+        if verbose and r.stderr.strip():
+            sys.stderr.write(r.stderr)
         return obj
 
     with cf.ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
         objs = list(ex.map(cc, SOURCES))
-    out = os.path.join(LIBDIR, "exp_%s.so" % name)
-    r = subprocess.run([hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-pthread", "-o", out] + objs,
-                       capture_output=True, text=True)
+    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-pthread", "-o", out] + objs
+    r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError("link failed (%s):\n%s" % (name, r.stderr[-4000:]))
+        raise RuntimeError("link failed%s:\n%s\n%s" % (tag, " ".join(cmd), r.stderr[-8000:]))
     if verbose:
         print("built", out)
+
+
+def build_variant(name: str, defines: dict, verbose: bool = False) -> str:
+    """Experiment builds: lib/exp_<name>.so compiled with extra -D switches (tools/tune_variants.py)."""
+    os.makedirs(LIBDIR, exist_ok=True)
+    # "__flags__": extra compiler flags of the variant (e.g. ["-fno-slp-vectorize"]); everything else is a -D switch
+    extra = list(defines.get("__flags__", [])) + ["-D%s=%s" % kv for kv in defines.items() if not kv[0].startswith("__")]
+    out = os.path.join(LIBDIR, "exp_%s.so" % name)
+    _compile_link(os.path.join(LIBDIR, "obj_" + name), out, extra, " (%s)" % name, verbose)
     return out
 
 
@@ -83,30 +89,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
     dig = _digest(_deps())
     if not force and os.path.exists(LIB) and os.path.exists(stamp) and open(stamp).read().strip() == dig:
         return LIB
-    hipcc = _hipcc()
-    objdir = os.path.join(LIBDIR, "obj")
-    os.makedirs(objdir, exist_ok=True)
-
-    def cc(src):
-        obj = os.path.join(objdir, src.replace(".hip", ".o"))
-        cmd = [hipcc] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, " ".join(cmd), r.stderr[-8000:]))
-        if verbose and r.stderr.strip():
-            sys.stderr.write(r.stderr)
-        return obj
-
-    with cf.ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
-        objs = list(ex.map(cc, SOURCES))
-    cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-pthread", "-o", LIB] + objs
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("link failed:\n%s\n%s" % (" ".join(cmd), r.stderr[-8000:]))
+    _compile_link(os.path.join(LIBDIR, "obj"), LIB, verbose=verbose)
     with open(stamp, "w") as f:
         f.write(dig)
-    if verbose:
-        print("built", LIB)
     return LIB
 
 

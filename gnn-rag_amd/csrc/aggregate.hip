@@ -35,24 +35,11 @@
 //    facts.  The FUSED walk takes them as a dense hub-by-relation product instead when the hub rows
 //    are in relation order (k_hub_weights / k_hub_dense / k_hub_finish below).
 #include <cstdlib>
-#include <type_traits>
 
 #include "gnnrag_common.h"
 
-#ifndef GNNRAG_REASON_SLICE
-#define GNNRAG_REASON_SLICE 0    // unfused aggregation through LDS table slices when the tables fit.  Measured (C2):
-                                 // dense prior 258 vs 281 us, seed prior 202 vs 138 us - its 64-byte output pieces
-                                 // (4 per node and slice) lose to the gather walk's full 3200-byte rows, so it is off
-#endif
-
-#ifndef GNNRAG_SLICE_WIDE
-#define GNNRAG_SLICE_WIDE 1         // LDS walk: 32-column slices for questions whose tables allow two of them per CU
-#endif
 #ifndef GNNRAG_SLICE_WIDE_LDS_KB
-#define GNNRAG_SLICE_WIDE_LDS_KB 79   // ... as long as two wide workgroups fit one CU's 160 KB
-#endif
-#ifndef GNNRAG_SLICE_HALFSTEP
-#define GNNRAG_SLICE_HALFSTEP 1     // LDS walk: facts 4..7 of a step are skipped when no node of the set has them (-2.5 us)
+#define GNNRAG_SLICE_WIDE_LDS_KB 79   // LDS walk: 32-column slices as long as two wide workgroups fit one CU's 160 KB
 #endif
 #ifndef GNNRAG_SLICE_SPLIT_TAIL
 #define GNNRAG_SLICE_SPLIT_TAIL 1   // LDS walk: work items of the last, partial round of workgroup slots are cut in two
@@ -457,12 +444,6 @@ __global__ __launch_bounds__(256) void k_walk_light(const WalkArgs a) {
 // merged runs 681, one step in flight instead of two 662 (50 registers: 8 waves per SIMD); a packed form with 5 facts
 // per four loads (slot k = 64 i + lane -> fact k / 50, piece k % 50, partial sums through LDS) 657 against 655: the
 // number of load instructions is not what bounds the gather, the 6.5 GB that pass through L1 are (DESIGN A.7).
-#ifndef GNNRAG_LIGHT_QUAD
-#define GNNRAG_LIGHT_QUAD 1       // 0: k_walk_light for every shape
-#endif
-#ifndef GNNRAG_QUAD_MERGED
-#define GNNRAG_QUAD_MERGED 1      // both directions of a node as one run of the merged record stream
-#endif
 #ifndef GNNRAG_QUAD_STEPS
 #define GNNRAG_QUAD_STEPS 1       // steps (4 facts each) whose table-row loads are in flight together
 #endif
@@ -751,14 +732,8 @@ __global__ __launch_bounds__(256) void k_heavy_reduce(const WalkArgs a, int na) 
 //                  streamed once per 16 hubs in coalesced pieces instead of gathered row by row;
 //   k_hub_finish   one workgroup per hub: row += dense result + the row's boundary records in chunk order.
 // Every sum has a fixed order: deterministic.  Needs the hub rows in relation order (structures of this library).
-#ifndef GNNRAG_HUB_DENSE
-#define GNNRAG_HUB_DENSE 1
-#endif
 #ifndef GNNRAG_HUB_W_GRID
 #define GNNRAG_HUB_W_GRID 2048   // workgroups (4 waves, a 256-fact chunk per wave and turn) of k_hub_weights per direction
-#endif
-#ifndef GNNRAG_HUB_U
-#define GNNRAG_HUB_U 0           // k_hub_dense: groups of 16 relations per register stage (0: 2, and 4 for a single hub tile)
 #endif
 #ifndef GNNRAG_HUB_KS_MAX
 #define GNNRAG_HUB_KS_MAX 8      // relation ranges per question (one k_hub_dense workgroup each) at batches of <= 32
@@ -918,7 +893,7 @@ __device__ __forceinline__ void hub_dense_tiles(const WalkArgs& a, int ks, int d
   // The kernel is latency bound (the MFMAs of a range are ~15 us of its ~80): two register stages, the loads of the
   // next U relation groups are requested before the MFMAs of the current ones.  The stages are two distinct objects
   // and the loop is written out twice - a rotated stage would be a register copy of a load in flight, which waits for it.
-  constexpr int U = GNNRAG_HUB_U ? (MT == 1 ? 2 * GNNRAG_HUB_U : GNNRAG_HUB_U) : (MT == 1 ? 4 : 2);
+  constexpr int U = MT == 1 ? 4 : 2;      // groups of 16 relations per register stage
   struct Stage {
     f32x4 av[U][MT];
     f32x2 bv[U][4];
@@ -1083,12 +1058,6 @@ __global__ __launch_bounds__(1024) void k_hub_finish(const WalkArgs a) {
 // shares them with width-4 shuffles.  Node sets are handed out by an LDS ticket so a set with a
 // hub does not hold up its wave's other sets.  All slice workgroups of a question run on one
 // XCD (workgroup b -> XCD b % 8), so their partial-line writes to out[] merge in that L2.
-#ifndef GNNRAG_SLICE_MERGED
-#define GNNRAG_SLICE_MERGED 1      // fused LDS walk over merged rows (both directions of a node in one loop)
-#endif
-#ifndef GNNRAG_SLICE_BL_GROUP
-#define GNNRAG_SLICE_BL_GROUP 1
-#endif
 constexpr int kSliceW = 16;                 // floats per slice (4 lanes x float4)
 #ifndef GNNRAG_SLICE_THREADS
 #define GNNRAG_SLICE_THREADS 1024     // threads per LDS-walk workgroup (two workgroups per CU either way: the table slices fill its LDS)
@@ -1205,15 +1174,12 @@ __device__ __forceinline__ int quad_bcast(int v) {
   return __builtin_amdgcn_mov_dpp(v, K * 0x55, 0xf, 0xf, true);
 }
 
-// Per-lane accumulators of the LDS walk.  REASON: NI float4 (one per instruction) per direction, relu(t * q_i)
-// applied per fact, 16-column slices.  FUSED: both directions summed; NI = number of 16-column groups of the
-// slice a lane owns (NI = 2: 32-column slices - half as many workgroups re-walk the question's facts; used
-// when a question's relation tables are small enough for two 32-column slices per CU).
-template <int MODE, int NI> struct SliceAcc {
+// Per-lane accumulators of the LDS walk: both directions summed.  NI = number of 16-column groups of the slice a
+// lane owns (NI = 2: 32-column slices - half as many workgroups re-walk the question's facts; used when a
+// question's relation tables are small enough for two 32-column slices per CU).
+template <int NI> struct SliceAcc {
   static constexpr int n = NI;
-  static constexpr int width = (MODE == MODE_REASON) ? kSliceW : kSliceW * NI;    // floats per table row in LDS
-  // column offset of accumulator i inside the slice
-  static constexpr int coff(int i) { return (MODE == MODE_REASON) ? 0 : kSliceW * i; }
+  static constexpr int width = kSliceW * NI;    // floats per table row in LDS
   f32x4 v[n];
   __device__ __forceinline__ void zero() {
 #pragma unroll
@@ -1222,59 +1188,39 @@ template <int MODE, int NI> struct SliceAcc {
 };
 
 // acc += sum over the 4 facts a lane group (one quad) holds one per lane in `pairs`.
-// Branch-free form (default): the four facts' (p, row) are broadcast, the four LDS rows are requested back to back and
-// multiplied after ONE wait - the per-fact `if (p != 0)` of the first form cost 4 of its 11 instructions per fact and
-// serialised four LDS round trips per step.  Slots without a fact carry (p = 0, row = the table's extra ZERO row), so
-// they add exactly 0; a real fact with p = 0 adds 0 * t like the reference's fact_val * fact_prior (reasongnn.py:82).
+// Branch-free form: the facts' (p, row) are broadcast and the LDS rows requested fact by fact (two 1024-thread
+// workgroups per CU leave 64 VGPRs: the broadcasts are not made up front) - the per-fact `if (p != 0)` of the first form
+// cost 4 of its 11 instructions per fact and serialised four LDS round trips per step.  Slots without a fact carry
+// (p = 0, row = the table's extra ZERO row), so they add exactly 0; a real fact with p = 0 adds 0 * t like the
+// reference's fact_val * fact_prior (reasongnn.py:82).
 // One wave-uniform test skips a step none of whose 64 facts has a prior (seed priors: most steps).
-template <int MODE, int NI>
-__device__ __forceinline__ void slice_fma4(SliceAcc<MODE, NI>& acc, int2 pairs, const float* __restrict__ Td,
-                                           const f32x4 (&q)[SliceAcc<MODE, NI>::n]) {
+template <int K, int NI>
+__device__ __forceinline__ void slice_fma1(SliceAcc<NI>& acc, int2 pairs, const float* __restrict__ Td) {
+  const float pk = __int_as_float(quad_bcast<K>(pairs.x));
+  const int rk = quad_bcast<K>(pairs.y);
+  f32x4 t[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+    t[i] = *reinterpret_cast<const f32x4*>(Td + (size_t)rk * SliceAcc<NI>::width + kSliceW * i);
+#pragma unroll
+  for (int i = 0; i < NI; ++i) acc.v[i] += pk * t[i];
+}
+template <int NI>
+__device__ __forceinline__ void slice_fma4(SliceAcc<NI>& acc, int2 pairs, const float* __restrict__ Td) {
   if (__ballot(pairs.x != 0) == 0) return;               // (p >= 0: bits == 0 <=> p == 0)
-  constexpr int NT = (MODE == MODE_REASON) ? 1 : NI;     // table float4s per fact
-  // G facts' rows are in flight together (two 1024-thread workgroups per CU leave 64 VGPRs: the broadcasts are made
-  // per group, not up front)
-  auto group = [&](auto k0c) {
-    constexpr int k0 = decltype(k0c)::value;
-    constexpr int G = GNNRAG_SLICE_BL_GROUP;
-    float pk[G];
-    int rk[G];
-    f32x4 t[G][NT];
-#pragma unroll
-    for (int k = 0; k < G; ++k) {
-      pk[k] = __int_as_float(k0 + k == 0 ? quad_bcast<0>(pairs.x) : k0 + k == 1 ? quad_bcast<1>(pairs.x)
-                             : k0 + k == 2 ? quad_bcast<2>(pairs.x) : quad_bcast<3>(pairs.x));
-      rk[k] = k0 + k == 0 ? quad_bcast<0>(pairs.y) : k0 + k == 1 ? quad_bcast<1>(pairs.y)
-              : k0 + k == 2 ? quad_bcast<2>(pairs.y) : quad_bcast<3>(pairs.y);
-#pragma unroll
-      for (int i = 0; i < NT; ++i)
-        t[k][i] = *reinterpret_cast<const f32x4*>(Td + (size_t)rk[k] * SliceAcc<MODE, NI>::width + kSliceW * i);
-    }
-#pragma unroll
-    for (int k = 0; k < G; ++k)
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        if constexpr (MODE == MODE_REASON) acc.v[i] += pk[k] * vrelu(t[k][0] * q[i]);
-        else acc.v[i] += pk[k] * t[k][i];
-      }
-  };
-  group(std::integral_constant<int, 0>{});
-  if constexpr (GNNRAG_SLICE_BL_GROUP < 4) group(std::integral_constant<int, GNNRAG_SLICE_BL_GROUP>{});
-  if constexpr (GNNRAG_SLICE_BL_GROUP == 1) {
-    group(std::integral_constant<int, 2>{});
-    group(std::integral_constant<int, 3>{});
-  }
+  slice_fma1<0, NI>(acc, pairs, Td);
+  slice_fma1<1, NI>(acc, pairs, Td);
+  slice_fma1<2, NI>(acc, pairs, Td);
+  slice_fma1<3, NI>(acc, pairs, Td);
 }
 
-// one direction of one row, walked by a whole wave: 64 facts per step (lane group k owns facts
-// 4k..4k+3 of a step), steps first, first+stride, ...; up to 8 (wide slices: 4) steps requested before consuming
-template <int MODE, int NI>
-__device__ __forceinline__ void slice_walk_wave(SliceAcc<MODE, NI>& acc, const int2* __restrict__ prd, int beg,
-                                                int len, int first, int stride, int lane,
-                                                const float* __restrict__ Td,
-                                                const f32x4 (&q)[SliceAcc<MODE, NI>::n], int zr) {
+// one row (merged: both directions; else one direction of it), walked by a whole wave: 64 facts per step (lane group k
+// owns facts 4k..4k+3 of a step), steps first, first+stride, ...; up to 8 (wide slices: 4) steps requested before consuming
+template <int NI>
+__device__ __forceinline__ void slice_walk_wave(SliceAcc<NI>& acc, const int2* __restrict__ prd, int beg, int len,
+                                                int first, int stride, int lane, const float* __restrict__ Td, int zr) {
   const int nsteps = (len + 63) >> 6;
-  constexpr int INF = (SliceAcc<MODE, NI>::n > 1 && MODE == MODE_FUSED) ? 4 : 8;   // steps in flight (register budget)
+  constexpr int INF = NI > 1 ? 4 : 8;   // steps in flight (register budget)
   for (int st = first; st < nsteps; st += stride * INF) {
     int2 pairs[INF];
 #pragma unroll
@@ -1283,14 +1229,14 @@ __device__ __forceinline__ void slice_walk_wave(SliceAcc<MODE, NI>& acc, const i
       pairs[u] = (off < len) ? prd[beg + off] : make_int2(0, zr);
     }
 #pragma unroll
-    for (int u = 0; u < INF; ++u) slice_fma4<MODE, NI>(acc, pairs[u], Td, q);
+    for (int u = 0; u < INF; ++u) slice_fma4<NI>(acc, pairs[u], Td);
   }
 }
 
-template <int MODE, int NI>
-__device__ __forceinline__ void slice_wave_reduce(SliceAcc<MODE, NI>& acc) {
+template <int NI>
+__device__ __forceinline__ void slice_wave_reduce(SliceAcc<NI>& acc) {
 #pragma unroll
-  for (int i = 0; i < SliceAcc<MODE, NI>::n; ++i)
+  for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int o = 4; o < 64; o <<= 1) {
 #pragma unroll
@@ -1298,23 +1244,18 @@ __device__ __forceinline__ void slice_wave_reduce(SliceAcc<MODE, NI>& acc) {
     }
 }
 
-// where the float4 of (node n, accumulator i, direction d) goes
-template <int MODE>
-__device__ __forceinline__ float* slice_out(const WalkArgs& a, int n, int i, int d, int col) {
-  if constexpr (MODE == MODE_REASON)
-    return a.out + (size_t)n * (2 * a.I) * a.D + (size_t)(2 * (a.i0 + i) + d) * a.D + col;
-  else
-    return a.out + (size_t)n * a.D + col;
+// where the float4 of node n at column col goes
+__device__ __forceinline__ float* slice_out(const WalkArgs& a, int n, int col) {
+  return a.out + (size_t)n * a.D + col;
 }
 
-// Two 1024-thread workgroups per CU need 8 waves per SIMD, i.e. <= 64 VGPRs: ask for it where the
-// accumulators allow (one float4 per lane in FUSED mode).
-template <int MODE, int NI, bool MG>
-__global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_WPE : 4)) void k_walk_slice(const WalkArgs a, const int2* __restrict__ pr,
-                                                              int64_t F, int nslice, int nfull, int pl) {
-  typedef SliceAcc<MODE, NI> Acc;
+// Two 1024-thread workgroups per CU need 8 waves per SIMD, i.e. <= 64 VGPRs: the accumulators (one or two float4
+// per lane) allow it.
+template <int NI, bool MG>
+__global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(const WalkArgs a, const int2* __restrict__ pr,
+                                                                                int64_t F, int nslice, int nfull, int pl) {
+  typedef SliceAcc<NI> Acc;
   constexpr int NA = Acc::n;
-  constexpr int ND = (MODE == MODE_REASON) ? 2 : 1;     // output slots per node: per direction / summed
   extern __shared__ __attribute__((aligned(16))) float s_mem[];
   float* Ts = s_mem;                                   // [2][Rg + 1][16] (room for [2][R1 + 1][16]); row Rg is zero
   constexpr int SW = Acc::width;                       // floats per staged table row
@@ -1342,12 +1283,9 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
   const int c = item % nslice;
   const int col0 = c * SW;
   const int D = a.D, N = a.N;
-  // rows of this question's tables: FUSED tables hold only the relations the question uses
-  int Rg = a.R1, roff = 0;
-  if constexpr (MODE == MODE_FUSED) {
-    roff = a.rel_off[g];
-    Rg = a.rel_off[g + 1] - roff;
-  }
+  // rows of this question's tables: they hold only the relations the question uses
+  const int roff = a.rel_off[g];
+  const int Rg = a.rel_off[g + 1] - roff;
   const int tid = threadIdx.x;
   if (tid < 16) ctl[tid] = 0;
   // the question's big nodes (listed at plan time) with their row bounds -> LDS
@@ -1370,8 +1308,7 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
       e[4] = 0;
     }
   }
-  // stage the two table slices (float4 granules; rows are D*4 bytes apart).  FUSED: the question's own
-  // tables P[d, g]; REASON: the shared tables T_d
+  // stage the two slices of the question's own tables P[d, g] (float4 granules; rows are D*4 bytes apart)
   constexpr int GR = SW / 4;                           // float4 granules per staged row
   // five granules per thread requested before the first is written (one chunk covers 602 relations x 16 columns: the
   // loop used to be load -> LDS write -> load ..., five dependent round trips to L2 / HBM in front of the walk)
@@ -1408,18 +1345,11 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
   const int lane = tid & 63, wave = tid >> 6;
   const int grp = lane >> 2, sub = lane & 3;
   const int nsets = (N + 15) / 16;
-  bool col_ok[NA];                                     // accumulator i covers columns col0 + coff(i) + 4*sub .. +3
+  bool col_ok[NA];                                     // accumulator i covers columns col0 + 16 i + 4*sub .. +3
 #pragma unroll
-  for (int i = 0; i < NA; ++i) col_ok[i] = col0 + Acc::coff(i) + 4 * sub < D;
+  for (int i = 0; i < NA; ++i) col_ok[i] = col0 + kSliceW * i + 4 * sub < D;
   const int2* const prd[2] = {pr, pr + F};
   const float* Td[2] = {Ts + 4 * sub, Ts + (size_t)(Rg + 1) * SW + 4 * sub};
-  f32x4 q[NA];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    q[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (MODE == MODE_REASON && col_ok[i])
-      q[i] = *reinterpret_cast<const f32x4*>(a.ins + ((size_t)g * a.I + a.i0 + i) * D + col0 + 4 * sub);
-  }
 
   // ---- huge nodes first: the whole workgroup per node; wave w takes steps w, w+16, ...; wave sums
   // are combined by a fixed xor tree inside the wave and in wave order through LDS
@@ -1432,9 +1362,9 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
       acc.zero();
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
-        slice_walk_wave<MODE, NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], wave, kSliceWaves, lane, Td[d], q, Rg);
-        if (ND == 2 || d == 1) {
-          slice_wave_reduce<MODE, NI>(acc);
+        slice_walk_wave<NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], wave, kSliceWaves, lane, Td[d], Rg);
+        if (d == 1) {     // (inside the unrolled loop: behind it, the wide kernels' prologue is scheduled differently)
+          slice_wave_reduce<NI>(acc);
           if (grp == 0) {
 #pragma unroll
             for (int i = 0; i < NA; ++i) *reinterpret_cast<f32x4*>(red + (wave * NA + i) * 16 + 4 * sub) = acc.v[i];
@@ -1445,8 +1375,8 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
             f32x4 t = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int w = 0; w < kSliceWaves; ++w) t += *reinterpret_cast<const f32x4*>(red + (w * NA + i) * 16 + 4 * sb);
-            const int cc = col0 + Acc::coff(i) + 4 * sb;
-            if (cc < D) *reinterpret_cast<f32x4*>(slice_out<MODE>(a, e[0], i, d, cc)) = t;
+            const int cc = col0 + kSliceW * i + 4 * sb;
+            if (cc < D) *reinterpret_cast<f32x4*>(slice_out(a, e[0], cc)) = t;
           }
           __syncthreads();
           acc.zero();
@@ -1473,18 +1403,12 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
       Acc acc;
       acc.zero();
 #pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        slice_walk_wave<MODE, NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], 0, 1, lane, Td[d], q, Rg);
-        if (ND == 2 || d == 1) {
-          slice_wave_reduce<MODE, NI>(acc);
-          if (grp == 0) {
+      for (int d = 0; d < 2; ++d) slice_walk_wave<NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], 0, 1, lane, Td[d], Rg);
+      slice_wave_reduce<NI>(acc);
+      if (grp == 0) {
 #pragma unroll
-            for (int i = 0; i < NA; ++i)
-              if (col_ok[i])
-                *reinterpret_cast<f32x4*>(slice_out<MODE>(a, e[0], i, d, col0 + Acc::coff(i) + 4 * sub)) = acc.v[i];
-          }
-          acc.zero();
-        }
+        for (int i = 0; i < NA; ++i)
+          if (col_ok[i]) *reinterpret_cast<f32x4*>(slice_out(a, e[0], col0 + kSliceW * i + 4 * sub)) = acc.v[i];
       }
     }
   };
@@ -1506,8 +1430,8 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
         if (MG) {
           // first step peeled: its successor's pairs are already here (set_load_first requested them a set ago)
           if (len > 0) {
-            slice_fma4<MODE, NI>(acc, c0, Td[d], q);
-            if (!GNNRAG_SLICE_HALFSTEP || __ballot(4 < len)) slice_fma4<MODE, NI>(acc, c1, Td[d], q);
+            slice_fma4<NI>(acc, c0, Td[d]);
+            if (__ballot(4 < len)) slice_fma4<NI>(acc, c1, Td[d]);
           }
           c0 = c.second[0];
           c1 = c.second[1];
@@ -1517,21 +1441,17 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
           int2 n0 = make_int2(0, Rg), n1 = make_int2(0, Rg);
           if (j + 8 + sub < len) n0 = prd[d][beg + j + 8 + sub];
           if (j + 12 + sub < len) n1 = prd[d][beg + j + 12 + sub];
-          slice_fma4<MODE, NI>(acc, c0, Td[d], q);
+          slice_fma4<NI>(acc, c0, Td[d]);
           // second half of the step only if some node of the set still has facts there (most rows of the
           // inverse direction hold one or two facts)
-          if (!GNNRAG_SLICE_HALFSTEP || __ballot(j + 4 < len)) slice_fma4<MODE, NI>(acc, c1, Td[d], q);
+          if (__ballot(j + 4 < len)) slice_fma4<NI>(acc, c1, Td[d]);
           c0 = n0;
           c1 = n1;
         }
-        if (ND == 2 || d == 1 || MG) {
-#pragma unroll
-          for (int i = 0; i < NA; ++i)
-            if (col_ok[i])
-              *reinterpret_cast<f32x4*>(slice_out<MODE>(a, c.n, i, d, col0 + Acc::coff(i) + 4 * sub)) = acc.v[i];
-          acc.zero();
-        }
       }
+#pragma unroll
+      for (int i = 0; i < NA; ++i)
+        if (col_ok[i]) *reinterpret_cast<f32x4*>(slice_out(a, c.n, col0 + kSliceW * i + 4 * sub)) = acc.v[i];
     }
   };
   SetRows s0, s1, s2;
@@ -1555,7 +1475,7 @@ __global__ __launch_bounds__(kSliceThreads, (MODE == MODE_FUSED ? GNNRAG_SLICE_W
 static bool hub_dense_enabled() {
   static const bool on = [] {
     const char* e = getenv("GNNRAG_HUB_DENSE");
-    return GNNRAG_HUB_DENSE && !(e && e[0] == '0');
+    return !(e && e[0] == '0');
   }();
   return on;
 }
@@ -1590,11 +1510,11 @@ static int launch_one(WalkArgs a, hipStream_t stream) {
     bool quad = false;
     if constexpr (MODE == MODE_FUSED && VEC == 4 && LPN == 64 && CPL == 1) {
       // four facts per step (k_walk_light_q); rel * 4 D must fit the 24-bit multiply and 32-bit offsets
-      quad = GNNRAG_LIGHT_QUAD && a.D > 128 && a.R1 < (1 << 20);
+      quad = a.D > 128 && a.R1 < (1 << 20);
       if (quad) {
         // both directions as one merged run: no per-fact weights, both tables within 32-bit byte offsets of the first
         const long long span = ((const char*)a.T[1] - (const char*)a.T[0]) + (long long)(a.R1 + 1) * a.D * 4;
-        const bool mg = GNNRAG_QUAD_MERGED && a.merged && !a.w[0] && !a.w[1] && a.T[1] > a.T[0] && span < (1ll << 32);
+        const bool mg = a.merged && !a.w[0] && !a.w[1] && a.T[1] > a.T[0] && span < (1ll << 32);
         if (a.D > 192) {
           if (mg) hipLaunchKernelGGL((k_walk_light_q<4, true>), dim3(nblk), dim3(256), 0, stream, a);
           else hipLaunchKernelGGL((k_walk_light_q<4, false>), dim3(nblk), dim3(256), 0, stream, a);
@@ -1683,7 +1603,7 @@ static size_t slice_lds_bytes(int R1, int na = 3, int width = kSliceW) {
          (size_t)na * 16 * 16 * sizeof(float);
 }
 // the LDS variant needs the two table slices of a question in one CU's LDS (160 KB); rows = table rows
-// of the largest question (fused: relations it uses; unfused: the whole vocabulary)
+// of the largest question (the relations it uses)
 static bool slice_walk_fits(int rows, int D) {
   return D % 4 == 0 && slice_lds_bytes(rows) <= 160 * 1024 - 1024;
 }
@@ -1713,16 +1633,16 @@ static int fill_common(WalkArgs& a, const gnnrag_csr* csr, int D, void* ws, size
   return 0;
 }
 
-// k_fact_prior + k_walk_slice<MODE, NI>: the LDS walk of one aggregation call (or one pass of <= 3
-// instructions of it).  na = accumulators whose partial-sum scratch precedes the prior pairs.
-template <int MODE, int NI>
+// k_fact_prior + k_walk_slice<NI>: the LDS walk of one fused aggregation call.  The prior pairs follow the
+// partial-sum scratch of one accumulator in the workspace.
+template <int NI>
 static int launch_slice(const WalkArgs& a, const gnnrag_csr* csr, void* workspace, size_t workspace_bytes,
-                        int na_ws, hipStream_t stream, bool pairs_ready = false) {
+                        hipStream_t stream, bool pairs_ready = false) {
   const int D = a.D;
-  if (workspace_bytes < partial_bytes(csr, D, na_ws) + prior_bytes(csr)) return GNNRAG_E_WORKSPACE;
-  int2* pr = (int2*)((char*)workspace + partial_bytes(csr, D, na_ws));
+  if (workspace_bytes < partial_bytes(csr, D, 1) + prior_bytes(csr)) return GNNRAG_E_WORKSPACE;
+  int2* pr = (int2*)((char*)workspace + partial_bytes(csr, D, 1));
   const int64_t F = csr->F;
-  if (F > 0 && a.i0 == 0 && !(pairs_ready && a.merged)) {     // the (p, rel) pairs do not depend on the instruction pass
+  if (F > 0 && !(pairs_ready && a.merged)) {
     if (a.merged)
       hipLaunchKernelGGL(k_fact_prior_merged, dim3((unsigned)((2 * F + 255) / 256)), dim3(256), 0, stream, a.edge_m,
                          a.m_from, a.w[0], a.w[1], a.dist, F, pr);
@@ -1731,18 +1651,15 @@ static int launch_slice(const WalkArgs& a, const gnnrag_csr* csr, void* workspac
                          a.edge[1], a.w[0], a.w[1], a.dist, F, pr);
     GNNRAG_LAUNCH_CHECK();
   }
-  constexpr int SW = SliceAcc<MODE, NI>::width;
+  constexpr int SW = SliceAcc<NI>::width;
   const int nslice = (D + SW - 1) / SW;
-  const size_t lds = slice_lds_bytes(a.R1, SliceAcc<MODE, NI>::n, SW);
-  static DeviceMask cap_raised;    // per kernel instantiation, per device
+  const size_t lds = slice_lds_bytes(a.R1, NI, SW);
+  static DeviceMask cap_raised, cap_raised_m;    // per kernel instantiation, per device
   {
-    const int rc = raise_lds_cap(k_walk_slice<MODE, NI, false>, cap_raised);
+    const int rc = raise_lds_cap(k_walk_slice<NI, false>, cap_raised);
     if (rc) return rc;
-    if constexpr (MODE == MODE_FUSED) {
-      static DeviceMask cap_raised_m;
-      const int rc2 = raise_lds_cap(k_walk_slice<MODE, NI, true>, cap_raised_m);
-      if (rc2) return rc2;
-    }
+    const int rc2 = raise_lds_cap(k_walk_slice<NI, true>, cap_raised_m);
+    if (rc2) return rc2;
   }
   // per XCD: items = (questions of the XCD) x slices, slots = 2 workgroups on each of its CUs
   int cus = 0;
@@ -1763,14 +1680,12 @@ static int launch_slice(const WalkArgs& a, const gnnrag_csr* csr, void* workspac
     if (pl < 2) pl = 0;       // halves are what the tail split above already gives
     if (pl) nblk = 8 * (items_x << pl);
   }
-  if (MODE == MODE_FUSED && a.merged) {
-    if constexpr (MODE == MODE_FUSED)
-      hipLaunchKernelGGL((k_walk_slice<MODE, NI, true>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
-                         nslice, nfull, pl);
-  } else {
-    hipLaunchKernelGGL((k_walk_slice<MODE, NI, false>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
+  if (a.merged)
+    hipLaunchKernelGGL((k_walk_slice<NI, true>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
                        nslice, nfull, pl);
-  }
+  else
+    hipLaunchKernelGGL((k_walk_slice<NI, false>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
+                       nslice, nfull, pl);
   GNNRAG_LAUNCH_CHECK();
   return 0;   // hubs were walked inside the kernel, nothing to add afterwards
 }
@@ -1788,7 +1703,7 @@ extern "C" int gnnrag_aggregate(const gnnrag_csr* csr, const float* dist, const 
                                 const float* T_fwd, const float* T_inv, float* agg, int32_t D, int32_t I,
                                 void* workspace, size_t workspace_bytes, gnnrag_stream_t stream) {
   if (!csr || !dist || !ins || !T_fwd || !T_inv || !agg || D <= 0 || I <= 0) return GNNRAG_E_BADARG;
-  // the stated size, whichever walk this call takes (the gather walk alone would get by with less)
+  // the stated size (shared with the fused walks, which keep their prior pairs behind the partial sums)
   if (!workspace || workspace_bytes < gnnrag_aggregate_workspace_bytes(csr, D, I)) return GNNRAG_E_WORKSPACE;
   WalkArgs a;
   memset(&a, 0, sizeof(a));
@@ -1803,18 +1718,10 @@ extern "C" int gnnrag_aggregate(const gnnrag_csr* csr, const float* dist, const 
   a.out = agg;
   a.I = I;
   // up to 3 instructions share one walk (their accumulators live in registers side by side)
-  const bool lds_walk = slice_walk_fits(csr->R1, D) && GNNRAG_REASON_SLICE;
   for (int i0 = 0; i0 < I; i0 += 3) {
     a.i0 = i0;
     const int ni = (I - i0) < 3 ? (I - i0) : 3;
-    if (lds_walk) {
-      const int na_ws = I < 3 ? I : 3;
-      if (ni == 1) rc = launch_slice<MODE_REASON, 1>(a, csr, workspace, workspace_bytes, na_ws, (hipStream_t)stream);
-      else if (ni == 2) rc = launch_slice<MODE_REASON, 2>(a, csr, workspace, workspace_bytes, na_ws, (hipStream_t)stream);
-      else rc = launch_slice<MODE_REASON, 3>(a, csr, workspace, workspace_bytes, na_ws, (hipStream_t)stream);
-    } else {
-      rc = launch_walk<MODE_REASON>(a, ni, (hipStream_t)stream);
-    }
+    rc = launch_walk<MODE_REASON>(a, ni, (hipStream_t)stream);
     if (rc) return rc;
   }
   return 0;
@@ -1848,7 +1755,7 @@ static int prepare_fused(WalkArgs& a, const gnnrag_csr* csr, const float* dist, 
   a.I = 1;
   a.skip_dir = skip_dir;
   // merged rows: whenever both directions are walked and the structure carries the merged positions
-  a.merged = (GNNRAG_SLICE_MERGED && skip_dir == 0 && csr->edge_m && csr->m_from) ? 1 : 0;
+  a.merged = (skip_dir == 0 && csr->edge_m && csr->m_from) ? 1 : 0;
   a.edge_m = (const int2*)csr->edge_m;
   a.m_from = csr->m_from;
   const int variant = gnnrag_aggregate_fused_variant(csr, D);
@@ -1910,8 +1817,8 @@ int gnnrag::aggregate_fused_dirs(const gnnrag_csr* csr, const float* dist, const
     case GNNRAG_WALK_L2_GATHER: return launch_walk<MODE_FUSED>(a, 1, stream);   // tables too big for LDS
     // 32-column slices when two of them still fit a CU's LDS (questions that use up to ~300 relations): half
     // as many workgroups re-walk the question's facts
-    case GNNRAG_WALK_LDS_32: return launch_slice<MODE_FUSED, 2>(a, csr, workspace, workspace_bytes, 1, stream, pairs_ready);
-    default: return launch_slice<MODE_FUSED, 1>(a, csr, workspace, workspace_bytes, 1, stream, pairs_ready);
+    case GNNRAG_WALK_LDS_32: return launch_slice<2>(a, csr, workspace, workspace_bytes, stream, pairs_ready);
+    default: return launch_slice<1>(a, csr, workspace, workspace_bytes, stream, pairs_ready);
   }
 }
 
@@ -1940,7 +1847,7 @@ extern "C" int gnnrag_aggregate_fused_hub_form(const gnnrag_csr* csr, int32_t D,
 extern "C" int gnnrag_aggregate_fused_variant(const gnnrag_csr* csr, int32_t D) {
   if (!csr || D <= 0 || csr->rel_total < 0) return GNNRAG_E_BADARG;
   if (!slice_walk_fits(csr->rel_max, D)) return GNNRAG_WALK_L2_GATHER;
-  if (GNNRAG_SLICE_WIDE && D > kSliceW && slice_lds_bytes(csr->rel_max, 2, 2 * kSliceW) <= GNNRAG_SLICE_WIDE_LDS_KB * 1024)
+  if (D > kSliceW && slice_lds_bytes(csr->rel_max, 2, 2 * kSliceW) <= GNNRAG_SLICE_WIDE_LDS_KB * 1024)
     return GNNRAG_WALK_LDS_32;
   return GNNRAG_WALK_LDS_16;
 }

@@ -29,19 +29,6 @@
 // pinning (+-0), A tiles requested two k-tiles ahead (+-0), prefetching all A tiles of a short-K problem
 // (register blow-up), direct stores from the MFMA layout instead of the LDS-staged epilogue (-25 % on the
 // self-block update).
-#define GNNRAG_GEMM_MT1_NW 8     // the one-row-tile-per-wave variant may use 8-wave (128-row) workgroups
-#ifndef GNNRAG_UPDATE_B3
-#define GNNRAG_UPDATE_B3 1       // bf16x3 self-block update on the W-resident kernel of tables_b3.hip
-#endif
-#ifndef GNNRAG_TABLES_WRES
-#define GNNRAG_TABLES_WRES 1     // bf16x3 relation tables on the W-resident kernel of tables_b3.hip
-#endif
-#ifndef GNNRAG_GEMM_WRES
-#define GNNRAG_GEMM_WRES 1       // short-K problems in exact fp32 run the W-resident kernel (k_gemm_wres)
-#endif
-#ifndef GNNRAG_UPDATE_SKINNY
-#define GNNRAG_UPDATE_SKINNY 1   // self-block update of small batches (< 4096 rows) on the one-wave-per-tile kernel
-#endif
 
 namespace gnnrag {
 
@@ -966,8 +953,7 @@ static DenseForm gemm_form(const GemmArgs& g, int epi, int amode, int math) {
   // fills the chip evenly, else 4-wave workgroups (64 rows)
   const int slots8 = 512;
   const int t8 = tiles128;
-  const bool nw8 = small_tiles && (t8 >= 3 * slots8 / 2 || (t8 % slots8 == 0) || (t8 % slots8) > slots8 / 2) &&
-                   GNNRAG_GEMM_MT1_NW == 8;
+  const bool nw8 = small_tiles && (t8 >= 3 * slots8 / 2 || (t8 % slots8 == 0) || (t8 % slots8) > slots8 / 2);
   f.mt = small_tiles ? 1 : 2;
   f.nw = nw8 ? 8 : 4;
   // MIXED: the k-tiled kernel runs its bf16x3 form; the scalar loaders exist in the exact-fp32 form only
@@ -1032,18 +1018,18 @@ static DenseForm update_form(const GemmArgs& g_in, int64_t BN, int32_t D, int ma
     const bool al = aligned16(g.A0) && aligned16(g.W) && aligned16(g.C) && (!g.add || aligned16(g.add)) &&
                     g.ldw % 4 == 0 && g.wc0 % 4 == 0 && (!g.add || g.add_rows >= g.M);
     const bool flag_ok = !g.add_flag || ((uintptr_t)g.add_flag & 3) == 0;
-    if (GNNRAG_UPDATE_B3 && math != GNNRAG_MATH_FP32 && al && g.add && !g.A1 && g.K == D && flag_ok &&
+    if (math != GNNRAG_MATH_FP32 && al && g.add && !g.A1 && g.K == D && flag_ok &&
         update_b3_shape_ok(BN, D, g.ldw)) {
       f.family = f.block_family = GNNRAG_DENSE_UPDATE_B3;
       return f;
     }
-    const int S = (GNNRAG_GEMM_WRES && math != GNNRAG_MATH_BF16X3 && al && g.M >= 4096 && flag_ok) ? wres_stride(g) : 0;
+    const int S = (math != GNNRAG_MATH_BF16X3 && al && g.M >= 4096 && flag_ok) ? wres_stride(g) : 0;
     if (S && wres_class(g, &f)) {
       f.family = f.block_family = GNNRAG_DENSE_WRES;
       f.S = S;
       return f;
     }
-    if (GNNRAG_UPDATE_SKINNY && update_skinny_ok(g)) {      // small batches: exact fp32
+    if (update_skinny_ok(g)) {      // small batches: exact fp32
       f.family = f.block_family = GNNRAG_DENSE_UPDATE_SKINNY;
       return f;
     }
@@ -1294,7 +1280,7 @@ extern "C" int gnnrag_relation_tables(const gnnrag_csr* csr, const float* T_fwd,
     if (rc != GNNRAG_E_UNSUPPORTED) return rc;
   }
   if (math == GNNRAG_MATH_MIXED) math = GNNRAG_MATH_BF16X3;
-  if (math == GNNRAG_MATH_BF16X3 && GNNRAG_TABLES_WRES) {     // W-resident kernel (tables_b3.hip) where its shapes allow
+  if (math == GNNRAG_MATH_BF16X3) {    // W-resident kernel (tables_b3.hip) where its shapes allow
     const int rc = tables_b3_launch(csr, T_fwd, T_inv, ins, W, P, D, I, (hipStream_t)stream);
     if (rc != GNNRAG_E_UNSUPPORTED) return rc;
   }

@@ -91,15 +91,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // time, the sign carries the spare bit), lo = bf16(r - mid) is exact.  18 VALU per 4 values; the truncation split
 // (mask, subtract, mask, subtract, shift / or packing) needed 26.
 struct Split3 { uint2 hi, mid, lo; };
-#ifndef GNNRAG_SPLIT_RN
-#define GNNRAG_SPLIT_RN 1
-#endif
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ unsigned pack_bf16_rn(float a, float b) {
   return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){a, b}, bf16x2_t));
 }
 __device__ __forceinline__ Split3 split3(f32x4 x) {
-#if GNNRAG_SPLIT_RN
   Split3 s;
   const unsigned h01 = pack_bf16_rn(x[0], x[1]), h23 = pack_bf16_rn(x[2], x[3]);
   const float r0 = x[0] - __uint_as_float(h01 << 16), r1 = x[1] - __uint_as_float(h01 & 0xffff0000u);
@@ -111,24 +107,6 @@ __device__ __forceinline__ Split3 split3(f32x4 x) {
   s.mid = make_uint2(m01, m23);
   s.lo = make_uint2(pack_bf16_rn(q0, q1), pack_bf16_rn(q2, q3));
   return s;
-#else
-  // truncation split: hi keeps the top 8 significand bits, the remainder x - hi is exact in fp32 and has <= 16 bits ...
-  unsigned h[4], m[4], l[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const unsigned u = __float_as_uint(x[e]);
-    h[e] = u & 0xffff0000u;
-    const float r = x[e] - __uint_as_float(h[e]);
-    m[e] = __float_as_uint(r) & 0xffff0000u;
-    const float r2 = r - __uint_as_float(m[e]);
-    l[e] = __float_as_uint(r2);            // <= 8 significant bits: its low 16 encoding bits are zero
-  }
-  Split3 s;
-  s.hi = make_uint2((h[0] >> 16) | h[1], (h[2] >> 16) | h[3]);
-  s.mid = make_uint2((m[0] >> 16) | m[1], (m[2] >> 16) | m[3]);
-  s.lo = make_uint2((l[0] >> 16) | (l[1] & 0xffff0000u), (l[2] >> 16) | (l[3] & 0xffff0000u));
-  return s;
-#endif
 }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -3,7 +3,7 @@
 `--build`), then (GPU side, `--run`) times the hot ops of workload C2 with each variant in its own
 process and prints one line per variant.
     python tools/tune_variants.py --build          # here (hipcc cross-compiles)
-    python tools/tune_variants.py --run            # on the GPU box (gpurun)
+    python tools/tune_variants.py --run            # on the GPU box
 """
 import json
 import os
@@ -18,25 +18,19 @@ sys.path.insert(0, REPO)
 VARIANTS = {
     "default": {},
     # macros that exist in the kernel sources today (add a macro to a kernel, list its values here, run):
-    "gemm_nw4": {"GNNRAG_GEMM_MT1_NW": 4},                 # gemm_f32.hip: waves per workgroup of the k-tiled kernel
-    "no_wres": {"GNNRAG_GEMM_WRES": 0},                    # the k-tiled kernel instead of the W-resident one (exact fp32)
     "no_split_tail": {"GNNRAG_SLICE_SPLIT_TAIL": 0},       # aggregate.hip, LDS walk
-    "no_halfstep": {"GNNRAG_SLICE_HALFSTEP": 0},
     "wide_always": {"GNNRAG_SLICE_WIDE_LDS_KB": 159},
-    "sl_unmerged": {"GNNRAG_SLICE_MERGED": 0},
-    "sl_g2": {"GNNRAG_SLICE_BL_GROUP": 2}, "sl_g4": {"GNNRAG_SLICE_BL_GROUP": 4},
     # LDS walk workgroup sizes (two workgroups per CU either way): 512 / 640 / 768 threads = 4 / 5 / 6 waves per SIMD
-    "sl_t512_g1": {"GNNRAG_SLICE_THREADS": 512, "GNNRAG_SLICE_WPE": 4, "GNNRAG_SLICE_BL_GROUP": 1},
+    "sl_t512": {"GNNRAG_SLICE_THREADS": 512, "GNNRAG_SLICE_WPE": 4},
     "sl_t768": {"GNNRAG_SLICE_THREADS": 768, "GNNRAG_SLICE_WPE": 6},
     "sl_t640": {"GNNRAG_SLICE_THREADS": 640, "GNNRAG_SLICE_WPE": 5},
     "vq_un3": {"GNNRAG_VQ_UN": 3}, "vq_un4": {"GNNRAG_VQ_UN": 4},      # tables_b3.hip: V pieces in flight while staging
     # gather walk (tables larger than LDS, BASELINE config 5; GNNRAG_TUNE_WORKLOAD=C5)
     "light_npw1": {"GNNRAG_LIGHT_NPW": 1}, "light_npw4": {"GNNRAG_LIGHT_NPW": 4},
-    "quad_off": {"GNNRAG_LIGHT_QUAD": 0}, "quad_s2": {"GNNRAG_QUAD_STEPS": 2}, "quad_unmerged": {"GNNRAG_QUAD_MERGED": 0},
-    "hub_u4": {"GNNRAG_HUB_U": 4}, "hub_ks16": {"GNNRAG_HUB_KS_MAX": 16}, "hub_ks4": {"GNNRAG_HUB_KS_MAX": 4},
+    "quad_s2": {"GNNRAG_QUAD_STEPS": 2},
+    "hub_ks16": {"GNNRAG_HUB_KS_MAX": 16}, "hub_ks4": {"GNNRAG_HUB_KS_MAX": 4},
     "hub_wg8192": {"GNNRAG_HUB_W_GRID": 8192}, "hub_wg512": {"GNNRAG_HUB_W_GRID": 512},
     "noslp": {"__flags__": ["-fno-slp-vectorize"]},        # the compiler SLP-packs the split's subtractions into v_pk_add_f32
-    "split_trunc": {"GNNRAG_SPLIT_RN": 0},                 # the truncation form of the exact 3-way bf16 split (rounds 1-2)
     # the product library as built (lib/libgnnrag_hip.so) against lib/exp_default.so from an earlier build
     "mainlib": {"__env__": {"GNNRAG_LIB": os.path.join(REPO, "gnn-rag_amd", "lib", "libgnnrag_hip.so")}},
 }
