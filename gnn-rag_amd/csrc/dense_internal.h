@@ -10,10 +10,6 @@ namespace gnnrag {
 int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
                        int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream);
 
-int update_b3_launch_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
-                       const float* b_s, const float* mask, float* h_out, float* score, int64_t BN, int32_t D,
-                       int32_t ldw, hipStream_t stream, bool score_zeroed);
-
 // Row-gated form of the self-block update: `nbr` holds valid data only in the rows whose byte in add_flag is non-zero,
 // every other row reads the ZERO ROW behind the buffer (row index BN), so the unflagged rows of nbr are never
 // touched (frontier layers: frontier.hip).  add_flag: [BN + at least 16 bytes of readable padding] (the kernels

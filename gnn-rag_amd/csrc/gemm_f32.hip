@@ -23,6 +23,7 @@
 // tile t+1 are issued before the MFMAs of tile t (register prefetch), two workgroups per CU.
 #include "gnnrag_common.h"
 #include "dense_internal.h"
+#include "b3_tile.h"
 
 // Variants that were A/B-tested on MI355X and did NOT pay (removed; see DESIGN.md section 3.5 and git history):
 // branch-free clamped tile loads (-8 %), source-level fragment double buffering / sched_group_barrier
@@ -311,17 +312,14 @@ void k_gemm_f32(GemmArgs g) {
             b[q][pl] = (nt0 + q < NT) ? __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(
                                             &Ws[((nt0 + q) * 16 + fr) * kLS + pl * 16 + fg * 4]))
                                       : a[0][pl];
-        // (A plane, B plane) pairs, smallest terms first: mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-        constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
 #pragma unroll
-        for (int p = 0; p < 6; ++p)
+        for (int p = 0; p < 6; ++p)       // the six plane pairs, smallest terms first (b3_tile.h)
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
             for (int q = 0; q < NG; ++q)
               if (nt0 + q < NT)
-                acc[mt][nt0 + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt][PA[p]], b[q][PB[p]],
+                acc[mt][nt0 + q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mt][kB3PA[p]], b[q][kB3PB[p]],
                                                                            acc[mt][nt0 + q], 0, 0, 0);
       }
     }
@@ -422,34 +420,7 @@ void k_gemm_f32(GemmArgs g) {
   }
 }
 
-// ---- cross-lane helpers of the epilogue: VALU only (DPP row operations), no LDS crossbar round trips (the first
-// version reduced every row's score with six dependent ds_bpermute shuffles: 96 LDS round trips per wave and tile)
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_f(float old, float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, 0xf, BANK, false));
-}
-__device__ __forceinline__ float lane_xor1(float x) { return dpp_f<0xB1, 0xf>(x, x); }   // quad_perm [1,0,3,2]
-__device__ __forceinline__ float lane_xor2(float x) { return dpp_f<0x4E, 0xf>(x, x); }   // quad_perm [2,3,0,1]
-__device__ __forceinline__ float lane_xor4(float x) {
-  const float t = dpp_f<0x104, 0x5>(x, x);      // row_shl:4 into lanes 0-3, 8-11 of a 16-lane row (they read lane + 4)
-  return dpp_f<0x114, 0xA>(t, x);               // row_shr:4 into lanes 4-7, 12-15 (they read lane - 4)
-}
-__device__ __forceinline__ float lane_xor8(float x) { return dpp_f<0x128, 0xf>(x, x); }  // row_ror:8
-
-// Sums 4 values per lane over the 16 lanes of a DPP row with 6 DPP moves (instead of 4 x 4 shuffles): two
-// reduce-scatter steps over lane bits 0 and 1 halve the values a lane carries, two all-reduce steps over bits 2
-// and 3 finish.  Returns the total of value index 2*(lane&1) + ((lane>>1)&1); one fixed summation order.
-__device__ __forceinline__ float row16_sum4(const float (&v)[4], int lane) {
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float w2[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) w2[j] = (b0 ? v[j + 2] : v[j]) + lane_xor1(b0 ? v[j] : v[j + 2]);
-  float w = (b1 ? w2[1] : w2[0]) + lane_xor2(b1 ? w2[0] : w2[1]);
-  w += lane_xor4(w);
-  w += lane_xor8(w);
-  return w;
-}
-__device__ __forceinline__ int row16_sum4_index(int lane) { return 2 * (lane & 1) + ((lane >> 1) & 1); }
+// (the register epilogues' cross-lane helpers - dpp_f, lane_xor*, row16_sum4 - and opaque() live in b3_tile.h)
 
 // Output-column permutation.  The MFMA C layout gives lane (fr = lane & 15, fg = lane >> 4) the entries
 // (row 4*fg + q, column slot fr) of every 16x16 tile nt.  WHICH output column a slot stands for is free: it is
@@ -471,13 +442,6 @@ template <int NT> struct ColMap {
     return j;
   }
 };
-
-// Opaque copy of a lane-dependent value: address arithmetic derived from it is redone where it is used instead of
-// being hoisted out of the row-tile loop and kept in (spilled) registers across the k loop.
-__device__ __forceinline__ int opaque(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
 
 // ---- W-resident kernel: the whole weight block lives in LDS, A fragments come straight from global memory ------
 // For C[M, Nout] = A[M, K] . W^T with a SHORT K and a huge M (the self-block update: M = B*N = 128 000,

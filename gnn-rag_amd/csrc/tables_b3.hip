@@ -3,7 +3,9 @@
 //   k_tables_vq   relation tables in "V form" from pre-split relation planes (what a layer / stack call runs)
 //   k_update_b3   the self-block update h' = relu(h W^T + b + nbr) with the fused score
 // They share the LDS weight-plane layout (three bf16 planes of an exact 3-way split, 26-slot row stride), the six
-// plane products on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, and the register epilogue.
+// plane products on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, and the register epilogue: b3_tile.h holds each of
+// these once (layout constants, kB3PA / kB3PB, b3_pack_a, b3_products_pair, tab_store_tiles); only the staging of the
+// weight planes is still written twice (tables_b3_part says why).
 //
 // ---- k_tables_b3: per-question relation tables of the fused path, operand generated on the fly ----------------------
 //
@@ -28,6 +30,8 @@
 // Two barriers per instruction and workgroup instead of two per 32 k.
 #include "gnnrag_common.h"
 #include "dense_internal.h"
+#include "b3_tile.h"
+#include <type_traits>
 
 namespace gnnrag {
 
@@ -38,10 +42,7 @@ namespace gnnrag {
 #define GNNRAG_TAB_MINBLK 2       // waves per SIMD: one 8-wave workgroup per CU (the planes fill its LDS) = 2, 256 registers each
 #endif
 constexpr int kTabTPW = GNNRAG_TAB_TPW;        // row tiles per wave and pass (accumulators in registers; 5 spill: 140 + 40 + 36 VGPRs)
-constexpr int kTabNTH = 7;        // column tiles per column part (two parts cover up to 13 tiles = 208 columns)
-constexpr int kTabNKB = 7;        // k blocks of 32: 192 < D <= 208 (the hidden size of the BASELINE configs is 200)
-constexpr int kTabSlots = 26;     // LDS row stride of a weight plane in 16-byte slots (26 % 4 == 2: conflict free)
-constexpr int kTabQBytes = 160 * 1024 - 3 * kTabNTH * 16 * kTabSlots * 16 - 64;   // LDS left for instruction rows (24 000 B)
+constexpr int kTabQBytes = 160 * 1024 - 3 * kTabPlaneB - 64;   // LDS left for instruction rows (24 000 B)
 
 struct TabArgs {
   const float* T[2];       // [R1, D] relation tables of the two directions
@@ -54,56 +55,12 @@ struct TabArgs {
   int32_t npass;           // passes of kTabTPW tiles per wave
 };
 
-__device__ __forceinline__ int opaque_i(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-
-// sum of 4 values per lane over the 16 lanes of a DPP row (see gemm_f32.hip: row16_sum4); returns the total of value
-// index 2*(lane&1) + ((lane>>1)&1)
-template <int CTRL, int BANK>
-__device__ __forceinline__ float dpp_b3(float old, float x) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(old), __float_as_int(x), CTRL, 0xf, BANK, false));
-}
-__device__ __forceinline__ float row16_sum4_b3(const float (&v)[4], int lane) {
-  const bool b0 = lane & 1, b1 = lane & 2;
-  float w2[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const float send = b0 ? v[j] : v[j + 2];
-    w2[j] = (b0 ? v[j + 2] : v[j]) + dpp_b3<0xB1, 0xf>(send, send);
-  }
-  const float send = b1 ? w2[0] : w2[1];
-  float w = (b1 ? w2[1] : w2[0]) + dpp_b3<0x4E, 0xf>(send, send);
-  const float t4 = dpp_b3<0x104, 0x5>(w, w);
-  w += dpp_b3<0x114, 0xA>(t4, w);
-  w += dpp_b3<0x128, 0xf>(w, w);
-  return w;
-}
-
-// LDS row of column slot: the first four column tiles of a part are interleaved so that a lane holds four
-// consecutive columns (float4 stores in the epilogue), the others keep the plain order
-__device__ __forceinline__ int tab_lds_row(int j) {
-  if (j < 64) return ((j & 3) << 4) + (j >> 2);
-  return j;
-}
-
-// Weight rows a column part stages per plane: its CTN x 16 columns (columns past the part's last real one as zeros)
-// PLUS ONE zero row when the part does not fill the plane - the last k block of a row reads up to 32 bytes past the
-// row's end (k >= D; the A side is zero there), i.e. the head of the NEXT row, and 0 x (whatever an unwritten LDS row
-// holds) is NaN when that happens to be an Inf / NaN pattern.  With D = 200 the next row is one of the part's own zero
-// rows; with D = 208 the 6-tile part ends exactly at its last staged row (found by the D = 208 shape-sweep test:
-// column 207 came out as relu(NaN) = 0 for some rows).  A full plane (7 tiles) is followed by the next plane's row 0
-// or the zeroed slack.
-__device__ __forceinline__ constexpr int tab_stage_rows(int ctn) { return ctn < kTabNTH ? ctn * 16 + 1 : ctn * 16; }
-
 // One column part with CTN column tiles (compile time: the MFMA loop has no branches).  QLDS: the instruction rows
 // of the chunk's questions are in LDS (the usual case) - also compile time: a run-time branch around the global-memory
 // variant's loads would make every vmcnt wait of the loop conservative, i.e. wait for the prefetch just issued.
 template <int CTN, bool QLDS>
 __device__ __forceinline__ void tables_b3_part(const TabArgs& a, unsigned char* lds, int col0, int bmin, int nq) {
-  constexpr int RB = kTabSlots * 16;                        // bytes per weight row of one plane
-  constexpr int PL = kTabNTH * 16 * RB;                     // bytes per plane
+  constexpr int RB = kTabRowB, PL = kTabPlaneB;
   constexpr int ctn = CTN;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -144,7 +101,10 @@ __device__ __forceinline__ void tables_b3_part(const TabArgs& a, unsigned char* 
 
     for (int i = 0; i < I; ++i) {
       __syncthreads();                                      // the previous block's fragment reads are done
-      // ---- this instruction's weight block -> three bf16 planes in LDS ----
+      // ---- this instruction's weight block -> three bf16 planes in LDS.  The same text as in update_b3_part but for
+      // wcol, and it stays text: as a function in b3_tile.h the array v comes out as one 24-register tuple that is
+      // copied after every load, each load waited for at once (k_tables_b3: 256 registers and 256 bytes of scratch);
+      // `#pragma nounroll` on the loop over `base` avoids that (204, none) but leaves the loop rolled ----
       {
         const int wcol = (1 + 2 * i + d) * D;               // first k column of the block inside e2e_linear.weight
         const int total = tab_stage_rows(ctn) * kTabSlots * 2;      // 8-byte pieces (4 k) per plane: rows x 52
@@ -223,67 +183,19 @@ __device__ __forceinline__ void tables_b3_part(const TabArgs& a, unsigned char* 
             // A planes of this k block: relu(T * ins), exact 3-way bf16 split
             const Split3 s0 = split3(kok ? __builtin_elementwise_max(t0 * q0, zero4) : zero4);
             const Split3 s1 = split3(kok ? __builtin_elementwise_max(t1 * q1, zero4) : zero4);
-            typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
             bf16x8 ap[3];
-            ap[0] = __builtin_bit_cast(bf16x8, (u32x4){s0.hi.x, s0.hi.y, s1.hi.x, s1.hi.y});
-            ap[1] = __builtin_bit_cast(bf16x8, (u32x4){s0.mid.x, s0.mid.y, s1.mid.x, s1.mid.y});
-            ap[2] = __builtin_bit_cast(bf16x8, (u32x4){s0.lo.x, s0.lo.y, s1.lo.x, s1.lo.y});
-            // (A plane, B plane) pairs, smallest terms first: mid*mid, lo*hi, hi*lo, mid*hi, hi*mid, hi*hi
-            constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-            constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
+            b3_pack_a(s0, s1, ap);
 #pragma unroll
-            for (int nt = 0; nt < CTN; nt += 2) {
-              bf16x8 b0[3], b1[3];
-#pragma unroll
-              for (int pl = 0; pl < 3; ++pl) {
-                b0[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wb + pl * PL + nt * 16 * RB));
-                b1[pl] = b0[pl];
-                if (nt + 1 < CTN)
-                  b1[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wb + pl * PL + (nt + 1) * 16 * RB));
-              }
-#pragma unroll
-              for (int p = 0; p < 6; ++p) {
-                acc[j][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[PA[p]], b0[PB[p]], acc[j][nt], 0, 0, 0);
-                if (nt + 1 < CTN)
-                  acc[j][nt + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[PA[p]], b1[PB[p]], acc[j][nt + 1], 0, 0, 0);
-              }
-            }
+            for (int nt = 0; nt < CTN; nt += 2) b3_products_pair<CTN>(acc[j], nt, ap, wb, wb + PL, wb + 2 * PL, 0);
           }
         }
       }
     }
 
-    // ---- epilogue: the pass's tiles leave the registers (C layout: rows 4 fg + q, column slot fr) ----
+    // ---- epilogue: the pass's tiles leave the registers ----
 #pragma unroll
-    for (int j = 0; j < kTabTPW; ++j) {
-      if (j < ntile) {
-        const int rbase = (tbase + j) * 16 + 4 * fg;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = rbase + q;
-          if (row < a.M) {
-            float* prow = P + (size_t)row * D + col0;
-            // interleaved group (column tiles 0..3): columns 4 fr .. 4 fr + 3
-            static_assert(CTN >= 4, "a column part holds at least the interleaved group");
-            {
-              const f32x4 v = {acc[j][0][q], acc[j][1][q], acc[j][2][q], acc[j][3][q]};
-              const int c = 4 * fr;
-              if (c + 4 <= ncol) *reinterpret_cast<f32x4*>(prow + c) = v;
-              else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  if (c + e < ncol) prow[c + e] = v[e];
-              }
-            }
-#pragma unroll
-            for (int nt = 4; nt < CTN; ++nt) {
-              const int c = nt * 16 + fr;
-              if (c < ncol) prow[c] = acc[j][nt][q];
-            }
-          }
-        }
-      }
-    }
+    for (int j = 0; j < kTabTPW; ++j)
+      if (j < ntile) tab_store_tiles<CTN>(acc[j], P, D, (tbase + j) * 16, a.M, col0, ncol, fr, fg);
   }
 }
 
@@ -406,9 +318,8 @@ __device__ __forceinline__ int vq_row(int x, int nb) { return nb == 3 ? (int)(((
 template <int CTN, int UN>
 __device__ __forceinline__ void vq_stage(const VqArgs& a, unsigned char* lds, const float* qarea, int col0, int ncol,
                                          int d, int blk0, int nb) {
-  constexpr int RB = kTabSlots * 16;
-  constexpr int PL = kTabNTH * 16 * RB;
-  const int total = CTN * 16 * 8 * nb;                          // 8 pieces per (row, block); nb is 3 or 1
+  constexpr int RB = kTabRowB, PL = kTabPlaneB;
+  const int total = CTN * 16 * 8 * nb;                         // 8 pieces per (row, block); nb is 3 or 1
   const int tid = threadIdx.x;
   const int D = a.D, I = a.I, KC = D >> 2;
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -492,9 +403,7 @@ __device__ __forceinline__ VqA vq_compress(const VqRaw& r) {
 
 template <int CTN>
 __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* lds, int col0) {
-  constexpr int RB = kTabSlots * 16;
-  constexpr int PL = kTabNTH * 16 * RB;
-  constexpr int NKB = kTabNKB;
+  constexpr int RB = kTabRowB, PL = kTabPlaneB;
   constexpr int NPAIR = (kVqTPW + 1) / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -548,8 +457,6 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
       for (int kb = 0; kb < nblk; ++kb) {       // (not unrolled: register pressure)
         const int blk = 3 * s + kb;
         const unsigned char* wb = lds + fr * RB + kb * 64 + fg * 16;
-        constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-        constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
 #pragma unroll
         for (int p = 0; p < NPAIR; ++p) {
           const int j0 = 2 * p, j1 = 2 * p + 1 < kVqTPW ? 2 * p + 1 : 2 * p;
@@ -559,11 +466,9 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
             cur[0] = vq_compress(vq_load_a(plane_base, aoff[j0] + (unsigned)(blk * 64)));
             cur[1] = two ? vq_compress(vq_load_a(plane_base, aoff[j1] + (unsigned)(blk * 64))) : cur[0];
           }
-          // wave-uniform.  Two row tiles share every B fragment; a slot whose second tile is past the wave's run still
-          // computes it (never stored: at most one tile per wave and k block for nothing, none with 4 or 5 tiles as at
-          // C2) - a third branch for it sinks the second tile's loads behind the branch, where they are issued one at
-          // a time, each waiting for the one before
-          if (two && j0 < ntile) {
+          // the six plane products of this k block on every column tile, for row tile j0 or (two_c) for j0 and j1, which
+          // then share each B fragment, their accumulator chains alternating
+          auto products = [&](auto two_c) {
 #pragma unroll
             for (int nt = 0; nt < CTN; ++nt) {
               bf16x16 b[3];
@@ -571,55 +476,26 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
               for (int pl = 0; pl < 3; ++pl) b[pl] = vq_read_b(wb + pl * PL + nt * 16 * RB);
 #pragma unroll
               for (int q = 0; q < 6; ++q) {
-                acc[j0][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[0].pl[PA[q]], b[PB[q]], acc[j0][nt], cur[0].idx, 0, 0);
-                acc[j1][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[1].pl[PA[q]], b[PB[q]], acc[j1][nt], cur[1].idx, 0, 0);
+                acc[j0][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[0].pl[kB3PA[q]], b[kB3PB[q]], acc[j0][nt], cur[0].idx, 0, 0);
+                if (decltype(two_c)::value)
+                  acc[j1][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[1].pl[kB3PA[q]], b[kB3PB[q]], acc[j1][nt], cur[1].idx, 0, 0);
               }
             }
-          } else if (!two && j0 < ntile) {                  // the odd last row tile
-#pragma unroll
-            for (int nt = 0; nt < CTN; ++nt) {
-              bf16x16 b[3];
-#pragma unroll
-              for (int pl = 0; pl < 3; ++pl) b[pl] = vq_read_b(wb + pl * PL + nt * 16 * RB);
-#pragma unroll
-              for (int q = 0; q < 6; ++q)
-                acc[j0][nt] = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(cur[0].pl[PA[q]], b[PB[q]], acc[j0][nt], cur[0].idx, 0, 0);
-            }
-          }
+          };
+          // wave-uniform.  Two row tiles share every B fragment; a slot whose second tile is past the wave's run still
+          // computes it (never stored: at most one tile per wave and k block for nothing, none with 4 or 5 tiles as at
+          // C2) - a third branch for it sinks the second tile's loads behind the branch, where they are issued one at
+          // a time, each waiting for the one before
+          if (two && j0 < ntile) products(std::true_type{});
+          else if (!two && j0 < ntile) products(std::false_type{});      // the odd last row tile
         }
       }
     }
 
-    // ---- epilogue: the pass's tiles leave the registers (C layout: rows 4 fg + q, column slot fr) ----
+    // ---- epilogue: the pass's tiles leave the registers ----
 #pragma unroll
-    for (int j = 0; j < kVqTPW; ++j) {
-      if (j < ntile) {
-        const int rbase = r0 + (tbase + j) * 16 + 4 * fg;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int row = rbase + q;
-          if (row < r1) {
-            float* prow = P + (size_t)row * D + col0;
-            static_assert(CTN >= 4, "a column part holds at least the interleaved group");
-            {
-              const f32x4 v = {acc[j][0][q], acc[j][1][q], acc[j][2][q], acc[j][3][q]};
-              const int c = 4 * fr;
-              if (c + 4 <= ncol) *reinterpret_cast<f32x4*>(prow + c) = v;
-              else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  if (c + e < ncol) prow[c + e] = v[e];
-              }
-            }
-#pragma unroll
-            for (int nt = 4; nt < CTN; ++nt) {
-              const int c = nt * 16 + fr;
-              if (c < ncol) prow[c] = acc[j][nt][q];
-            }
-          }
-        }
-      }
-    }
+    for (int j = 0; j < kVqTPW; ++j)
+      if (j < ntile) tab_store_tiles<CTN>(acc[j], P, D, r0 + (tbase + j) * 16, r1, col0, ncol, fr, fg);
   }
 }
 
@@ -668,8 +544,7 @@ struct UpdB3Args {
 template <int CTN, bool FL>
 __device__ __forceinline__ void update_b3_part(const UpdB3Args& a, unsigned char* lds, int col0, bool first_part,
                                                int chunk, int nchunks) {
-  constexpr int RB = kTabSlots * 16;
-  constexpr int PL = kTabNTH * 16 * RB;
+  constexpr int RB = kTabRowB, PL = kTabPlaneB;
   constexpr int NKB = kTabNKB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -685,7 +560,7 @@ __device__ __forceinline__ void update_b3_part(const UpdB3Args& a, unsigned char
     Bl[j] = (j < ncol && a.bias) ? a.bias[col0 + j] : 0.f;
     Sl[j] = j < ncol ? a.w_s[col0 + j] : 0.f;
   }
-  {   // weight planes of this column part (self block: columns 0..D-1 of e2e_linear.weight)
+  {   // weight planes of this column part (self block: columns 0..D-1 of e2e_linear.weight; see tables_b3_part)
     const int total = tab_stage_rows(CTN) * kTabSlots * 2;
     constexpr int UN = 6;
     for (int base = 0; base < total; base += 512 * UN) {
@@ -773,11 +648,7 @@ __device__ __forceinline__ void update_b3_part(const UpdB3Args& a, unsigned char
 #pragma unroll
       for (int nt = 4; nt < CTN; ++nt) addt[nt - 4][q] = *reinterpret_cast<const float*>(addb + (ro + ctB[nt - 4]));
     }
-    float mrow = 0.f;
-    {
-      const int srow = min(rbase + (2 * (fr & 1) + ((fr >> 1) & 1)), a.M - 1);
-      mrow = a.mask[srow];
-    }
+    const float mrow = a.mask[min(rbase + row16_sum4_index(fr), a.M - 1)];
     __builtin_amdgcn_sched_barrier(0);
     f32x4 acc[CTN];
 #pragma unroll
@@ -786,43 +657,19 @@ __device__ __forceinline__ void update_b3_part(const UpdB3Args& a, unsigned char
     // one base register per LDS plane (made opaque once per tile: keeps the loop-invariant plane reads inside the loop)
     const unsigned char* wbp[3];
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) {
-      unsigned o = (unsigned)(fr * RB + fg * 16 + pl * PL);
-      asm volatile("" : "+v"(o));
-      wbp[pl] = lds + o;
-    }
-    constexpr int PA[6] = {1, 2, 0, 1, 0, 0};
-    constexpr int PB[6] = {1, 0, 2, 0, 1, 0};
+    for (int pl = 0; pl < 3; ++pl) wbp[pl] = lds + (unsigned)opaque(fr * RB + fg * 16 + pl * PL);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
       bf16x8 ap[3];
       // only the LAST k block can reach past D (the launcher admits 192 < D <= 208): no select in the others
       const bool kok = kb < NKB - 1 || 32 * kb + 8 * fg <= kmax;
       const Split3 s0 = split3(kok ? ra[kb][0] : zero4);
       const Split3 s1 = split3(kok ? ra[kb][1] : zero4);
-      ap[0] = __builtin_bit_cast(bf16x8, (u32x4){s0.hi.x, s0.hi.y, s1.hi.x, s1.hi.y});
-      ap[1] = __builtin_bit_cast(bf16x8, (u32x4){s0.mid.x, s0.mid.y, s1.mid.x, s1.mid.y});
-      ap[2] = __builtin_bit_cast(bf16x8, (u32x4){s0.lo.x, s0.lo.y, s1.lo.x, s1.lo.y});
+      b3_pack_a(s0, s1, ap);
       ra[kb][0] = a_piece(ro_next, kb, 0);                   // refill: the next tile's k block kb
       ra[kb][1] = a_piece(ro_next, kb, 1);
 #pragma unroll
-      for (int nt = 0; nt < CTN; nt += 2) {
-        bf16x8 b0[3], b1[3];
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          b0[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wbp[pl] + (nt * 16 * RB + kb * 64)));
-          b1[pl] = b0[pl];
-          if (nt + 1 < CTN)
-            b1[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4*>(wbp[pl] + ((nt + 1) * 16 * RB + kb * 64)));
-        }
-#pragma unroll
-        for (int p = 0; p < 6; ++p) {
-          acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[PA[p]], b0[PB[p]], acc[nt], 0, 0, 0);
-          if (nt + 1 < CTN)
-            acc[nt + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap[PA[p]], b1[PB[p]], acc[nt + 1], 0, 0, 0);
-        }
-      }
+      for (int nt = 0; nt < CTN; nt += 2) b3_products_pair<CTN>(acc, nt, ap, wbp[0], wbp[1], wbp[2], kb * 64);
     }
     // epilogue from the registers
     float part[4] = {0.f, 0.f, 0.f, 0.f};
@@ -851,8 +698,8 @@ __device__ __forceinline__ void update_b3_part(const UpdB3Args& a, unsigned char
       }
     }
     {
-      const float tot = row16_sum4_b3(part, lane);
-      const int srow = rbase + (2 * (fr & 1) + ((fr >> 1) & 1));
+      const float tot = row16_sum4(part, lane);
+      const int srow = rbase + row16_sum4_index(fr);
       if (fr < 4 && srow < a.M) {
         // this part's share of the score; the first part carries bias and mask term (fp32 adds: a masked slot's
         // share is exactly -1e11 and stays there when the other part's share is added)
@@ -877,21 +724,29 @@ __global__ __launch_bounds__(512, 2) void k_update_b3(UpdB3Args a, int nchunks) 
   else if (NT - a.ct0 == 6) update_b3_part<6, FL>(a, lds, a.ct0 * 16, false, chunk, nchunks);
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+// Hidden sizes the three kernels take: D a multiple of 8 (a lane's 8 consecutive k), kTabNKB k blocks of 32 and two
+// column parts of 7 + 6 tiles, i.e. 192 < D <= 208
+constexpr int kTabNT = 2 * kTabNTH - 1;
+static bool b3_shape_ok(int32_t D) { return D % 8 == 0 && (D + 31) / 32 == kTabNKB && (D + 15) / 16 == kTabNT; }
+
+// Row chunks of a launch over `tiles` 16-row tiles: `target` of them (from the CU count), at least one, and no more than
+// leave a chunk 8 tiles (one per wave)
+static int b3_row_chunks(int target, long long tiles) {
+  int chunks = target < 1 ? 1 : target;
+  if ((long long)chunks * 8 > tiles) chunks = (int)((tiles + 7) / 8);
+  return chunks;
+}
+
 int update_b3_launch(const float* h, const float* nbr, const float* W, const float* b, const float* w_s, const float* b_s,
                      const float* mask, float* h_out, float* score, int64_t BN, int32_t D, int32_t ldw,
                      hipStream_t stream) {
-  return update_b3_launch_z(h, nbr, W, b, w_s, b_s, mask, h_out, score, BN, D, ldw, stream, false);
-}
-
-int update_b3_launch_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
-                       const float* b_s, const float* mask, float* h_out, float* score, int64_t BN, int32_t D,
-                       int32_t ldw, hipStream_t stream, bool score_zeroed) {
-  return update_b3_launch_f(h, nbr, nullptr, W, b, w_s, b_s, mask, h_out, score, BN, D, ldw, stream, score_zeroed);
+  return update_b3_launch_f(h, nbr, nullptr, W, b, w_s, b_s, mask, h_out, score, BN, D, ldw, stream, false);
 }
 
 bool update_b3_shape_ok(int64_t BN, int32_t D, int32_t ldw) {
   // (32-bit byte offsets from the kernel's base pointers: the zero row behind nbr included)
-  return !(D % 8 || (D + 31) / 32 != kTabNKB || (D + 15) / 16 != 13 || BN < 8192 || (BN + 1) * D * 4 >= ((int64_t)1 << 32) || ldw % 4);
+  return b3_shape_ok(D) && BN >= 8192 && (BN + 1) * D * 4 < ((int64_t)1 << 32) && ldw % 4 == 0;
 }
 
 int update_b3_launch_f(const float* h, const float* nbr, const uint8_t* add_flag, const float* W, const float* b,
@@ -910,10 +765,7 @@ int update_b3_launch_f(const float* h, const float* nbr, const uint8_t* add_flag
     const int rc = device_cu_count(&cus);
     if (rc) return rc;
   }
-  const long long U = (BN + 15) / 16;
-  int chunks = cus / 2;
-  if (chunks < 1) chunks = 1;
-  if ((long long)chunks * 8 > U) chunks = (int)((U + 7) / 8);
+  const int chunks = b3_row_chunks(cus / 2, (BN + 15) / 16);
   if (!score_zeroed) GNNRAG_HIP(hipMemsetAsync(score, 0, (size_t)BN * sizeof(float), stream));
   static DeviceMask cap, cap_f;
   {
@@ -930,8 +782,7 @@ int update_b3_launch_f(const float* h, const float* nbr, const uint8_t* add_flag
 size_t tables_vq_planes_bytes(int64_t R1) { return (size_t)2 * 3 * R1 * kVqRowB; }
 
 bool tables_vq_shape_ok(int32_t D, int32_t I) {
-  return D % 8 == 0 && (D + 31) / 32 == kTabNKB && (D + 15) / 16 == 13 && I >= 1 &&
-         (size_t)I * D * sizeof(float) <= (size_t)kTabQBytes;
+  return b3_shape_ok(D) && I >= 1 && (size_t)I * D * sizeof(float) <= (size_t)kTabQBytes;
 }
 
 int tables_vq_launch(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
@@ -978,9 +829,8 @@ int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* i
 
 int tables_b3_launch(const gnnrag_csr* csr, const float* T_fwd, const float* T_inv, const float* ins, const float* W,
                      float* P, int32_t D, int32_t I, hipStream_t stream) {
-  // shapes of the kernel: D a multiple of 8 (a lane's 8 consecutive k), at most 2 x 7 column tiles, 4-byte offsets
-  // that keep float4 accesses aligned, enough rows to fill the chip
-  if (D % 8 || (D + 31) / 32 != kTabNKB || (D + 15) / 16 != 13 || csr->rel_total < 1024) return GNNRAG_E_UNSUPPORTED;
+  // shapes of the kernel: b3_shape_ok, 4-byte offsets that keep float4 accesses aligned, enough rows to fill the chip
+  if (!b3_shape_ok(D) || csr->rel_total < 1024) return GNNRAG_E_UNSUPPORTED;
   if (!aligned16(T_fwd, T_inv, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
   TabArgs a;
   memset(&a, 0, sizeof(a));
@@ -996,9 +846,7 @@ int tables_b3_launch(const gnnrag_csr* csr, const float* T_fwd, const float* T_i
     if (rc) return rc;
   }
   const long long U = ((long long)a.M + 15) / 16;
-  int chunks = cus / (2 * parts);
-  if (chunks < 1) chunks = 1;
-  if ((long long)chunks * 8 > U) chunks = (int)((U + 7) / 8);
+  const int chunks = b3_row_chunks(cus / (2 * parts), U);
   const int tiles_per_wave = (int)((((U + chunks - 1) / chunks) + 7) / 8);         // largest w1 - w0 of the floor split
   a.npass = (tiles_per_wave + kTabTPW - 1) / kTabTPW;
   const size_t lds = 160 * 1024;          // three weight planes, 64 B of slack, instruction rows

@@ -832,7 +832,7 @@ def test_relation_tables_from_relation_planes(dev, B, R, used, I, N, D):
 def test_update_bf16x3_w_resident_vs_exact_fp32(dev, M, D):
     """k_update_b3 against the exact-fp32 kernel on random data at both hidden sizes it admits.  Regression: at
     D = 208 the 6-tile column part ends at its last staged LDS row, and the last k block of column 207 read 32 bytes of
-    an UNWRITTEN row behind it - 0 x stale Inf/NaN = NaN, relu -> 0 for some rows (tables_b3.hip: tab_stage_rows)."""
+    an UNWRITTEN row behind it - 0 x stale Inf/NaN = NaN, relu -> 0 for some rows (b3_tile.h: tab_stage_rows)."""
     from gnnrag_amd import ops
     g = torch.Generator(device="cpu").manual_seed(M + D)
     r = lambda *shape: torch.randn(*shape, generator=g).to(dev)
