@@ -7,8 +7,12 @@ namespace gnnrag {
 // tables_vq_launch that ALSO zeroes `zero_n` floats at `zero` (may be null): the layer driver passes the layer's score
 // buffer, onto which k_update_b3 accumulates its two column parts' shares - that kernel's own memset launch (~5 us
 // per layer) is then skipped (update_score_fused_z(..., score_zeroed = true)).
+// packed: `planes` is the packed sparse operand (gnnrag_rel_transform_packed: [2][R1][1408 B] of one layer) instead of
+// the public planes - what the layer driver passes
 int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
-                       int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream);
+                       int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream, bool packed);
+// bytes of one layer's packed operand (fits the slot of tables_vq_planes_bytes: 2 * 1408 against 6 * 896 per row)
+size_t tables_vq_packed_bytes(int64_t R1);
 
 // Row-gated form of the self-block update: `nbr` holds valid data only in the rows whose byte in add_flag is non-zero,
 // every other row reads the ZERO ROW behind the buffer (row index BN), so the unflagged rows of nbr are never
@@ -44,5 +48,9 @@ int update_score_fused_z(const float* h, const float* nbr, const float* W, const
 // rel_transform.hip: whether gnnrag_rel_transform takes these operands (then, and only then, it writes T and the planes)
 bool rel_transform_accepts(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D, int32_t L,
                            const gnnrag_layer_params* layers, int32_t pos_rows, const float* T_out, const void* planes_out);
+// gnnrag_rel_transform with the planes (planes_out), the packed sparse operand (packed_out) or neither beside T
+int rel_transform_launch(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D, int32_t L,
+                         const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out, void* planes_out,
+                         void* packed_out, gnnrag_stream_t stream);
 
 }  // namespace gnnrag

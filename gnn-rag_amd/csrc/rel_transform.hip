@@ -30,6 +30,7 @@ struct RelTArgs {
   const float* add[kRtMaxL][2];   // pos_emb{j} / pos_emb_inv{j} [add_rows, N] or null
   float* C;                       // [L][2][M][N]
   unsigned short* planes;         // null or [L][2][3][M][kPlaneRow] bf16: planes of relu(T) | relu(-T), see below
+  unsigned char* packed;          // null or [L][2][M][kPackRowB]: planes of |T| and its signs, see below (never both)
   int M, K, N, add_rows;
 };
 
@@ -37,6 +38,19 @@ struct RelTArgs {
 // planes (exact 3-way split) of [relu(T[r, :]) | relu(-T[r, :])], each half padded with zeros to 7 k blocks of 32.
 constexpr int kPlaneHalf = 224;
 constexpr int kPlaneRow = 2 * kPlaneHalf;     // bf16 elements per plane row (896 bytes)
+// The same operand as the sparse product of k_tables_vq takes it ("packed"): of relu(T) and relu(-T) at most one is not
+// zero, so the compressed left operand of v_smfmac is the three planes of |T| plus one sign bit per element.  Per (layer,
+// direction, relation row) kPackRowB bytes: three planes of |T| (kPlaneHalf bf16 each, k >= D zero), then 64 index bytes.
+// The index byte of the four k of group q = k / 4 is 0x88 | s0 | s1 << 2 | s2 << 4 | s3 << 6 with s = (T[r, k] < 0): two
+// of them are the finished 16-bit index word of a lane's 8 k (positions 0 / 1 for the first value of a pair, 2 / 3 for the
+// second).  They are stored in the order the lanes read them - the byte of q at (q % 8 / 2) * 16 + (q / 8) * 2 + q % 2,
+// i.e. the word of (k block q / 8, lane group fg = q % 8 / 2) at fg * 16 + block * 2 - so that a lane's planes and its
+// index word share one lane offset (fg * 16).  The 8 bytes no k stands behind are 0.
+// -0.0 and values whose three planes are all zero (fp32 denormals below the smallest bf16) may get either sign bit: their
+// operand is zero, and 0 times either half of the (finite) right operand adds nothing to a sum that starts at +0.
+constexpr int kPackPlaneB = kPlaneHalf * 2;             // bytes per plane of a packed row (448)
+constexpr int kPackIdxB = 3 * kPackPlaneB;              // offset of the index bytes (1344)
+constexpr int kPackRowB = kPackIdxB + 64;               // 1408
 
 // TPW: 16-row tiles per wave (1: few relation rows, many small workgroups; 4: large vocabularies, the weight slice
 // staged once per 256 rows)
@@ -74,6 +88,7 @@ __global__ __launch_bounds__(256) void k_rel_transform(RelTArgs g) {
   const float* __restrict__ addp = g.add[j][d];
   float* __restrict__ cp = g.C + ((size_t)(2 * j + d) * g.M) * g.N;
   unsigned short* pp = g.planes ? g.planes + ((size_t)(2 * j + d) * 3 * g.M) * kPlaneRow : nullptr;
+  unsigned char* pk = g.packed ? g.packed + ((size_t)(2 * j + d) * g.M) * kPackRowB : nullptr;
 
 #pragma unroll 1
   for (int t = 0; t < TPW; ++t) {
@@ -107,7 +122,7 @@ __global__ __launch_bounds__(256) void k_rel_transform(RelTArgs g) {
       }
     }
     // accumulator element r of lane (fr, fg), tile a = C[row0 + 4 fg + r][colg + 4 fr + a]
-    if (!in_T && !(pp && in_pad)) continue;
+    if (!in_T && !(pp && in_pad) && !pk) continue;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = row0 + 4 * fg + r;
@@ -130,6 +145,20 @@ __global__ __launch_bounds__(256) void k_rel_transform(RelTArgs g) {
           *reinterpret_cast<uint2*>(pp + (size_t)g.M * kPlaneRow + e) = sp.mid;
           *reinterpret_cast<uint2*>(pp + (size_t)2 * g.M * kPlaneRow + e) = sp.lo;
         }
+      }
+      if (pk) {
+        // the same register values, packed: split3(|v|) and the signs; padding columns get zero planes and "all +"
+        unsigned char* rowp = pk + (size_t)row * kPackRowB;
+        if (c4 < kPlaneHalf) {
+          const Split3 sp = split3(__builtin_elementwise_abs(v));
+          *reinterpret_cast<uint2*>(rowp + 2 * c4) = sp.hi;
+          *reinterpret_cast<uint2*>(rowp + kPackPlaneB + 2 * c4) = sp.mid;
+          *reinterpret_cast<uint2*>(rowp + 2 * kPackPlaneB + 2 * c4) = sp.lo;
+        }
+        const int q = c4 >> 2;                               // (the column groups run on to 256: q < 64)
+        const unsigned ix = 0x88u | (unsigned)(v[0] < 0.f) | (unsigned)(v[1] < 0.f) << 2 | (unsigned)(v[2] < 0.f) << 4 |
+                            (unsigned)(v[3] < 0.f) << 6;
+        rowp[kPackIdxB + ((q & 7) >> 1) * 16 + (q >> 3) * 2 + (q & 1)] = (unsigned char)(c4 < kPlaneHalf ? ix : 0u);
       }
     }
   }
@@ -162,16 +191,24 @@ bool gnnrag::rel_transform_accepts(const float* relfeat_fwd, const float* relfea
   return (size_t)64 * ((D + 15) / 16) * 16 * sizeof(float) <= 160 * 1024;   // 64 columns x K padded to k groups in LDS
 }
 
-extern "C" int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D,
-                                    int32_t L, const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out,
-                                    void* planes_out, gnnrag_stream_t stream) {
+extern "C" size_t gnnrag_rel_packed_bytes(int64_t R1, int32_t D, int32_t L) {
+  if (R1 <= 0 || D <= 0 || D > kPlaneHalf || L <= 0) return 0;
+  return (size_t)L * 2 * R1 * kPackRowB;
+}
+
+// the projections with the planes (planes_out), the packed operand (packed_out) or neither; never both
+int gnnrag::rel_transform_launch(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D, int32_t L,
+                                 const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out, void* planes_out,
+                                 void* packed_out, gnnrag_stream_t stream) {
+  if (planes_out && packed_out) return GNNRAG_E_BADARG;
+  void* const side_out = planes_out ? planes_out : packed_out;
   if (!relfeat_fwd || !relfeat_inv || !layers || !T_out || R1 < 0 || D <= 0 || L <= 0 || pos_rows < 0)
     return GNNRAG_E_BADARG;
   for (int j = 0; j < L; ++j) {
     if (!layers[j].W_rel) return GNNRAG_E_BADARG;
     if ((layers[j].pos_fwd == nullptr) != (layers[j].pos_inv == nullptr)) return GNNRAG_E_BADARG;
   }
-  if (!gnnrag::rel_transform_accepts(relfeat_fwd, relfeat_inv, R1, D, L, layers, pos_rows, T_out, planes_out))
+  if (!gnnrag::rel_transform_accepts(relfeat_fwd, relfeat_inv, R1, D, L, layers, pos_rows, T_out, side_out))
     return GNNRAG_E_UNSUPPORTED;
   if (R1 == 0) return 0;
   for (int j0 = 0; j0 < L; j0 += kRtMaxL) {
@@ -189,10 +226,11 @@ extern "C" int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfe
     }
     g.C = T_out + (size_t)j0 * 2 * R1 * D;
     g.planes = planes_out ? (unsigned short*)planes_out + (size_t)j0 * 2 * 3 * R1 * kPlaneRow : nullptr;
+    g.packed = packed_out ? (unsigned char*)packed_out + (size_t)j0 * 2 * R1 * kPackRowB : nullptr;
     g.M = (int)R1; g.K = D; g.N = D;
     g.add_rows = (int)(pos_rows < R1 ? pos_rows : R1);
-    // with planes the column groups run on to 224 columns: the part past D only writes the zero padding
-    const unsigned gy = (unsigned)(((planes_out ? kPlaneHalf : D) + 63) / 64), gz = (unsigned)(2 * n);
+    // with planes / the packed operand the column groups run on to 224 columns: the part past D only writes the padding
+    const unsigned gy = (unsigned)(((side_out ? kPlaneHalf : D) + 63) / 64), gz = (unsigned)(2 * n);
     const size_t lds = (size_t)64 * ((D + 15) / 16) * 16 * sizeof(float);      // 64 columns x K padded to k groups
     static DeviceMask cap1, cap4;
     if (R1 > 2048) {
@@ -207,4 +245,17 @@ extern "C" int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfe
     GNNRAG_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D,
+                                    int32_t L, const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out,
+                                    void* planes_out, gnnrag_stream_t stream) {
+  return gnnrag::rel_transform_launch(relfeat_fwd, relfeat_inv, R1, D, L, layers, pos_rows, T_out, planes_out, nullptr, stream);
+}
+
+extern "C" int gnnrag_rel_transform_packed(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D,
+                                           int32_t L, const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out,
+                                           void* packed_out, gnnrag_stream_t stream) {
+  if (!packed_out) return GNNRAG_E_BADARG;
+  return gnnrag::rel_transform_launch(relfeat_fwd, relfeat_inv, R1, D, L, layers, pos_rows, T_out, nullptr, packed_out, stream);
 }

@@ -203,7 +203,9 @@ static LayerWs layer_ws(const gnnrag_csr* csr, int32_t D, int32_t I) {
   const size_t BN = (size_t)csr->B * csr->N;
   w.T_fwd = cv.take((size_t)2 * csr->R1 * D * sizeof(float));          // [2][R1][D]: forward, inverse
   w.T_inv = w.T_fwd + (size_t)csr->R1 * D * sizeof(float);
-  // bf16 planes of relu(+-T) for the V form of the relation tables (one layer), where that kernel's shapes apply
+  // the relation operand of the V form of the relation tables (one layer), where that kernel's shapes apply: the slot has
+  // the size of the public bf16 planes of relu(+-T); the layer sequence writes the smaller packed form (planes of |T| and
+  // sign bits, tables_vq_packed_bytes) into it
   w.planes = cv.take(tables_vq_shape_ok(D, I) ? tables_vq_planes_bytes(csr->R1) : 0);
   // the two paths never run in the same call: their big buffers share one region
   const size_t a_bytes = BN * 2 * I * D * sizeof(float);
@@ -338,7 +340,7 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     rc = GNNRAG_E_UNSUPPORTED;
     bool score_zeroed = false;    // the V-form table kernel also zeroes the score the update accumulates onto
     if (planes && math != GNNRAG_MATH_FP32 && csr->rel_total > 0) {
-      rc = tables_vq_launch_z(csr, planes, ins, W_e2e, P, D, I, one_dir ? only : -1, score_out, BN, (hipStream_t)stream);
+      rc = tables_vq_launch_z(csr, planes, ins, W_e2e, P, D, I, one_dir ? only : -1, score_out, BN, (hipStream_t)stream, true);
       score_zeroed = rc == 0;
     }
     if (rc == GNNRAG_E_UNSUPPORTED) rc = gnnrag_relation_tables(csr, T_fwd, T_inv, ins, W_e2e, P, D, I, math, stream);
@@ -362,13 +364,14 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
 }
 
 // T[j][d] = rel_linear{j}(rel_features_d) (+ pos_emb{j}_d) for n layers into T [n][2][R1][D]: once per relation
-// row, not once per fact; all layers in one launch when the float4 kernel applies (rel_transform.hip)
+// row, not once per fact; all layers in one launch when the float4 kernel applies (rel_transform.hip).  `planes`: null or
+// where that kernel also writes the layers' packed sparse operands for k_tables_vq ([n][2][R1][1408 B])
 static int rel_projections(const gnnrag_csr* csr, int32_t n, const gnnrag_layer_params* layers,
                            const float* relfeat_fwd, const float* relfeat_inv, int32_t pos_rows, float* T,
                            void* planes, bool* planes_written, int32_t D, int32_t math, gnnrag_stream_t stream) {
   *planes_written = false;
   if ((D & 3) == 0) {
-    const int rc = gnnrag_rel_transform(relfeat_fwd, relfeat_inv, csr->R1, D, n, layers, pos_rows, T, planes, stream);
+    const int rc = rel_transform_launch(relfeat_fwd, relfeat_inv, csr->R1, D, n, layers, pos_rows, T, nullptr, planes, stream);
     if (rc == 0) *planes_written = planes != nullptr;
     // unaligned operands: the k-tiled kernel below (its scalar loaders take any address); the planes stay unwritten,
     // which the caller learns through *planes_written and then builds the tables from T (gnnrag_relation_tables)
@@ -448,7 +451,7 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
   float* T0 = (float*)(base + w.T_fwd);
   float* Tall = (float*)(base + w.total);
   const bool want_planes = planes_wanted(csr, D, I, path, math);
-  const size_t plane_bytes = tables_vq_planes_bytes(csr->R1);
+  const size_t plane_bytes = tables_vq_packed_bytes(csr->R1);      // (the L packed layers lie at the head of the L plane slots)
   char* planes_all = base + w.total + align_up((size_t)L * 2 * RD * sizeof(float), 256);
   bool planes_written = false;
   const bool reuse = upfront && (path & GNNRAG_PATH_REUSE_PROJ) != 0;

@@ -1,6 +1,7 @@
 // The bf16x3 W-resident kernels of the fused path (gfx950):
 //   k_tables_b3   relation tables, operand relu(T * ins) generated in registers (a lone gnnrag_relation_tables call)
-//   k_tables_vq   relation tables in "V form" from pre-split relation planes (what a layer / stack call runs)
+//   k_tables_vq   relation tables in "V form" from pre-split relation planes (<false>: the public planes; <true>: the
+//                 packed sparse operand, what a layer / stack call runs)
 //   k_update_b3   the self-block update h' = relu(h W^T + b + nbr) with the fused score
 // They share the LDS weight-plane layout (three bf16 planes of an exact 3-way split, 26-slot row stride), the six
 // plane products on v_mfma_f32_16x16x32_bf16 with fp32 accumulation, and the register epilogue: b3_tile.h holds each of
@@ -401,9 +402,29 @@ __device__ __forceinline__ VqA vq_compress(const VqRaw& r) {
   return o;
 }
 
-template <int CTN>
+// The packed operand (rel_transform.hip: k_rel_transform writes it once per projection): per relation row the three planes
+// of |T| (kVqHalf bf16 each) and 64 index bytes, the 16-bit index word of (k block, lane group fg) at fg * 16 + block * 2
+// - already what vq_compress builds.  Three 16-byte loads and one 16-bit load per (row tile, k block) on one lane offset,
+// against six 16-byte loads, ~55 VALU instructions and 24 transient registers for the public planes.
+constexpr int kVqPackPlaneB = kVqHalf * 2;           // bytes per plane of a packed row
+constexpr int kVqPackIdxB = 3 * kVqPackPlaneB;       // offset of the index bytes
+constexpr int kVqPackRowB = kVqPackIdxB + 64;        // 1408
+__device__ __forceinline__ VqA vq_load_packed(const unsigned char* row_base, unsigned off, int blk) {
+  VqA o;
+  // 32-bit offsets from the uniform base (scalar base + lane offset).  Folding the k block into the base and the rest into
+  // immediates - (row_base + blk * 64) + off - makes the compiler form 64-bit lane addresses instead: 256 registers, 52 B scratch
+#pragma unroll
+  for (int pl = 0; pl < 3; ++pl)
+    o.pl[pl] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(row_base + (off + (unsigned)(pl * kVqPackPlaneB + blk * 64))));
+  o.idx = *reinterpret_cast<const unsigned short*>(row_base + (off + (unsigned)(kVqPackIdxB + blk * 2)));
+  return o;
+}
+
+// PACKED: the A operand comes from the packed form (the layer sequence) instead of the public planes - the only difference
+template <int CTN, bool PACKED>
 __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* lds, int col0) {
   constexpr int RB = kTabRowB, PL = kTabPlaneB;
+  constexpr unsigned AROWB = PACKED ? kVqPackRowB : kVqRowB;      // bytes of a relation row of the A operand
   constexpr int NPAIR = (kVqTPW + 1) / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fg = lane >> 4;
@@ -415,8 +436,8 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
   const int ncol = min(CTN * 16, D - col0);
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   float* P = a.P + (size_t)d * a.M * D;
-  const unsigned char* planes = a.planes + (size_t)d * 3 * a.R1 * kVqRowB;
-  const size_t plane_stride = (size_t)a.R1 * kVqRowB;
+  const unsigned char* planes = a.planes + (size_t)d * (PACKED ? 1 : 3) * a.R1 * AROWB;
+  const size_t plane_stride = (size_t)a.R1 * kVqRowB;          // (public planes)
 
   // 16-row tiles of the question start at its first row; the chunk's tiles are dealt out contiguously to the 8 waves
   const int U = (r1 - r0 + 15) >> 4;
@@ -442,13 +463,14 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
 #pragma unroll
     for (int j = 0; j < kVqTPW; ++j) {
       const int m = min(r0 + (tbase + (j < ntile ? j : 0)) * 16 + fr, r1 - 1);
-      aoff[j] = (unsigned)a.rows[m].y * (unsigned)kVqRowB + (unsigned)fg * 16u;
+      aoff[j] = (unsigned)a.rows[m].y * AROWB + (unsigned)fg * 16u;
     }
     const unsigned char* const plane_base[3] = {planes, planes + plane_stride, planes + 2 * plane_stride};
 
-    // A operands are requested where they are used: the pair's 12 plane loads (L2 hits) go out together and the other
-    // wave of the SIMD has a pair's products (84 instructions) to issue meanwhile.  Holding the next pair's raw loads
-    // beside the pair in use (48 registers, or 37 in a two-step form) spills: 140 accumulators + 26 A + 2 x 24 B.
+    // A operands are requested where they are used: the pair's 12 plane loads (packed: 6 + 2 index words; L2 hits) go out
+    // together and the other wave of the SIMD has a pair's products (84 instructions) to issue meanwhile.  Holding the
+    // next pair's raw loads beside the pair in use (48 registers, or 37 in a two-step form) spills: 140 accumulators +
+    // 26 A + 2 x 24 B; so does holding the next pair's first PACKED tile (13 registers: 12 B of scratch).
     for (int s = 0; s < 3; ++s) {           // k blocks 0-2, 3-5, 6 (rolled: register pressure)
       __syncthreads();                                        // q rows staged / the previous stage's fragment reads done
       const int nblk = s < 2 ? 3 : 1;
@@ -462,7 +484,10 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
           const int j0 = 2 * p, j1 = 2 * p + 1 < kVqTPW ? 2 * p + 1 : 2 * p;
           const bool two = 2 * p + 1 < kVqTPW;
           VqA cur[2];
-          {
+          if constexpr (PACKED) {
+            cur[0] = vq_load_packed(planes, aoff[j0], blk);
+            cur[1] = two ? vq_load_packed(planes, aoff[j1], blk) : cur[0];
+          } else {
             cur[0] = vq_compress(vq_load_a(plane_base, aoff[j0] + (unsigned)(blk * 64)));
             cur[1] = two ? vq_compress(vq_load_a(plane_base, aoff[j1] + (unsigned)(blk * 64))) : cur[0];
           }
@@ -499,6 +524,7 @@ __device__ __forceinline__ void tables_vq_part(const VqArgs& a, unsigned char* l
   }
 }
 
+template <bool PACKED>
 __global__ __launch_bounds__(512, 2) void k_tables_vq(VqArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   if (a.zero) {               // every workgroup zeroes its share (a few floats per thread)
@@ -511,8 +537,8 @@ __global__ __launch_bounds__(512, 2) void k_tables_vq(VqArgs a) {
   const int ctn = h == 0 ? a.ct0 : NT - a.ct0;
   const int col0 = h == 0 ? 0 : a.ct0 * 16;
   switch (ctn) {
-    case 6: tables_vq_part<6>(a, lds, col0); break;
-    case 7: tables_vq_part<7>(a, lds, col0); break;
+    case 6: tables_vq_part<6, PACKED>(a, lds, col0); break;
+    case 7: tables_vq_part<7, PACKED>(a, lds, col0); break;
     default: break;
   }
 }
@@ -782,6 +808,8 @@ int update_b3_launch_f(const float* h, const float* nbr, const uint8_t* add_flag
 }
 
 size_t tables_vq_planes_bytes(int64_t R1) { return (size_t)2 * 3 * R1 * kVqRowB; }
+size_t tables_vq_packed_bytes(int64_t R1) { return (size_t)2 * R1 * kVqPackRowB; }
+static_assert(2 * kVqPackRowB <= 2 * 3 * kVqRowB, "a layer's packed operand fits the slot of its planes");
 
 bool tables_vq_shape_ok(int32_t D, int32_t I) {
   return b3_shape_ok(D) && I >= 1 && (size_t)I * D * sizeof(float) <= (size_t)kTabQBytes;
@@ -789,12 +817,14 @@ bool tables_vq_shape_ok(int32_t D, int32_t I) {
 
 int tables_vq_launch(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
                      int32_t I, int32_t only_dir, hipStream_t stream) {
-  return tables_vq_launch_z(csr, planes, ins, W, P, D, I, only_dir, nullptr, 0, stream);
+  return tables_vq_launch_z(csr, planes, ins, W, P, D, I, only_dir, nullptr, 0, stream, false);
 }
 
 int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W, float* P, int32_t D,
-                       int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream) {
+                       int32_t I, int32_t only_dir, float* zero, int64_t zero_n, hipStream_t stream, bool packed) {
   if (!tables_vq_shape_ok(D, I) || csr->rel_total < 1024 || only_dir > 1) return GNNRAG_E_UNSUPPORTED;
+  // (32-bit byte offsets from the operand's base)
+  if ((int64_t)csr->R1 * (packed ? kVqPackRowB : kVqRowB) >= ((int64_t)1 << 32)) return GNNRAG_E_UNSUPPORTED;
   if (!aligned16(planes, ins, W, P)) return GNNRAG_E_UNSUPPORTED;
   VqArgs a;
   memset(&a, 0, sizeof(a));
@@ -819,12 +849,13 @@ int tables_vq_launch_z(const gnnrag_csr* csr, const void* planes, const float* i
   a.nchunk = nchunk;
   a.zero = zero;
   a.zero_n = zero ? zero_n : 0;
-  static DeviceMask cap;
+  static DeviceMask cap, cap_p;
   {
-    const int rc = raise_lds_cap(k_tables_vq, cap);
+    const int rc = packed ? raise_lds_cap(k_tables_vq<true>, cap_p) : raise_lds_cap(k_tables_vq<false>, cap);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_tables_vq, dim3(csr->B * nchunk, ndir, 2), dim3(512), 160 * 1024, stream, a);
+  if (packed) hipLaunchKernelGGL(k_tables_vq<true>, dim3(csr->B * nchunk, ndir, 2), dim3(512), 160 * 1024, stream, a);
+  else hipLaunchKernelGGL(k_tables_vq<false>, dim3(csr->B * nchunk, ndir, 2), dim3(512), 160 * 1024, stream, a);
   GNNRAG_LAUNCH_CHECK();
   return 0;
 }
@@ -869,4 +900,12 @@ extern "C" int gnnrag_relation_tables_planes(const gnnrag_csr* csr, const void* 
   if (!csr || !planes || !ins || !W || !P || D <= 0 || I <= 0 || csr->rel_total < 0) return GNNRAG_E_BADARG;
   if (csr->rel_total == 0) return 0;
   return gnnrag::tables_vq_launch(csr, planes, ins, W, P, D, I, -1, (hipStream_t)stream);
+}
+
+extern "C" int gnnrag_relation_tables_packed(const gnnrag_csr* csr, const void* packed, const float* ins, const float* W,
+                                             float* P, int32_t D, int32_t I, int32_t only_dir, gnnrag_stream_t stream) {
+  if (!csr || !packed || !ins || !W || !P || D <= 0 || I <= 0 || csr->rel_total < 0 || only_dir < -1 || only_dir > 1)
+    return GNNRAG_E_BADARG;
+  if (csr->rel_total == 0) return 0;
+  return gnnrag::tables_vq_launch_z(csr, packed, ins, W, P, D, I, only_dir, nullptr, 0, (hipStream_t)stream, true);
 }

@@ -398,12 +398,15 @@ def linear(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None
     return out
 
 
-def rel_transform(relfeat: torch.Tensor, relfeat_inv: torch.Tensor, layers, planes: bool = False):
+def rel_transform(relfeat: torch.Tensor, relfeat_inv: torch.Tensor, layers, planes: bool = False, packed: bool = False):
     """Relation projections of all layers in one launch (reasongnn.py:75-79, :102-105):
     ``out[j, d] = rel_linear{j}(rel_features_d) (+ pos_emb{j}_d on its rows)``, d = 0 forward / 1 inverse.
     ``layers``: sequence of (W_rel [D,D], b_rel [D], pos_emb.weight or None, pos_emb_inv.weight or None).
     Returns [L, 2, R1, D]; with ``planes=True`` also the bf16 planes of relu(+-T) ([L, 2, 3, R1, 448] int16 view) that
-    :func:`relation_tables_planes` multiplies."""
+    :func:`relation_tables_planes` multiplies; with ``packed=True`` instead the packed sparse operand (planes of abs(T) and
+    sign bits, [L, 2, R1, 1408] uint8, include/gnnrag.h) that :func:`relation_tables_packed` multiplies."""
+    if planes and packed:
+        raise ValueError("planes and packed are two forms of the same operand: ask for one")
     lib = _lib.load()
     relfeat = _chk(relfeat, "rel_features")
     R1, D = relfeat.shape
@@ -431,10 +434,20 @@ def rel_transform(relfeat: torch.Tensor, relfeat_inv: torch.Tensor, layers, plan
         if nbytes == 0:
             raise _lib.GnnragError("relation planes need a hidden size <= 224")
         pl = _buf((L, 2, 3, R1, nbytes // (L * 6 * R1 * 2)), torch.int16, relfeat.device, "rel_transform: planes")
+    if packed:
+        nbytes = lib.gnnrag_rel_packed_bytes(R1, D, L)
+        if nbytes == 0:
+            raise _lib.GnnragError("the packed relation operand needs a hidden size <= 224")
+        pl = _buf((L, 2, R1, nbytes // (L * 2 * R1)), torch.uint8, relfeat.device, "rel_transform: packed")
     with torch.cuda.device(relfeat.device):
-        _lib.check(lib.gnnrag_rel_transform(relfeat.data_ptr(), relfeat_inv.data_ptr(), R1, D, L, params, pos_rows,
-                                            out.data_ptr(), _ptr(pl), _stream()), "gnnrag_rel_transform")
-    return (out, pl) if planes else out
+        if packed:
+            _lib.check(lib.gnnrag_rel_transform_packed(relfeat.data_ptr(), relfeat_inv.data_ptr(), R1, D, L, params,
+                                                       pos_rows, out.data_ptr(), _ptr(pl), _stream()),
+                       "gnnrag_rel_transform_packed")
+        else:
+            _lib.check(lib.gnnrag_rel_transform(relfeat.data_ptr(), relfeat_inv.data_ptr(), R1, D, L, params, pos_rows,
+                                                out.data_ptr(), _ptr(pl), _stream()), "gnnrag_rel_transform")
+    return (out, pl) if planes or packed else out
 
 
 def relation_tables_planes(plan: "CsrPlan", planes: torch.Tensor, ins: torch.Tensor, W_e2e: torch.Tensor) -> torch.Tensor:
@@ -453,6 +466,30 @@ def relation_tables_planes(plan: "CsrPlan", planes: torch.Tensor, ins: torch.Ten
     with torch.cuda.device(ins.device):
         _lib.check(lib.gnnrag_relation_tables_planes(C.byref(plan.c), planes.data_ptr(), ins.data_ptr(), W_e2e.data_ptr(),
                                                      P.data_ptr(), D, I, _stream()), "gnnrag_relation_tables_planes")
+    return P[:, :plan.rel_total]
+
+
+def relation_tables_packed(plan: "CsrPlan", packed: torch.Tensor, ins: torch.Tensor, W_e2e: torch.Tensor,
+                           only_dir: int = -1) -> torch.Tensor:
+    """:func:`relation_tables_planes` on ONE layer's packed operand (``rel_transform(..., packed=True)[1][j]``,
+    [2, R1, 1408] uint8): ``gnnrag_relation_tables_packed``, the form the layer sequence runs - the same P bit for bit.
+    ``only_dir`` 0 / 1: that direction's tables alone; the other half of the result is zeros."""
+    lib = _lib.load()
+    ins = _chk(ins, "relational_ins")
+    B, I, D = ins.shape
+    if (packed.dtype != torch.uint8 or packed.dim() != 3 or tuple(packed.shape[:2]) != (2, plan.R1)
+            or not packed.is_contiguous() or B != plan.B):
+        raise ValueError("packed must be a contiguous [2, R1, 1408] uint8 tensor of this plan's relation count")
+    if only_dir not in (-1, 0, 1):
+        raise ValueError("only_dir is -1, 0 or 1")
+    W_e2e = _chk(W_e2e, "e2e_linear.weight", shape=(D, (2 * I + 1) * D))
+    _on_plan_device(plan, ins, "relational_ins")
+    P = _buf((2, max(plan.rel_total, 1), D), torch.float32, ins.device, "relation_tables_packed: P")
+    if only_dir >= 0:
+        P.zero_()
+    with torch.cuda.device(ins.device):
+        _lib.check(lib.gnnrag_relation_tables_packed(C.byref(plan.c), packed.data_ptr(), ins.data_ptr(), W_e2e.data_ptr(),
+                                                     P.data_ptr(), D, I, only_dir, _stream()), "gnnrag_relation_tables_packed")
     return P[:, :plan.rel_total]
 
 

@@ -467,6 +467,21 @@ int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfeat_inv, int
 int gnnrag_relation_tables_planes(const gnnrag_csr* csr, const void* planes, const float* ins, const float* W,
                                   float* P, int32_t D, int32_t I, gnnrag_stream_t stream);
 
+/* The same two calls on the PACKED form of the left operand - what the layer sequence itself uses (additive to ABI 16).
+ * Of relu(t) and relu(-t) at most one is not zero, so the 2:4 sparse product takes the planes of |T| and one sign bit per
+ * element.  packed_out: gnnrag_rel_packed_bytes(R1, D, L) bytes (0 for D > 224), [L][2][R1][1408] bytes: per row the
+ * three bf16 planes of the exact 3-way split of |T[r, :]| (224 values each, zeros from D on), then 64 index bytes.  The
+ * index byte of the four columns 4q .. 4q+3 is 0x88 | s0 | s1 << 2 | s2 << 4 | s3 << 6, s = (T[r, k] < 0), stored at
+ * byte (q % 8 / 2) * 16 + (q / 8) * 2 + q % 2 of the 64; the eight bytes without columns are 0.
+ * gnnrag_relation_tables_packed: one layer's [2][R1][1408]; every element of P equals gnnrag_relation_tables_planes' bit
+ * for bit.  only_dir: -1 both directions, 0 / 1 that direction alone (the other half of P is left unwritten). */
+size_t gnnrag_rel_packed_bytes(int64_t R1, int32_t D, int32_t L);
+int gnnrag_rel_transform_packed(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D, int32_t L,
+                                const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out, void* packed_out,
+                                gnnrag_stream_t stream);
+int gnnrag_relation_tables_packed(const gnnrag_csr* csr, const void* packed, const float* ins, const float* W,
+                                  float* P, int32_t D, int32_t I, int32_t only_dir, gnnrag_stream_t stream);
+
 int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnrag_layer_params* layers,
                         const float* h0, const float* dist0, const float* ins,
                         const float* relfeat_fwd, const float* relfeat_inv, int32_t pos_rows,

@@ -24,7 +24,9 @@ VARIANTS = {
     "sl_t512": {"GNNRAG_SLICE_THREADS": 512, "GNNRAG_SLICE_WPE": 4},
     "sl_t768": {"GNNRAG_SLICE_THREADS": 768, "GNNRAG_SLICE_WPE": 6},
     "sl_t640": {"GNNRAG_SLICE_THREADS": 640, "GNNRAG_SLICE_WPE": 5},
-    "vq_un3": {"GNNRAG_VQ_UN": 3}, "vq_un4": {"GNNRAG_VQ_UN": 4},      # tables_b3.hip: V pieces in flight while staging
+    # tables_b3.hip: V pieces in flight while staging, both instantiations of k_tables_vq.  3: the packed one (what a step
+    # runs) has no scratch and is 1.8 us per step from 2, inside the noise; the public-planes one spills 44 B per lane
+    "vq_un3": {"GNNRAG_VQ_UN": 3}, "vq_un4": {"GNNRAG_VQ_UN": 4},
     # gather walk (tables larger than LDS, BASELINE config 5; GNNRAG_TUNE_WORKLOAD=C5)
     "light_npw1": {"GNNRAG_LIGHT_NPW": 1}, "light_npw4": {"GNNRAG_LIGHT_NPW": 4},
     "quad_s2": {"GNNRAG_QUAD_STEPS": 2},
