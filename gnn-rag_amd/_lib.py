@@ -156,6 +156,11 @@ SIGNATURES = {
                                                   C.c_int32, _VP]),
     "gnnrag_aggregate_fused_frontier": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP, C.c_int32, _VP]),
     "gnnrag_frontier_read": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, _VP, _VP]),
+    # the projections and the frontier build of a seed layer in one launch (additive to ABI 16)
+    "gnnrag_frontier_layout": (C.c_int, [C.POINTER(CsrStruct), C.POINTER(C.c_uint64)]),
+    "gnnrag_seed_prologue": (C.c_int, [C.POINTER(CsrStruct), _VP, _VP, C.c_size_t, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                      C.c_int32, C.c_int32, C.POINTER(LayerParams), C.c_int32, _VP, _VP,
+                                      C.POINTER(C.c_int32), _VP]),
     # instruction generation (additive to ABI 16)
     "gnnrag_instructions": (C.c_int, [_VP] * 4 + [C.POINTER(C.c_void_p)] * 2 + [_VP] * 4 + [C.c_int32] * 4 + [_VP] * 3),
     # training form of instruction generation (additive to ABI 16)

@@ -39,6 +39,9 @@ int tables_small_launch(const gnnrag_csr* csr, const float* T_fwd, const float* 
 int frontier_build_z(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
                      int64_t zero_na, float* zero_b, int64_t zero_nb, hipStream_t stream);
 const uint8_t* frontier_row_flags(const gnnrag_csr* csr, const void* fws);
+struct FrontierArgs;                       // seed_prologue.h
+int frontier_args(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a, int64_t zero_na,
+                  float* zero_b, int64_t zero_nb, FrontierArgs* a);
 
 // gnnrag_update_score_fused with the promise that `score` already holds zeros
 int update_score_fused_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
@@ -52,5 +55,12 @@ bool rel_transform_accepts(const float* relfeat_fwd, const float* relfeat_inv, i
 int rel_transform_launch(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D, int32_t L,
                          const gnnrag_layer_params* layers, int32_t pos_rows, float* T_out, void* planes_out,
                          void* packed_out, gnnrag_stream_t stream);
+// The same projections AND the frontier build of `dist` (frontier_build_z's arguments) in ONE launch, each workgroup
+// running one or the other (k_seed_prologue).  Returns GNNRAG_E_UNSUPPORTED, nothing launched, outside its range
+// (rel_transform_accepts false, L > 8 layers, R1 > 2048 or no relation rows): the caller then makes the two launches.
+int seed_prologue_launch(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                         int64_t zero_na, float* zero_b, int64_t zero_nb, const float* relfeat_fwd,
+                         const float* relfeat_inv, int32_t D, int32_t L, const gnnrag_layer_params* layers,
+                         int32_t pos_rows, float* T_out, void* packed_out, gnnrag_stream_t stream);
 
 }  // namespace gnnrag

@@ -23,6 +23,7 @@
 //                      position order, sums p * P[d, row(b, rel), :] over them - in one chain when there are few
 //                      (identical to the LDS walk's light-row arithmetic), by 4 waves + a fixed-order reduction else.
 #include "dense_internal.h"
+#include "seed_prologue.h"
 
 namespace gnnrag {
 
@@ -50,7 +51,7 @@ static FrontierWs frontier_ws(const gnnrag_csr* csr) {
   return w;
 }
 
-// ---- frontier of one question ---------------------------------------------------------------------------------------
+// ---- frontier of one question (the body: seed_prologue.h) -----------------------------------------------------------
 __global__ __launch_bounds__(kFrThreads) void k_frontier_build(
     const float* __restrict__ dist, const int32_t* __restrict__ rp0, const int32_t* __restrict__ rp1,
     const int2* __restrict__ el0, const int2* __restrict__ el1, const int32_t* __restrict__ rel_off, int N,
@@ -58,93 +59,11 @@ __global__ __launch_bounds__(kFrThreads) void k_frontier_build(
     int32_t* __restrict__ trows, int32_t* __restrict__ counts, int32_t* __restrict__ seeds,
     int32_t* __restrict__ seedinfo, float* __restrict__ zero_a, long long zero_na, float* __restrict__ zero_b,
     long long zero_nb) {
+  static_assert(kFrSeedCap == kSpSeedCap && kFrAltSeeds == kSpAltSeeds, "k_seed_prologue builds the same frontier");
   __shared__ int s_seed[kFrSeedCap];
-  __shared__ int s_ns, s_wsum[kFrThreads / 64];
-  const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int roff = rel_off[g], Rg = rel_off[g + 1] - roff;
-  const size_t n0 = (size_t)g * N;
-  // side jobs of this launch (it runs in front of the layer's other kernels): zero the score buffer the bf16x3 update
-  // accumulates onto, and the zero row behind nbr that unflagged rows read
-  for (long long i = (long long)blockIdx.x * kFrThreads + tid; i < zero_na; i += (long long)gridDim.x * kFrThreads) zero_a[i] = 0.f;
-  for (long long i = (long long)blockIdx.x * kFrThreads + tid; i < zero_nb; i += (long long)gridDim.x * kFrThreads) zero_b[i] = 0.f;
-  if (tid == 0) s_ns = 0;
-  if (g == (int)gridDim.x - 1 && tid < 64) row_flag[(size_t)gridDim.x * N + tid] = 0;     // the padding behind the flags
-  for (int i = tid; i < N; i += kFrThreads) row_flag[n0 + i] = 0;
-  for (int i = tid; i < Rg; i += kFrThreads) tflag[roff + i] = 0;
-  __syncthreads();
-  for (int i = tid; i < N; i += kFrThreads) {
-    if (dist[n0 + i] != 0.f) {
-      const int k = atomicAdd(&s_ns, 1);
-      if (k < kFrSeedCap) s_seed[k] = (int)n0 + i;
-    }
-  }
-  __syncthreads();
-  const int ns = s_ns;
-  if (tid == 0) {
-    // the seeds in ascending order and the number of facts that touch them, for k_walk_frontier: a listed HUB finds its
-    // few facts from a seed in the seeds' short rows instead of scanning its own (the LDS list is in atomic order)
-    int cnt = -1, facts = 0;
-    if (ns <= kFrAltSeeds) {
-      cnt = ns;
-      for (int i = 1; i < ns; ++i) {
-        const int v = s_seed[i];
-        int j = i - 1;
-        for (; j >= 0 && s_seed[j] > v; --j) s_seed[j + 1] = s_seed[j];
-        s_seed[j + 1] = v;
-      }
-      for (int i = 0; i < ns; ++i) {
-        const int sn = s_seed[i];
-        seeds[g * kFrAltSeeds + i] = sn;
-        facts += (rp0[sn + 1] - rp0[sn]) + (rp1[sn + 1] - rp1[sn]);
-      }
-    }
-    seedinfo[2 * g] = cnt;
-    seedinfo[2 * g + 1] = facts;
-  }
-  __syncthreads();
-  if (ns > kFrSeedCap) {                   // not a seed distribution: everything is frontier
-    for (int i = tid; i < N; i += kFrThreads) row_flag[n0 + i] = 1;
-    for (int i = tid; i < Rg; i += kFrThreads) tflag[roff + i] = 1;
-  } else {
-    for (int k = 0; k < ns; ++k) {
-      const int s = s_seed[k];
-#pragma unroll
-      for (int dd = 0; dd < 2; ++dd) {     // row s of structure dd = the facts of direction 1 - dd that START at s
-        const int32_t* rp = dd ? rp1 : rp0;
-        const int2* el = dd ? el1 : el0;
-        const int beg = rp[s], end = rp[s + 1];
-        for (int j = beg + tid; j < end; j += kFrThreads) {
-          const int2 e = el[j];            // (destination of the fact in direction 1 - dd, compact relation)
-          row_flag[e.x] = 1;
-          tflag[roff + e.y] = 1;
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // ordered compaction (ballot + wave prefix) into the question's own list segment
-  auto compact = [&](const uint8_t* flag, int n, int first, int32_t* list, int32_t* count_out) {
-    int base = 0;
-    for (int c0 = 0; c0 < n; c0 += kFrThreads) {
-      const int i = c0 + tid;
-      const bool on = i < n && flag[i] != 0;
-      const unsigned long long m = __ballot(on);
-      if (lane == 0) s_wsum[wave] = __popcll(m);
-      __syncthreads();
-      int off = base, tot = 0;
-      for (int w = 0; w < kFrThreads / 64; ++w) {
-        const int c = s_wsum[w];
-        if (w < wave) off += c;
-        tot += c;
-      }
-      if (on) list[off + __popcll(m & ((1ull << lane) - 1))] = first + i;
-      base += tot;
-      __syncthreads();
-    }
-    if (tid == 0) *count_out = base;
-  };
-  compact(row_flag + n0, N, (int)n0, rows + n0, counts + 2 * g);
-  compact(tflag + roff, Rg, roff, trows + roff, counts + 2 * g + 1);
+  __shared__ int s_ns, s_wsum[kFrPass / 64];
+  frontier_body<kFrThreads, kFrSeedCap, kFrAltSeeds>(dist, rp0, rp1, el0, el1, rel_off, N, row_flag, rows, tflag, trows, counts, seeds, seedinfo,
+                            zero_a, zero_na, zero_b, zero_nb, (int)blockIdx.x, (int)gridDim.x, s_seed, s_ns, s_wsum);
 }
 
 // ---- relation-table rows of the listed compact rows -----------------------------------------------------------------
@@ -419,19 +338,46 @@ extern "C" int gnnrag_frontier_supported(const gnnrag_csr* csr, int32_t D) {
   return csr && csr->edge_m && csr->m_from && D > 0 && D % 4 == 0 && D <= 256 ? 1 : 0;
 }
 
-int gnnrag::frontier_build_z(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
-                             int64_t zero_na, float* zero_b, int64_t zero_nb, hipStream_t stream) {
-  if (!csr || !dist || !fws) return GNNRAG_E_BADARG;
+// the arguments of the frontier build, checked - for k_frontier_build here and for k_seed_prologue (rel_transform.hip)
+int gnnrag::frontier_args(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                          int64_t zero_na, float* zero_b, int64_t zero_nb, FrontierArgs* a) {
+  if (!csr || !dist || !fws || !a) return GNNRAG_E_BADARG;
   const FrontierWs w = frontier_ws(csr);
   if (fws_bytes < w.total) return GNNRAG_E_WORKSPACE;
   char* base = (char*)fws;
-  hipLaunchKernelGGL(k_frontier_build, dim3(csr->B), dim3(kFrThreads), 0, stream, dist, csr->row_ptr[0], csr->row_ptr[1],
-                     (const int2*)csr->edge_l[0], (const int2*)csr->edge_l[1], csr->rel_off, csr->N,
-                     (uint8_t*)(base + w.row_flag), (int32_t*)(base + w.rows), (uint8_t*)(base + w.tflag),
-                     (int32_t*)(base + w.trows), (int32_t*)(base + w.counts), (int32_t*)(base + w.seeds),
-                     (int32_t*)(base + w.seedinfo), zero_a, (long long)zero_na, zero_b,
-                     (long long)zero_nb);
+  a->dist = dist;
+  a->rp0 = csr->row_ptr[0]; a->rp1 = csr->row_ptr[1];
+  a->el0 = (const int2*)csr->edge_l[0]; a->el1 = (const int2*)csr->edge_l[1];
+  a->rel_off = csr->rel_off;
+  a->row_flag = (uint8_t*)(base + w.row_flag); a->rows = (int32_t*)(base + w.rows);
+  a->tflag = (uint8_t*)(base + w.tflag); a->trows = (int32_t*)(base + w.trows);
+  a->counts = (int32_t*)(base + w.counts); a->seeds = (int32_t*)(base + w.seeds);
+  a->seedinfo = (int32_t*)(base + w.seedinfo);
+  a->zero_a = zero_a; a->zero_na = (long long)zero_na; a->zero_b = zero_b; a->zero_nb = (long long)zero_nb;
+  a->N = csr->N; a->B = csr->B;
+  return 0;
+}
+
+int gnnrag::frontier_build_z(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                             int64_t zero_na, float* zero_b, int64_t zero_nb, hipStream_t stream) {
+  if (!csr || !dist || !fws) return GNNRAG_E_BADARG;
+  FrontierArgs a;
+  const int rc = frontier_args(csr, dist, fws, fws_bytes, zero_a, zero_na, zero_b, zero_nb, &a);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_frontier_build, dim3(csr->B), dim3(kFrThreads), 0, stream, a.dist, a.rp0, a.rp1, a.el0, a.el1,
+                     a.rel_off, a.N, a.row_flag, a.rows, a.tflag, a.trows, a.counts, a.seeds, a.seedinfo, a.zero_a,
+                     a.zero_na, a.zero_b, a.zero_nb);
   GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// where a question's lists, counts and seeds lie in the frontier workspace (tests, tools): byte offsets of
+// counts [B][2], row_flag [B N + 64], rows [B N], tflag, trows [rel_total], seeds [B][32], seedinfo [B][2], and the total
+extern "C" int gnnrag_frontier_layout(const gnnrag_csr* csr, uint64_t* offsets8) {
+  if (!csr || !offsets8) return GNNRAG_E_BADARG;
+  const FrontierWs w = frontier_ws(csr);
+  const size_t o[8] = {w.counts, w.row_flag, w.rows, w.tflag, w.trows, w.seeds, w.seedinfo, w.total};
+  for (int i = 0; i < 8; ++i) offsets8[i] = (uint64_t)o[i];
   return 0;
 }
 

@@ -17,151 +17,36 @@
 // per lane - T as float4, the bf16 planes as 8-byte pieces.
 #include "gnnrag_common.h"
 #include "dense_internal.h"
+#include "seed_prologue.h"
 
 namespace gnnrag {
 
-constexpr int kRtMaxL = 8;        // layers per launch (more layers: more launches)
-constexpr int kRtUnroll = 7;      // k groups (16 columns each) of A in flight per wave: K = 200 -> 13 groups -> 2 rounds
-
-struct RelTArgs {
-  const float* A[2];              // rel_features, rel_features_inv  [M, K]
-  const float* W[kRtMaxL];        // rel_linear{j}.weight [N, K]
-  const float* b[kRtMaxL];        // rel_linear{j}.bias [N] or null
-  const float* add[kRtMaxL][2];   // pos_emb{j} / pos_emb_inv{j} [add_rows, N] or null
-  float* C;                       // [L][2][M][N]
-  unsigned short* planes;         // null or [L][2][3][M][kPlaneRow] bf16: planes of relu(T) | relu(-T), see below
-  unsigned char* packed;          // null or [L][2][M][kPackRowB]: planes of |T| and its signs, see below (never both)
-  int M, K, N, add_rows;
-};
-
-// Planes for the "V form" of the relation tables (tables_b3.hip: k_tables_vq): per (layer, direction) three bf16
-// planes (exact 3-way split) of [relu(T[r, :]) | relu(-T[r, :])], each half padded with zeros to 7 k blocks of 32.
-constexpr int kPlaneHalf = 224;
-constexpr int kPlaneRow = 2 * kPlaneHalf;     // bf16 elements per plane row (896 bytes)
-// The same operand as the sparse product of k_tables_vq takes it ("packed"): of relu(T) and relu(-T) at most one is not
-// zero, so the compressed left operand of v_smfmac is the three planes of |T| plus one sign bit per element.  Per (layer,
-// direction, relation row) kPackRowB bytes: three planes of |T| (kPlaneHalf bf16 each, k >= D zero), then 64 index bytes.
-// The index byte of the four k of group q = k / 4 is 0x88 | s0 | s1 << 2 | s2 << 4 | s3 << 6 with s = (T[r, k] < 0): two
-// of them are the finished 16-bit index word of a lane's 8 k (positions 0 / 1 for the first value of a pair, 2 / 3 for the
-// second).  They are stored in the order the lanes read them - the byte of q at (q % 8 / 2) * 16 + (q / 8) * 2 + q % 2,
-// i.e. the word of (k block q / 8, lane group fg = q % 8 / 2) at fg * 16 + block * 2 - so that a lane's planes and its
-// index word share one lane offset (fg * 16).  The 8 bytes no k stands behind are 0.
-// -0.0 and values whose three planes are all zero (fp32 denormals below the smallest bf16) may get either sign bit: their
-// operand is zero, and 0 times either half of the (finite) right operand adds nothing to a sum that starts at +0.
-constexpr int kPackPlaneB = kPlaneHalf * 2;             // bytes per plane of a packed row (448)
-constexpr int kPackIdxB = 3 * kPackPlaneB;              // offset of the index bytes (1344)
-constexpr int kPackRowB = kPackIdxB + 64;               // 1408
-
+// (the kernel body: seed_prologue.h)
 // TPW: 16-row tiles per wave (1: few relation rows, many small workgroups; 4: large vocabularies, the weight slice
 // staged once per 256 rows)
 template <int TPW>
 __global__ __launch_bounds__(256) void k_rel_transform(RelTArgs g) {
-  extern __shared__ __attribute__((aligned(16))) float Wf[];  // the weight slice in FRAGMENT order, see below
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int fr = lane & 15, fg = lane >> 4;
-  const int j = blockIdx.z >> 1, d = blockIdx.z & 1;
-  const int colg = blockIdx.y * 64;                          // this workgroup's 64 columns: four MFMA tiles
-  const int K = g.K;
-  const int nch = (K + 15) >> 4;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  const bool compute = colg < g.N;                           // (column groups past N only write the planes' zero padding)
-  // column slot fr of tile a stands for column colg + 4 fr + a: a lane ends up with 4 CONSECUTIVE columns of its rows
-  // (16-byte stores of T, 8-byte stores of the bf16 planes).  LDS holds W[colg .. colg+63][:] as the lanes will read
-  // it: float4 number ((c * 4 + a) * 64 + lane) = W[colg + 4 fr + a][16 c + 4 fg ..] - one contiguous KB per
-  // (k group c, tile a) and wave instruction, conflict free.
-  if (compute) {
-    const int total = 64 * nch * 4;                          // float4 pieces: 64 columns x (K/4 padded to 4 nch)
-    for (int x = tid; x < total; x += 256) {
-      const int col = x / (nch * 4), kq = x - col * (nch * 4);       // kq = k / 4: consecutive threads, consecutive k
-      f32x4 v = zero4;
-      if (colg + col < g.N && 4 * kq < K) v = *reinterpret_cast<const f32x4*>(g.W[j] + (size_t)(colg + col) * K + 4 * kq);
-      const int c = kq >> 2, fgq = kq & 3, a = col & 3, frq = col >> 2;
-      *reinterpret_cast<f32x4*>(Wf + ((size_t)((c * 4 + a) * 64 + fgq * 16 + frq)) * 4) = v;
-    }
-  }
-  __syncthreads();
-  const int c4 = colg + 4 * fr;
-  const bool in_T = c4 < g.N;                                // (N % 4 == 0: a lane's 4 columns are all in or all out)
-  const bool in_pad = !in_T && c4 < kPlaneHalf;
-  f32x4 bias = zero4;
-  if (in_T && g.b[j]) bias = *reinterpret_cast<const f32x4*>(g.b[j] + c4);
-  const float* __restrict__ addp = g.add[j][d];
-  float* __restrict__ cp = g.C + ((size_t)(2 * j + d) * g.M) * g.N;
-  unsigned short* pp = g.planes ? g.planes + ((size_t)(2 * j + d) * 3 * g.M) * kPlaneRow : nullptr;
-  unsigned char* pk = g.packed ? g.packed + ((size_t)(2 * j + d) * g.M) * kPackRowB : nullptr;
+  extern __shared__ __attribute__((aligned(16))) float Wf[];
+  rel_transform_body<TPW>(g, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, Wf);
+}
 
-#pragma unroll 1
-  for (int t = 0; t < TPW; ++t) {
-    const int row0 = (blockIdx.x * TPW + t) * 64 + wave * 16;
-    if (row0 >= g.M) break;
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[a][0] = acc[a][1] = zero4;
-    if (compute) {
-      // rows past the end read the last valid one (never stored); the A fragments come straight from global memory
-      const float* __restrict__ ap = g.A[d] + (size_t)min(row0 + fr, g.M - 1) * K;
-      for (int c0 = 0; c0 < nch; c0 += kRtUnroll) {
-        f32x4 av[kRtUnroll];
-#pragma unroll
-        for (int u = 0; u < kRtUnroll; ++u)    // k groups past K: a clamped (valid) address, zeroed at use - no branch around a load
-          av[u] = *reinterpret_cast<const f32x4*>(ap + min(16 * (c0 + u) + 4 * fg, K - 4));
-#pragma unroll
-        for (int u = 0; u < kRtUnroll; ++u) {
-          const int c = min(c0 + u, nch - 1);
-          const bool live = 16 * (c0 + u) + 4 * fg < K;
-          const f32x4 x = live ? av[u] : zero4;
-          f32x4 wv[4];
-#pragma unroll
-          for (int a = 0; a < 4; ++a) wv[a] = *reinterpret_cast<const f32x4*>(Wf + ((size_t)((c * 4 + a) * 64 + lane)) * 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-              acc[a][e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(x[e], wv[a][e], acc[a][e & 1], 0, 0, 0);
-        }
-      }
-    }
-    // accumulator element r of lane (fr, fg), tile a = C[row0 + 4 fg + r][colg + 4 fr + a]
-    if (!in_T && !(pp && in_pad) && !pk) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = row0 + 4 * fg + r;
-      if (row >= g.M) continue;
-      f32x4 v = zero4;
-      if (in_T) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) v[a] = acc[a][0][r] + acc[a][1][r];
-        v += bias;
-        if (addp && row < g.add_rows) v += *reinterpret_cast<const f32x4*>(addp + (size_t)row * g.N + c4);
-        *reinterpret_cast<f32x4*>(cp + (size_t)row * g.N + c4) = v;
-      }
-      if (pp) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          // exact 3-way bf16 split of relu(+-T) (gnnrag_common.h: split3); the padding columns get zeros
-          const Split3 sp = split3(__builtin_elementwise_max(half ? -v : v, zero4));
-          const size_t e = (size_t)row * kPlaneRow + half * kPlaneHalf + c4;
-          *reinterpret_cast<uint2*>(pp + e) = sp.hi;
-          *reinterpret_cast<uint2*>(pp + (size_t)g.M * kPlaneRow + e) = sp.mid;
-          *reinterpret_cast<uint2*>(pp + (size_t)2 * g.M * kPlaneRow + e) = sp.lo;
-        }
-      }
-      if (pk) {
-        // the same register values, packed: split3(|v|) and the signs; padding columns get zero planes and "all +"
-        unsigned char* rowp = pk + (size_t)row * kPackRowB;
-        if (c4 < kPlaneHalf) {
-          const Split3 sp = split3(__builtin_elementwise_abs(v));
-          *reinterpret_cast<uint2*>(rowp + 2 * c4) = sp.hi;
-          *reinterpret_cast<uint2*>(rowp + kPackPlaneB + 2 * c4) = sp.mid;
-          *reinterpret_cast<uint2*>(rowp + 2 * kPackPlaneB + 2 * c4) = sp.lo;
-        }
-        const int q = c4 >> 2;                               // (the column groups run on to 256: q < 64)
-        const unsigned ix = 0x88u | (unsigned)(v[0] < 0.f) | (unsigned)(v[1] < 0.f) << 2 | (unsigned)(v[2] < 0.f) << 4 |
-                            (unsigned)(v[3] < 0.f) << 6;
-        rowp[kPackIdxB + ((q & 7) >> 1) * 16 + (q >> 3) * 2 + (q & 1)] = (unsigned char)(c4 < kPlaneHalf ? ix : 0u);
-      }
-    }
+// The projections AND the frontier of the seed distribution in one launch: both are needed first by k_tables_frontier
+// and neither reads what the other writes.  Workgroups [0, f.B) build the frontier of one question each (256 threads
+// instead of k_frontier_build's 1024: more rounds of the same ordered compaction, the same lists), the others run
+// workgroup (bx, by, bz) of k_rel_transform<1>'s grid (gx, gy, ..).  A workgroup runs one body or the other; nothing
+// passes between workgroups.  The frontier's LDS lies at the head of the dynamic LDS the projection stages W in.
+constexpr int kSpThreads = 256;
+__global__ __launch_bounds__(kSpThreads) void k_seed_prologue(RelTArgs g, FrontierArgs f, int gx, int gy) {
+  extern __shared__ __attribute__((aligned(16))) float Wf[];
+  if ((int)blockIdx.x < f.B) {
+    int* s = reinterpret_cast<int*>(Wf);
+    frontier_body<kSpThreads>(f.dist, f.rp0, f.rp1, f.el0, f.el1, f.rel_off, f.N, f.row_flag, f.rows, f.tflag, f.trows,
+                              f.counts, f.seeds, f.seedinfo, f.zero_a, f.zero_na, f.zero_b, f.zero_nb, (int)blockIdx.x, f.B,
+                              s, s[kSpSeedCap], s + kSpSeedCap + 1);
+    return;
   }
+  const int r = (int)blockIdx.x - f.B;
+  rel_transform_body<1>(g, r % gx, (r / gx) % gy, r / (gx * gy), Wf);
 }
 
 }  // namespace gnnrag
@@ -245,6 +130,66 @@ int gnnrag::rel_transform_launch(const float* relfeat_fwd, const float* relfeat_
     GNNRAG_LAUNCH_CHECK();
   }
   return 0;
+}
+
+int gnnrag::seed_prologue_launch(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                                 int64_t zero_na, float* zero_b, int64_t zero_nb, const float* relfeat_fwd,
+                                 const float* relfeat_inv, int32_t D, int32_t L, const gnnrag_layer_params* layers,
+                                 int32_t pos_rows, float* T_out, void* packed_out, gnnrag_stream_t stream) {
+  if (!csr || !relfeat_fwd || !relfeat_inv || !layers || !T_out || D <= 0 || L <= 0 || pos_rows < 0) return GNNRAG_E_BADARG;
+  for (int j = 0; j < L; ++j) {
+    if (!layers[j].W_rel) return GNNRAG_E_BADARG;
+    if ((layers[j].pos_fwd == nullptr) != (layers[j].pos_inv == nullptr)) return GNNRAG_E_BADARG;
+  }
+  const int64_t R1 = csr->R1;
+  // one launch, one block size: the range of k_rel_transform<1>, all layers in one grid
+  if (L > kRtMaxL || R1 <= 0 || R1 > 2048 || csr->B <= 0) return GNNRAG_E_UNSUPPORTED;
+  if (!gnnrag::rel_transform_accepts(relfeat_fwd, relfeat_inv, R1, D, L, layers, pos_rows, T_out, packed_out))
+    return GNNRAG_E_UNSUPPORTED;
+  FrontierArgs f;
+  int rc = frontier_args(csr, dist, fws, fws_bytes, zero_a, zero_na, zero_b, zero_nb, &f);
+  if (rc) return rc;
+  RelTArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A[0] = relfeat_fwd;
+  g.A[1] = relfeat_inv;
+  for (int j = 0; j < L; ++j) {
+    g.W[j] = layers[j].W_rel;
+    g.b[j] = layers[j].b_rel;
+    g.add[j][0] = pos_rows > 0 ? layers[j].pos_fwd : nullptr;
+    g.add[j][1] = pos_rows > 0 ? layers[j].pos_inv : nullptr;
+  }
+  g.C = T_out;
+  g.packed = (unsigned char*)packed_out;
+  g.M = (int)R1; g.K = D; g.N = D;
+  g.add_rows = (int)(pos_rows < R1 ? pos_rows : R1);
+  const int gx = (int)((R1 + 63) / 64), gy = ((packed_out ? kPlaneHalf : D) + 63) / 64, gz = 2 * L;
+  size_t lds = (size_t)64 * ((D + 15) / 16) * 16 * sizeof(float);
+  const size_t fr_lds = align_up((size_t)kFrLdsInts * sizeof(int), 16);
+  if (lds < fr_lds) lds = fr_lds;
+  static DeviceMask cap;
+  if (lds > 64 * 1024) { rc = raise_lds_cap(k_seed_prologue, cap); if (rc) return rc; }
+  hipLaunchKernelGGL(k_seed_prologue, dim3((unsigned)(csr->B + gx * gy * gz)), dim3(kSpThreads), lds, (hipStream_t)stream,
+                     g, f, gx, gy);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the exported form: the one launch where it applies, else the two it stands for - the same bytes either way
+extern "C" int gnnrag_seed_prologue(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                                    int64_t zero_na, float* zero_b, int64_t zero_nb, const float* relfeat_fwd,
+                                    const float* relfeat_inv, int32_t D, int32_t L, const gnnrag_layer_params* layers,
+                                    int32_t pos_rows, float* T_out, void* packed_out, int32_t* combined,
+                                    gnnrag_stream_t stream) {
+  if (combined) *combined = 0;
+  if (!csr || !dist || !fws) return GNNRAG_E_BADARG;
+  int rc = gnnrag::seed_prologue_launch(csr, dist, fws, fws_bytes, zero_a, zero_na, zero_b, zero_nb, relfeat_fwd, relfeat_inv,
+                                        D, L, layers, pos_rows, T_out, packed_out, stream);
+  if (rc == 0 && combined) *combined = 1;
+  if (rc != GNNRAG_E_UNSUPPORTED) return rc;
+  rc = gnnrag::rel_transform_launch(relfeat_fwd, relfeat_inv, csr->R1, D, L, layers, pos_rows, T_out, nullptr, packed_out, stream);
+  if (rc) return rc;
+  return gnnrag::frontier_build_z(csr, dist, fws, fws_bytes, zero_a, zero_na, zero_b, zero_nb, (hipStream_t)stream);
 }
 
 extern "C" int gnnrag_rel_transform(const float* relfeat_fwd, const float* relfeat_inv, int64_t R1, int32_t D,

@@ -290,18 +290,39 @@ static int finish_softmax(const gnnrag_csr* csr, const LayerWs& w, char* base, c
   return gnnrag_masked_softmax(score, dist_out, csr->B, csr->N, stream);
 }
 
+// THE decision that a layer call takes the frontier form (frontier.hip), as one function: layer_body asks it, and the
+// callers that project in front of a seed layer ask it with the same operands to run the frontier build in the
+// projections' launch (seed_prologue_launch).  `path` as the caller passed it (hint and direction flags included).
+static bool frontier_form_ok(const gnnrag_csr* csr, const LayerWs& w, const char* base, const float* dist, const float* ins,
+                             const float* T_fwd, const float* T_inv, const float* W_e2e, int32_t D, int32_t I, int32_t path) {
+  if (!(path & GNNRAG_PATH_SEED_PRIOR) || (path & (GNNRAG_PATH_ONLY_FWD | GNNRAG_PATH_ONLY_INV))) return false;
+  int p = path & 0xf;
+  if (p == GNNRAG_PATH_AUTO)
+    p = fused_is_cheaper(csr->B, csr->N, csr->rel_total, D, I) ? GNNRAG_PATH_FUSED : GNNRAG_PATH_UNFUSED;
+  if (p != GNNRAG_PATH_FUSED) return false;
+  // the frontier kernels issue 16-byte loads / stores on ins, W, T, P (workspace) and the node rows: a misaligned view
+  // takes the regular fused path, whose launchers check alignment themselves
+  const float* P = (const float*)(base + w.P);
+  const float* nbr = (const float*)(base + w.nbr);
+  return aligned16(ins, W_e2e, T_fwd, T_inv, P, nbr, dist) && csr->N > 0 && gnnrag_frontier_supported(csr, D) &&
+         csr->rel_total > 0;
+}
+
 // one layer behind its relation projections T_fwd / T_inv (already computed)
 static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const float* h, const float* dist,
                       const float* ins, const float* T_fwd, const float* T_inv, const void* planes, const float* W_e2e,
                       const float* b_e2e, const float* w_score, const float* b_score, const float* mask,
                       float* h_out, float* score_out, float* dist_out, int32_t D, int32_t I, int32_t path,
-                      int32_t math, gnnrag_stream_t stream, bool pairs_ready = false, bool* pairs_for_next = nullptr) {
+                      int32_t math, gnnrag_stream_t stream, bool pairs_ready = false, bool* pairs_for_next = nullptr,
+                      bool frontier_built = false) {
   // pairs_ready: the previous layer's softmax launch left this layer's (prior, relation) pairs in the workspace;
   // pairs_for_next != nullptr: the caller will run another layer on dist_out - *pairs_for_next reports whether this
-  // layer's last launch wrote that layer's pairs
+  // layer's last launch wrote that layer's pairs; frontier_built: the caller's projection launch already built the
+  // frontier of `dist` (and zeroed the score and the zero row) - it asked frontier_form_ok with these operands
   if (pairs_for_next) *pairs_for_next = false;
   const int64_t BN = (int64_t)csr->B * csr->N;
   int rc;
+  const bool frontier_form = frontier_form_ok(csr, w, base, dist, ins, T_fwd, T_inv, W_e2e, D, I, path);
   // one-direction layers (NSM): only that direction's tables are built and walked where the kernels at hand can
   // leave a direction out (V-form tables + LDS walk); otherwise both directions run and the caller's zero weight
   // block makes the other one contribute exactly 0
@@ -314,10 +335,6 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
     float* P = (float*)(base + w.P);
     float* nbr = (float*)(base + w.nbr);
     const bool one_dir = only >= 0 && gnnrag_aggregate_fused_variant(csr, D) != GNNRAG_WALK_L2_GATHER;
-    // the frontier kernels issue 16-byte loads / stores on ins, W, T, P (workspace) and the node rows: a misaligned view
-    // takes the regular fused path below, whose launchers check alignment themselves
-    const bool fr_aligned = aligned16(ins, W_e2e, T_fwd, T_inv, P, nbr, dist) && csr->N > 0;
-    const bool frontier_form = seed_prior && only < 0 && fr_aligned && gnnrag_frontier_supported(csr, D) && csr->rel_total > 0;
     if (frontier_form) {
       // The caller says `dist` is a seed distribution (first layer of a ReaRev iteration, rearev.py:208): only the
       // seeds' facts have a prior, so only the relation-table rows those facts use and the neighbour sums of the nodes
@@ -326,8 +343,10 @@ static int layer_body(const gnnrag_csr* csr, const LayerWs& w, char* base, const
       void* fws = base + w.fws;
       const bool gated = update_rows_supported(h, nbr, W_e2e, h_out, BN, D, I, math);
       if (!gated) GNNRAG_HIP(hipMemsetAsync(nbr, 0, (size_t)BN * D * sizeof(float), (hipStream_t)stream));
-      rc = frontier_build_z(csr, dist, fws, w.fws_bytes, score_out, BN, nbr + (size_t)BN * D, D, (hipStream_t)stream);
-      if (rc) return rc;
+      if (!frontier_built) {
+        rc = frontier_build_z(csr, dist, fws, w.fws_bytes, score_out, BN, nbr + (size_t)BN * D, D, (hipStream_t)stream);
+        if (rc) return rc;
+      }
       rc = gnnrag_relation_tables_frontier(csr, fws, T_fwd, T_inv, ins, W_e2e, P, D, I, stream);
       if (rc) return rc;
       rc = gnnrag_aggregate_fused_frontier(csr, fws, dist, P, nbr, D, stream);
@@ -387,6 +406,30 @@ static int rel_projections(const gnnrag_csr* csr, int32_t n, const gnnrag_layer_
   return 0;
 }
 
+// rel_projections in front of a layer that starts from `dist` and writes its scores to `score0`: when that layer will take
+// the frontier form, the frontier build (with its zeroing of the score and of the zero row behind nbr) runs in the
+// projections' launch and *frontier_built tells layer_body so; outside that launch's range: rel_projections, as before
+static int seed_projections(const gnnrag_csr* csr, const LayerWs& w, char* base, int32_t n, const gnnrag_layer_params* layers,
+                            const float* relfeat_fwd, const float* relfeat_inv, int32_t pos_rows, float* T, void* planes,
+                            bool* planes_written, const float* dist, const float* ins, float* score0, int32_t D, int32_t I,
+                            int32_t path, int32_t math, gnnrag_stream_t stream, bool* frontier_built) {
+  *frontier_built = false;
+  const size_t RD = (size_t)csr->R1 * D;
+  const int64_t BN = (int64_t)csr->B * csr->N;
+  if (frontier_form_ok(csr, w, base, dist, ins, T, T + RD, layers[0].W_e2e, D, I, path)) {
+    float* nbr = (float*)(base + w.nbr);
+    const int rc = seed_prologue_launch(csr, dist, base + w.fws, w.fws_bytes, score0, BN, nbr + (size_t)BN * D, D, relfeat_fwd,
+                                        relfeat_inv, D, n, layers, pos_rows, T, planes, stream);
+    if (rc == 0) {
+      *planes_written = planes != nullptr;
+      *frontier_built = true;
+      return 0;
+    }
+    if (rc != GNNRAG_E_UNSUPPORTED) return rc;
+  }
+  return rel_projections(csr, n, layers, relfeat_fwd, relfeat_inv, pos_rows, T, planes, planes_written, D, math, stream);
+}
+
 extern "C" size_t gnnrag_stack_workspace_bytes(const gnnrag_csr* csr, int32_t L, int32_t D, int32_t I) {
   if (!csr || L <= 0 || D <= 0 || I <= 0) return 0;
   // one layer's workspace + the relation projections of all L layers (one contiguous block, computed up front)
@@ -414,13 +457,13 @@ extern "C" int gnnrag_reason_layer(const gnnrag_csr* csr, const float* h, const 
   float* T_inv = (float*)(base + w.T_inv);
   const gnnrag_layer_params p = {W_rel, b_rel, pos_fwd, pos_inv, W_e2e, b_e2e};
   void* planes = planes_wanted(csr, D, I, path, math) ? (void*)(base + w.planes) : nullptr;
-  bool planes_written = false;
-  const int rc = rel_projections(csr, 1, &p, relfeat_fwd, relfeat_inv, pos_rows, T_fwd, planes, &planes_written, D, math,
-                                 stream);
+  bool planes_written = false, frontier_built = false;
+  const int rc = seed_projections(csr, w, base, 1, &p, relfeat_fwd, relfeat_inv, pos_rows, T_fwd, planes, &planes_written, dist,
+                                  ins, score_out, D, I, path, math, stream, &frontier_built);
   if (rc) return rc;
   if (!planes_written) planes = nullptr;
   return layer_body(csr, w, base, h, dist, ins, T_fwd, T_inv, planes, W_e2e, b_e2e, w_score, b_score, mask, h_out, score_out,
-                    dist_out, D, I, path, math, stream);
+                    dist_out, D, I, path, math, stream, false, nullptr, frontier_built);
 }
 
 // Argument checks, the relation projections of all layers up front where the workspace has room for them, then the
@@ -453,7 +496,7 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
   const bool want_planes = planes_wanted(csr, D, I, path, math);
   const size_t plane_bytes = tables_vq_packed_bytes(csr->R1);      // (the L packed layers lie at the head of the L plane slots)
   char* planes_all = base + w.total + align_up((size_t)L * 2 * RD * sizeof(float), 256);
-  bool planes_written = false;
+  bool planes_written = false, frontier_built = false;
   const bool reuse = upfront && (path & GNNRAG_PATH_REUSE_PROJ) != 0;
   path &= ~GNNRAG_PATH_REUSE_PROJ;
   if (reuse) {
@@ -462,8 +505,10 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
     planes_written = want_planes && rel_transform_accepts(relfeat_fwd, relfeat_inv, csr->R1, D, L, layers, pos_rows, Tall,
                                                           planes_all);
   } else if (upfront) {
-    const int rc = rel_projections(csr, L, layers, relfeat_fwd, relfeat_inv, pos_rows, Tall,
-                                   want_planes ? planes_all : nullptr, &planes_written, D, math, stream);
+    // (layer 0 reads dist0 and writes score_out[0]: its frontier build rides in the projections' launch where it can)
+    const int rc = seed_projections(csr, w, base, L, layers, relfeat_fwd, relfeat_inv, pos_rows, Tall,
+                                    want_planes ? planes_all : nullptr, &planes_written, dist0, ins, score_out, D, I, path, math,
+                                    stream, &frontier_built);
     if (rc) return rc;
   }
   const float* h = h0;
@@ -486,7 +531,7 @@ extern "C" int gnnrag_reason_stack(const gnnrag_csr* csr, int32_t L, const gnnra
     bool pairs_next = false;
     const int rc = layer_body(csr, w, base, h, dist, ins, T, T + RD, planes, p.W_e2e, p.b_e2e, w_score, b_score, mask, hj, sj,
                               dj, D, I, j == 0 ? path : (path & ~GNNRAG_PATH_SEED_PRIOR), math, stream, pairs_ready,
-                              j + 1 < L ? &pairs_next : nullptr);
+                              j + 1 < L ? &pairs_next : nullptr, j == 0 && frontier_built);
     if (rc) return rc;
     pairs_ready = pairs_next;
     h = hj;

@@ -682,6 +682,65 @@ class Frontier:
         return out
 
 
+FRONTIER_PARTS = ("counts", "row_flag", "rows", "tflag", "trows", "seeds", "seedinfo")
+
+
+def frontier_layout(plan: CsrPlan) -> dict:
+    """Byte offsets of the parts of a frontier workspace (``gnnrag_frontier_layout``), plus ``total``."""
+    off = (C.c_uint64 * 8)()
+    _lib.check(_lib.load().gnnrag_frontier_layout(C.byref(plan.c), off), "gnnrag_frontier_layout")
+    return dict(zip(FRONTIER_PARTS + ("total",), (int(x) for x in off)))
+
+
+def seed_prologue(plan: CsrPlan, dist: torch.Tensor, ws: torch.Tensor, relfeat: torch.Tensor, relfeat_inv: torch.Tensor,
+                  layers, T_out: torch.Tensor, packed_out: Optional[torch.Tensor] = None,
+                  zero_a: Optional[torch.Tensor] = None, zero_b: Optional[torch.Tensor] = None) -> bool:
+    """What the layer stack launches in front of a seed layer (``gnnrag_seed_prologue``): the relation projections of
+    ``layers`` (as :func:`rel_transform` takes them) into ``T_out [L, 2, R1, D]`` (+ ``packed_out [L, 2, R1, 1408]``
+    uint8) and the frontier of ``dist`` into the frontier workspace ``ws`` (uint8), zeroing ``zero_a`` / ``zero_b`` on the
+    way - one launch where that applies, else the two launches it stands for.  Test-side: every output is the caller's
+    buffer.  Returns whether the one launch was taken."""
+    lib = _lib.load()
+    relfeat = _chk(relfeat, "rel_features")
+    R1, D = relfeat.shape
+    relfeat_inv = _chk(relfeat_inv, "rel_features_inv", shape=(R1, D))
+    dist = _chk(dist, "dist").reshape(-1)
+    _on_plan_device(plan, dist, "dist")
+    if dist.numel() != plan.B * plan.N or R1 != plan.R1:
+        raise ValueError("dist / rel_features do not match the plan")
+    L = len(layers)
+    params = (_lib.LayerParams * max(L, 1))()
+    keep, pos_rows = [], 0
+    for j, (W, b, pos, pos_inv) in enumerate(layers):
+        W = _chk(W, "rel_linear.weight", shape=(D, D))
+        b = _chk(b, "rel_linear.bias", shape=(D,))
+        keep += [W, b]
+        params[j].W_rel, params[j].b_rel = W.data_ptr(), b.data_ptr()
+        if pos is not None:
+            pos = _chk(pos, "pos_emb.weight")
+            pos_inv = _chk(pos_inv, "pos_emb_inv.weight", shape=tuple(pos.shape))
+            pos_rows = pos.shape[0]
+            keep += [pos, pos_inv]
+            params[j].pos_fwd, params[j].pos_inv = pos.data_ptr(), pos_inv.data_ptr()
+    if T_out.dtype != torch.float32 or T_out.numel() < L * 2 * R1 * D or not T_out.is_contiguous():
+        raise ValueError("T_out must be a contiguous float32 buffer of at least L*2*R1*D elements")
+    if packed_out is not None and packed_out.numel() * packed_out.element_size() < lib.gnnrag_rel_packed_bytes(R1, D, L):
+        raise ValueError("packed_out is smaller than gnnrag_rel_packed_bytes")
+    if ws.numel() * ws.element_size() < lib.gnnrag_frontier_workspace_bytes(C.byref(plan.c)):
+        raise ValueError("ws is smaller than gnnrag_frontier_workspace_bytes")
+    for z in (zero_a, zero_b):
+        if z is not None and (z.dtype != torch.float32 or not z.is_contiguous()):
+            raise ValueError("zero_a / zero_b must be contiguous float32")
+    combined = C.c_int32(0)
+    with torch.cuda.device(dist.device):
+        _lib.check(lib.gnnrag_seed_prologue(
+            C.byref(plan.c), dist.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _ptr(zero_a),
+            zero_a.numel() if zero_a is not None else 0, _ptr(zero_b), zero_b.numel() if zero_b is not None else 0,
+            relfeat.data_ptr(), relfeat_inv.data_ptr(), D, L, params, pos_rows, T_out.data_ptr(), _ptr(packed_out),
+            C.byref(combined), _stream()), "gnnrag_seed_prologue")
+    return bool(combined.value)
+
+
 def update_score_fused(h, nbr, W, b, w_s, b_s, mask, I: int, math: Optional[int] = None):
     lib = _lib.load()
     h = _chk(h, "h")

@@ -526,6 +526,21 @@ int gnnrag_aggregate_fused_frontier(const gnnrag_csr* csr, const void* fws, cons
                                     float* out, int32_t D, gnnrag_stream_t stream);
 int gnnrag_frontier_read(const gnnrag_csr* csr, const void* fws, int32_t* counts2, uint8_t* row_flag_host,
                          gnnrag_stream_t stream);
+/* Byte offsets inside fws (tests, tools): offsets8 = counts [B][2] int32 (listed nodes, listed relation rows of each
+ * question), row gates [B N + 64] uint8, node lists [B N] int32 (question g's at g N), relation-row flags, relation-row
+ * lists [rel_total] int32 (question g's at rel_off[g]), seeds [B][32] int32 (ascending; used when there are at most 32),
+ * seedinfo [B][2] int32 (number of seeds or -1, facts that touch them), total bytes. */
+int gnnrag_frontier_layout(const gnnrag_csr* csr, uint64_t* offsets8);
+/* What gnnrag_reason_stack launches in front of a seed layer (GNNRAG_PATH_SEED_PRIOR): gnnrag_rel_transform_packed
+ * (packed_out may be null: T alone) for csr->R1 relation rows AND gnnrag_frontier_build of `dist`, which also zeroes
+ * zero_na floats at zero_a and zero_nb at zero_b (either may be null / 0), in ONE launch whose workgroups run one or the
+ * other - neither reads what the other writes.  The one launch covers L <= 8 layers, 0 < R1 <= 2048 and the operands
+ * gnnrag_rel_transform takes; outside that range the same call makes the two launches.  Every byte written equals what
+ * the two stand-alone calls write.  *combined (may be null): 1 when the one launch was taken. */
+int gnnrag_seed_prologue(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a,
+                         int64_t zero_na, float* zero_b, int64_t zero_nb, const float* relfeat_fwd,
+                         const float* relfeat_inv, int32_t D, int32_t L, const gnnrag_layer_params* layers,
+                         int32_t pos_rows, float* T_out, void* packed_out, int32_t* combined, gnnrag_stream_t stream);
 
 /* Candidate selection of Evaluator.evaluate (evaluate.py:188-207) + the sort and top-p cut of
  * f1_and_hits (evaluate.py:34-51), one workgroup per question:
