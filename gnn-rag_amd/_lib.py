@@ -66,6 +66,15 @@ class BertLayer(C.Structure):
                                           "ln2_g", "ln2_b")]
 
 
+class OptimSeg(C.Structure):
+    """Mirror of ``struct gnnrag_optim_seg`` (include/gnnrag.h): 80 bytes, one entry per tensor of an optimiser step."""
+    _fields_ = ([(n, C.c_void_p) for n in ("p", "g", "m", "v")] + [("n", C.c_int64), ("first_chunk", C.c_int64)] +
+                [(n, C.c_float) for n in ("beta1", "beta2", "om_beta1", "om_beta2", "eps", "weight_decay", "step_size",
+                                          "bc2_sqrt")])
+
+
+OPTIM_CHUNK = 4096                               # GNNRAG_OPTIM_CHUNK (include/gnnrag.h)
+
 # name -> (restype, argtypes); every symbol include/gnnrag.h declares
 _VP = C.c_void_p
 SIGNATURES = {
@@ -223,6 +232,10 @@ SIGNATURES = {
     "gnnrag_rule_paths_out_bytes": (C.c_size_t, [C.c_int32] * 5),
     "gnnrag_rule_paths": (C.c_int, [C.POINTER(UGraphStruct), _VP, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     _VP, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    # gradient-norm clip and Adam step (additive to ABI 16)
+    "gnnrag_optim_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gnnrag_grad_norm": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_float, _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_adam_step": (C.c_int, [_VP, C.c_int32, C.c_int64, _VP, _VP]),
     "gnnrag_stream_copy": (C.c_int, [_VP, _VP, C.c_int64, _VP]),
     "gnnrag_abi_version": (C.c_int, []),
     "gnnrag_error_string": (C.c_char_p, [C.c_int]),

@@ -253,6 +253,16 @@ def patch_loss_metrics(model):
     return _patch(model)
 
 
+def patch_trainer(trainer):
+    """``trainer.optim_model`` (train_model.py:89-94) and ``trainer.train_epoch`` (:209-233) of a constructed
+    ``Trainer_KBQA``: the gradient-norm clip and the Adam step that end every training step as one
+    ``optimizer.clip_and_step`` call - three launches on the library (optim.py; ``GNNRAG_HIP_OPTIM=0`` - the default - leaves
+    torch's ``clip_grad_norm_`` and ``Adam.step`` in charge).  The optimiser object stays the one the trainer's scheduler
+    holds.  NOTE: on the library path ``.grad`` is not rescaled by the clip (the trainer clears it next)."""
+    from .optim import patch_trainer as _patch
+    return _patch(trainer)
+
+
 def swap_lstm(model) -> int:
     """The question encoder's ``nn.LSTM`` (lstm_encoder.py:27-30) -> ``HipLSTM`` (same parameters, shared); works on a model
     built either way (install() or the reference's own modules).  Returns the number of LSTMs replaced."""

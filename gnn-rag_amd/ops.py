@@ -1540,6 +1540,63 @@ def train_metrics(pred, answer, seed, local_entity, pad_id: int, eps: float):
     return out_pred, h1, f1, cnt
 
 
+OPTIM_CHUNK = _lib.OPTIM_CHUNK                  # GNNRAG_OPTIM_CHUNK (include/gnnrag.h)
+OPTIM_SEG_BYTES = C.sizeof(_lib.OptimSeg)
+# numpy mirror of gnnrag_optim_seg: a table is filled column by column on the host (gnnrag_amd/optim.py)
+OPTIM_SEG_DTYPE = np.dtype([(n, np.uint64) for n in ("p", "g", "m", "v")] + [("n", np.int64), ("first_chunk", np.int64)] +
+                           [(n, np.float32) for n in ("beta1", "beta2", "om_beta1", "om_beta2", "eps", "weight_decay",
+                                                      "step_size", "bc2_sqrt")])
+assert OPTIM_SEG_DTYPE.itemsize == OPTIM_SEG_BYTES == 80
+
+
+def optim_chunks(numels):
+    """(first_chunk of every tensor, n_chunks) for tensors of ``numels`` elements: the prefix sums of
+    ceil(n / GNNRAG_OPTIM_CHUNK) a segment table carries."""
+    first, total = [], 0
+    for n in numels:
+        first.append(total)
+        total += (int(n) + OPTIM_CHUNK - 1) // OPTIM_CHUNK
+    return first, total
+
+
+def _optim_table(segs, T: int, who: str) -> torch.Tensor:
+    if not segs.is_cuda:
+        raise _lib.GnnragError("%s: segs must live on the GPU (got %s); there is no CPU path" % (who, segs.device))
+    if segs.dtype != torch.uint8 or not segs.is_contiguous() or segs.numel() < T * OPTIM_SEG_BYTES or T <= 0:
+        raise ValueError("%s: segs must be a contiguous uint8 tensor of at least T * %d bytes, T > 0" % (who, OPTIM_SEG_BYTES))
+    return segs
+
+
+def grad_norm(segs: torch.Tensor, T: int, n_chunks: int, max_norm: float) -> torch.Tensor:
+    """``clip_grad_norm_`` without the rescaling (``gnnrag_grad_norm``): segs a DEVICE table of T ``gnnrag_optim_seg`` entries
+    as a uint8 tensor (``OPTIM_SEG_DTYPE``; only g, n and first_chunk are read), n_chunks from :func:`optim_chunks`.
+    Returns out2 [2] on the device: (total_norm, clip_coef = min(1, max_norm / (total_norm + 1e-6))).  The gradients are
+    not touched; nothing is read on the host."""
+    lib = _lib.load()
+    segs = _optim_table(segs, T, "grad_norm")
+    dev, role = segs.device, "grad_norm: "
+    out2 = _buf((2,), torch.float32, dev, role + "out2")
+    with torch.cuda.device(dev):
+        ws = _buf(max(lib.gnnrag_optim_workspace_bytes(n_chunks), 16), torch.uint8, dev, role + "workspace")
+        _lib.check(lib.gnnrag_grad_norm(segs.data_ptr(), T, n_chunks, float(max_norm), out2.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), _stream()), "gnnrag_grad_norm")
+    return out2
+
+
+def adam_step(segs: torch.Tensor, T: int, n_chunks: int, clip_coef: Optional[torch.Tensor] = None) -> None:
+    """One ``torch.optim.Adam`` step over every tensor of the table in one launch (``gnnrag_adam_step``): p, m and v are
+    updated in place, g is read and NOT rewritten.  clip_coef: a device float tensor whose first element scales every
+    gradient as it is read (``grad_norm(...)[1:]``), None for no clipping."""
+    lib = _lib.load()
+    segs = _optim_table(segs, T, "adam_step")
+    if clip_coef is not None:
+        clip_coef = _chk(clip_coef, "clip_coef")
+        if clip_coef.numel() < 1 or clip_coef.device != segs.device:
+            raise ValueError("adam_step: clip_coef must hold one float on the table's device")
+    with torch.cuda.device(segs.device):
+        _lib.check(lib.gnnrag_adam_step(segs.data_ptr(), T, n_chunks, _ptr(clip_coef), _stream()), "gnnrag_adam_step")
+
+
 MAX_INS = 8                                     # GNNRAG_MAX_INS (include/gnnrag.h)
 
 

@@ -1051,6 +1051,58 @@ int gnnrag_rule_paths(const gnnrag_ugraph* graph, const int32_t* fact_rel, const
                       int32_t* path_nodes, int32_t* path_facts, void* workspace, size_t workspace_bytes,
                       gnnrag_stream_t stream);
 
+/* ---- Optimiser step (additive to ABI 16; optim.hip) -----------------------------------------------------------------------
+ * The two statements that end a training step (gnn/train_model.py:228-230): torch.nn.utils.clip_grad_norm_ over a list of
+ * gradients and torch.optim.Adam.step (torch/optim/adam.py::_single_tensor_adam, non-capturable; no amsgrad, no maximize,
+ * coupled weight decay) over a list of tensors, in three launches whatever the number of tensors.  All math is fp32 except
+ * the one sum named below; no atomics; one summation order, so a second call on the same inputs gives the same bits.
+ *
+ * A DEVICE array of gnnrag_optim_seg, one entry per tensor, drives the three kernels.  The unit of work is a chunk of
+ * GNNRAG_OPTIM_CHUNK elements of one tensor; first_chunk is the prefix sum of ceil(n / GNNRAG_OPTIM_CHUNK) over the entries
+ * before this one (entry 0: 0) and n_chunks of the calls below is that sum over all T entries.  A tensor's last chunk is
+ * handled by element count (nothing is padded, nothing is read or written past n).  A tensor whose pointers (g alone for
+ * the norm; p, g, m and v for the step) are all 16-byte aligned is accessed 16 bytes at a time, any other 4 bytes at a time:
+ * the same values either way.  An entry with n == 0 owns no chunk and is never touched.
+ *
+ * The scalars are what torch forms on the host in double and hands to fp32 ops, each rounded to fp32 once: beta2,
+ * om_beta1 = 1 - beta1 and om_beta2 = 1 - beta2 (the weights of lerp_ and addcmul_), eps, weight_decay,
+ * step_size = lr / (1 - beta1^t) and bc2_sqrt = sqrt(1 - beta2^t) with t the tensor's step count AFTER its increment.
+ * Per-tensor scalars cover parameter groups and per-parameter step counts without further machinery.  80 bytes: four
+ * pointers, two int64 and eight floats (the six named quantities do not fit the 64 bytes first planned for them, and
+ * 1 - beta formed in fp32 from a rounded beta would be off by 1e-5 relative for beta2 = 0.999). */
+#define GNNRAG_OPTIM_CHUNK 4096
+typedef struct gnnrag_optim_seg {
+  float* p;              /* parameter, updated in place (gnnrag_adam_step only)                      */
+  const float* g;        /* gradient, never written                                                  */
+  float* m;              /* exp_avg, updated in place (gnnrag_adam_step only)                        */
+  float* v;              /* exp_avg_sq, updated in place (gnnrag_adam_step only)                     */
+  int64_t n;             /* elements                                                                 */
+  int64_t first_chunk;   /* chunks of the entries before this one                                    */
+  float beta1, beta2, om_beta1, om_beta2, eps, weight_decay, step_size, bc2_sqrt;
+} gnnrag_optim_seg;
+
+/* gnnrag_grad_norm: out2[0] = total_norm = sqrt(sum over all tensors of sum g^2), out2[1] = clip_coef =
+ * min(1, max_norm / (total_norm + 1e-6)) as clip_grad_norm_ forms it (a NaN norm gives a NaN coefficient; an infinite one
+ * gives 0).  Reads g, n and first_chunk of an entry only.  Two launches: per chunk, the thread-strided fp32 sum of squares
+ * through the library's block sum into the workspace; then one workgroup adds the chunks' sums in ascending chunk order in
+ * double and rounds the root to fp32 once.  workspace: gnnrag_optim_workspace_bytes(n_chunks) bytes (0 for n_chunks <= 0);
+ * every byte the second launch reads was written by the first.
+ * gnnrag_adam_step: per element, in torch's order,
+ *   g' = g * clip_coef[0]  (clip_coef a DEVICE pointer, e.g. out2 + 1; NULL: no clipping)
+ *   g' += weight_decay * p  (if weight_decay != 0)
+ *   m  += (g' - m) * om_beta1                      (lerp_; the other branch of lerp's formula where om_beta1 >= 0.5)
+ *   v   = v * beta2 + om_beta2 * g' * g'
+ *   p  -= step_size * m / (sqrt(v) / bc2_sqrt + eps)        with IEEE division and square root
+ * One launch; writes p, m and v and nothing else: g is NOT rescaled (clip_grad_norm_ rescales .grad in place).
+ * Both: a NULL segs / out2, T <= 0, n_chunks <= 0 or max_norm not > 0 (NaN included) is GNNRAG_E_BADARG, a workspace that is
+ * NULL or below the stated size GNNRAG_E_WORKSPACE, both before a device is touched.  Nothing is allocated, nothing waits
+ * for the stream.  The table must stay unchanged until the launches have run (it is read on the device). */
+size_t gnnrag_optim_workspace_bytes(int64_t n_chunks);
+int gnnrag_grad_norm(const gnnrag_optim_seg* segs, int32_t T, int64_t n_chunks, float max_norm, float* out2,
+                     void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
+int gnnrag_adam_step(const gnnrag_optim_seg* segs, int32_t T, int64_t n_chunks, const float* clip_coef,
+                     gnnrag_stream_t stream);
+
 /* Plain HBM copy kernel (float4 per lane) used by bench.py to measure the achievable
  * streaming ceiling next to the 8 TB/s spec.  n = number of floats (multiple of 4). */
 int gnnrag_stream_copy(const float* src, float* dst, int64_t n, gnnrag_stream_t stream);

@@ -173,6 +173,16 @@ def main():
         install.patch_rel_feature(self.model)
 
     evaluate.Evaluator.__init__ = _init_rel_text
+    # the clip + Adam that end every training step as one optimizer.clip_and_step (gnnrag_amd.optim; GNNRAG_HIP_OPTIM, read
+    # at every call, default off): the trainer's optimiser exists once optim_def has run (train_model.py:89-94)
+    import train_model
+    _optim_def = train_model.Trainer_KBQA.optim_def
+
+    def _optim_def_patched(self, *a, **kw):
+        _optim_def(self, *a, **kw)
+        install.patch_trainer(self)
+
+    train_model.Trainer_KBQA.optim_def = _optim_def_patched
     if world > 1 or force_dist:
         from gnnrag_amd import shard
         _ev_init = evaluate.Evaluator.__init__

@@ -83,6 +83,7 @@ def main():
     from utils import create_logger
     tr = Trainer_KBQA(args=vars(args), model_name=args.model_name, logger=create_logger(args))
     tr.load_ckpt(os.path.join(stage_ref.CKPT, stage_ref.ckpt_name(a.variant)))
+    fused_optim = False          # the clip + Adam as one optimizer.clip_and_step (GPU leg with GNNRAG_HIP_OPTIM=1)
     if not a.pure:
         from gnnrag_amd.data.fact_mat import patch_loader
         patch_loader(tr.train_data, cache=False, keep_rng_stream=True)
@@ -118,10 +119,14 @@ def main():
             lm_calls["train_metrics"] += 1
             return _metrics(*args, **kw)
         ops.kl_loss_train, ops.train_metrics = _kl_counted, _metrics_counted
+        # the clip + Adam that end the step as one optimizer.clip_and_step; acts only with GNNRAG_HIP_OPTIM=1
+        from gnnrag_amd import optim as hip_optim
+        hip_optim.patch_adam(tr.optim_model)
+        fused_optim = hip_optim.enabled()
     qr_calls = []                # reforms per ops.query_reform_train call (none with the switch off)
     lt_calls = []                # ops.layer_tail_train calls (none without GNNRAG_HIP_LAYER_TAIL_TRAIN=1)
     lm_calls = {"kl_loss_train": 0, "train_metrics": 0}     # none without GNNRAG_HIP_LOSS_METRICS=1
-    sync = (lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
+    sync =(lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
     tr.model.train()
     tr.train_data.reset_batches(is_sequential=False)
@@ -139,8 +144,11 @@ def main():
         loss.backward()
         sync()
         t.append(time.perf_counter())
-        torch.nn.utils.clip_grad_norm_([p for _, p in tr.model.named_parameters()], tr.args["gradient_clip"])
-        tr.optim_model.step()
+        if fused_optim:
+            tr.optim_model.clip_and_step([p for _, p in tr.model.named_parameters()], tr.args["gradient_clip"])
+        else:
+            torch.nn.utils.clip_grad_norm_([p for _, p in tr.model.named_parameters()], tr.args["gradient_clip"])
+            tr.optim_model.step()
         losses.append(loss.item())
         sync()
         t.append(time.perf_counter())
@@ -169,6 +177,8 @@ def main():
            "hip_loss_metrics": None if a.pure else os.environ.get("GNNRAG_HIP_LOSS_METRICS", "default"),
            "kl_loss_train_calls_per_step": lm_calls["kl_loss_train"] / float(a.warm + a.steps),
            "train_metrics_calls_per_step": lm_calls["train_metrics"] / float(a.warm + a.steps),
+           "hip_optim": None if a.pure else os.environ.get("GNNRAG_HIP_OPTIM", "default"),
+           "optim_library_steps_per_step": 0.0 if a.pure else tr.optim_model._gnnrag_optim.calls / float(a.warm + a.steps),
            "h1_f1_last_step": [float(np.mean(x)) for x in tp_list] if tp_list else None}
     import shutil
     shutil.rmtree(ck, ignore_errors=True)
