@@ -192,6 +192,12 @@ SIGNATURES = {
     "gnnrag_layer_tail_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "gnnrag_layer_tail_backward": (C.c_int, [_VP] * 3 + [C.c_float] + [_VP] * 3 + [C.c_int32] * 3 + [_VP] * 4 +
                                    [C.c_size_t, _VP]),
+    # the concatenated update under dropout, forward and backward (additive to ABI 16)
+    "gnnrag_update_drop_train": (C.c_int, [_VP] * 3 + [C.c_float] + [_VP] * 2 + [C.c_int64, C.c_int32, C.c_int32, _VP,
+                                           C.c_int32, _VP]),
+    "gnnrag_update_drop_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "gnnrag_update_drop_backward": (C.c_int, [_VP] * 4 + [C.c_float, _VP, C.c_int64, C.c_int32, C.c_int32] + [_VP] * 5 +
+                                    [C.c_size_t, C.c_int32, _VP]),
     # training loss and batch metrics (additive to ABI 16)
     "gnnrag_kl_loss_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gnnrag_kl_loss_train": (C.c_int, [_VP] * 3 + [C.c_int32] * 2 + [_VP] * 3 + [C.c_size_t, _VP]),

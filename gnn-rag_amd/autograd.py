@@ -10,7 +10,8 @@ encoder's LSTM trains on :class:`LstmFn` (``gnnrag_lstm_forward_train`` / ``gnnr
 features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text_pool_backward``), instruction generation on
 :class:`InstructionsFn` (``gnnrag_instructions_train`` / ``gnnrag_instructions_backward``), the instruction update between
 two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``), the tail of the
-reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``), the KL loss behind
+reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``), the concatenated update under
+dropout on :class:`UpdateDropFn` (``gnnrag_update_drop_train`` / ``gnnrag_update_drop_backward``), the KL loss behind
 the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``)."""
 from __future__ import annotations
 
@@ -304,6 +305,35 @@ class LayerTailFn(torch.autograd.Function):
         return (g_pre if nig[0] else None, g_pre if (ctx.has_b and nig[1]) else None, None, None,
                 None if g["dw"] is None else g["dw"].view(ctx.w_shape), None if g["db"] is None else g["db"].view(ctx.b_shape),
                 None)
+
+
+class UpdateDropFn(torch.autograd.Function):
+    """``pre = e2e_linear(linear_drop(cat(h, agg)))`` (reasongnn.py:161-163 in training) on ``gnnrag_update_drop_train`` /
+    ``gnnrag_update_drop_backward``: h [B*N,D], agg [B*N,2*I*D], keep [B*N,(2I+1)D] uint8 / scale the dropout (keep None: none),
+    W [D,(2I+1)D], b [D].  Saves h, agg, keep and W - not the dropped operand, which neither direction ever stores; h, agg,
+    W and b receive the gradients ``needs_input_grad`` asks for, an output nobody asks for is not computed."""
+
+    @staticmethod
+    def forward(ctx, h, agg, keep, scale, W, b):
+        h, agg = h.detach().float().contiguous(), agg.detach().float().contiguous()
+        Wd = W.detach().float().contiguous()
+        pre = ops.update_drop_train(h, agg, keep, scale, Wd, b.detach().float().contiguous())
+        ctx.scale, ctx.has_keep = float(scale), keep is not None
+        ctx.save_for_backward(h, agg, Wd, *([keep] if keep is not None else []))
+        return pre
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pre):
+        h, agg, Wd = ctx.saved_tensors[:3]
+        keep = ctx.saved_tensors[3] if ctx.has_keep else None
+        nig = ctx.needs_input_grad
+        if not (nig[0] or nig[1] or nig[4] or nig[5]):
+            return (None,) * 6
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as pre.sum().backward() delivers
+        g = ops.update_drop_backward(g_pre.float(), h, agg, keep, ctx.scale, Wd, need_h=nig[0], need_agg=nig[1],
+                                     need_dW=nig[4], need_db=nig[5])
+        return g["g_h"], g["g_agg"], None, None, g["dW"], g["db"]
 
 
 class KLLossFn(torch.autograd.Function):

@@ -43,6 +43,12 @@ struct FrontierArgs;                       // seed_prologue.h
 int frontier_args(const gnnrag_csr* csr, const float* dist, void* fws, size_t fws_bytes, float* zero_a, int64_t zero_na,
                   float* zero_b, int64_t zero_nb, FrontierArgs* a);
 
+// gemm_tn.hip: C [N1, N2] = A^T . Bd with Bd = keep ? [B0 | B1] * scale : +0 (B0 [M, K0], B1 [M, N2 - K0], keep [M, N2]
+// 0/1 bytes or null) formed as B is loaded; gnnrag_gemm_tn's chunks, reduce and workspace.  The caller has checked
+// N1 % 4 == K0 % 4 == N2 % 4 == 0, 16-byte aligned float operands and a 4-byte aligned keep.
+int gemm_tn_drop(const float* A, const float* B0, const float* B1, const uint8_t* keep, float scale, int64_t M, int32_t N1,
+                 int32_t K0, int32_t N2, float* C, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
 // gnnrag_update_score_fused with the promise that `score` already holds zeros
 int update_score_fused_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
                          const float* b_s, const float* mask, float* h_out, float* score, int64_t BN, int32_t D,

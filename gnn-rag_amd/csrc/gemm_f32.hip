@@ -37,7 +37,9 @@ namespace gnnrag {
 constexpr int kBK = 32;    // k per LDS tile
 constexpr int kSkinnyMaxM = 16384;   // up to here a problem runs on k_gemm_skinny (one wave per 16 x 64 tile, no LDS)
 
-enum { EPI_LINEAR = 0, EPI_UPDATE = 1 };
+// EPI_KEEP: EPI_LINEAR whose stored tile is multiplied by `scale` and gated by the keep bytes of its elements (the
+// input gradient of a product under dropout, gnnrag_update_drop_backward); float4 epilogue only
+enum { EPI_LINEAR = 0, EPI_UPDATE = 1, EPI_KEEP = 2 };
 
 struct GemmArgs {
   const float* A0;      // [M, K0]  (plain: K0 = K; update: h, K0 = D)
@@ -57,16 +59,41 @@ struct GemmArgs {
   int32_t n0;           // first output column of this launch's column block (EPI_LINEAR, Nout > 208)
   int32_t ldw;          // row stride of W in floats (>= K; e2e_linear column blocks are used in place)
   int32_t wc0;          // first column of W used (AMODE_PLAIN)
+  float scale;          // AMODE_DROP / EPI_KEEP: the dropout scale 1 / (1 - p) (1 without a keep mask)
   // AMODE_GEN (per-question relation tables): row m = compact row (b, r) = gen_rows[m], column k = (i, kk):
   //   A[m,k] = relu(A0[r*D + kk] * A1[(b*I + i)*D + kk]),  W column = (1 + 2i + gen_dir)*D + kk
   const int2* gen_rows;
-  int32_t gen_D, gen_I, gen_dir;
+  union {
+    int32_t gen_D;
+    int32_t ldkeep;     // AMODE_DROP / EPI_KEEP: row stride of `keep` in bytes (the K of the concatenated operand)
+  };
+  int32_t gen_I, gen_dir;
   int32_t v4out;        // rows of C/add are 16-byte aligned and Nout % 4 == 0: float4 epilogue
-  const uint8_t* add_flag;   // k_gemm_wres<.., AFL>: row gates of `add` [M + 4]; a row whose byte is 0 reads the zero row
+  union {
+    const uint8_t* add_flag; // k_gemm_wres<.., AFL>: row gates of `add` [M + 4]; a row whose byte is 0 reads the zero row
                              // `add + M * Nout` behind the buffer (frontier layers, frontier.hip)
+    const uint8_t* keep;     // k_gemm_f32<AMODE_DROP> / <EPI_KEEP>: 0/1 bytes, element (m, k) at keep[m * ldkeep + k] with k
+                             // counted from the launch's first A column (AMODE_DROP) or output column 0 (EPI_KEEP); null:
+                             // everything is kept.  No kernel reads both members, and the two share the slot so that
+                             // the argument block of the older instantiations is what it was.
+  };
 };
 
-enum { AMODE_PLAIN = 0, AMODE_GEN = 1 };
+// AMODE_DROP: the split operand [A0 | A1] under dropout, xd = keep ? x * scale : +0, formed as the tile is loaded (one
+// fp32 multiply per element, in front of the bf16 split): the dropped copy never exists in memory.  V4 forms only.
+enum { AMODE_PLAIN = 0, AMODE_GEN = 1, AMODE_DROP = 2 };
+
+constexpr unsigned kKeepAll = 0x01010101u;      // the four keep bytes of a float4 without a mask
+
+// v * scale where the element's keep byte (byte j of kb) is set, +0 elsewhere (a select: an Inf or NaN that was dropped
+// leaves nothing)
+__device__ __forceinline__ f32x4 keep4(f32x4 v, float scale, unsigned kb) {
+  v *= scale;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (((kb >> (8 * j)) & 0xffu) == 0u) v[j] = 0.f;
+  return v;
+}
 
 // 4 consecutive k of logical row m of A (= [A0 | A1], or generated); zero beyond M / K.
 template <bool V4, int AMODE>
@@ -96,6 +123,13 @@ __device__ __forceinline__ f32x4 load_a4(const GemmArgs& g, int m, int k) {
       }
     }
     return v;
+  } else if constexpr (AMODE == AMODE_DROP) {
+    static_assert(V4, "the dropout loader reads a float4 and the four keep bytes beside it");
+    if (k < g.K) {
+      v = (k < g.K0) ? *reinterpret_cast<const f32x4*>(g.A0 + (size_t)m * g.K0 + k)
+                     : *reinterpret_cast<const f32x4*>(g.A1 + (size_t)m * (g.K - g.K0) + (k - g.K0));
+      v = keep4(v, g.scale, g.keep ? *reinterpret_cast<const unsigned*>(g.keep + (size_t)m * g.ldkeep + k) : kKeepAll);
+    }
   } else if constexpr (V4) {
     // K0, K-K0 multiples of 4 and 16-byte aligned bases: a float4 never straddles the split.
     if (k < g.K0) v = *reinterpret_cast<const f32x4*>(g.A0 + (size_t)m * g.K0 + k);
@@ -374,6 +408,16 @@ void k_gemm_f32(GemmArgs g) {
         if (v4out && lane_cols && g.add && row < g.add_rows && row < g.M)
           addv[u] = *reinterpret_cast<const f32x4*>(g.add + (size_t)row * g.Nout + colv);
       }
+      unsigned kw[8];                                // EPI_KEEP: the rows' keep bytes, requested together as well
+      if constexpr (EPI == EPI_KEEP) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int row = row0 + rb + u;
+          kw[u] = kKeepAll;
+          if (lane_cols && g.keep && row < g.M)
+            kw[u] = *reinterpret_cast<const unsigned*>(g.keep + (size_t)row * g.ldkeep + colv);
+        }
+      }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int rr = rb + u;
@@ -386,6 +430,7 @@ void k_gemm_f32(GemmArgs g) {
             if (v4out) {
               v += addv[u];
               if (EPI == EPI_UPDATE || g.relu) v = __builtin_elementwise_max(v, zero4);
+              if constexpr (EPI == EPI_KEEP) v = keep4(v, g.scale, kw[u]);
               *reinterpret_cast<f32x4*>(crow) = v;
             } else {
               const bool has_add = g.add && row < g.add_rows;
@@ -944,26 +989,33 @@ static int launch_gemm(GemmArgs g, hipStream_t stream, int math) {
   g.v4out = f.v4out;
 #define GNNRAG_GEMM_LAUNCH(NT, MT, V, MATH, NW) \
   hipLaunchKernelGGL((k_gemm_f32<NT, MT, V, EPI, AMODE, MATH, NW>), grid, dim3(64 * NW), 0, stream, g)
+  // the dropout loader and the keep epilogue exist in the float4 forms only
+#define GNNRAG_GEMM_SCALAR(NT, MT, NW)                                              \
+  do {                                                                              \
+    if constexpr (EPI == EPI_KEEP || AMODE == AMODE_DROP) return GNNRAG_E_UNSUPPORTED; \
+    else GNNRAG_GEMM_LAUNCH(NT, MT, false, 0, NW);                                  \
+  } while (0)
 #define GNNRAG_GEMM_CASE(NT)                                                        \
   do {                                                                              \
     if (f.mt == 1 && f.nw == 8) {                                                   \
       if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 8);                    \
       else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 8);                         \
-      else GNNRAG_GEMM_LAUNCH(NT, 1, false, 0, 8);                                  \
+      else GNNRAG_GEMM_SCALAR(NT, 1, 8);                                            \
     } else if (f.mt == 1) {                                                         \
       if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 1, true, 1, 4);                    \
       else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 1, true, 0, 4);                         \
-      else GNNRAG_GEMM_LAUNCH(NT, 1, false, 0, 4);                                  \
+      else GNNRAG_GEMM_SCALAR(NT, 1, 4);                                            \
     } else {                                                                        \
       if (f.v4 && f.math) GNNRAG_GEMM_LAUNCH(NT, 2, true, 1, 4);                    \
       else if (f.v4) GNNRAG_GEMM_LAUNCH(NT, 2, true, 0, 4);                         \
-      else GNNRAG_GEMM_LAUNCH(NT, 2, false, 0, 4);                                  \
+      else GNNRAG_GEMM_SCALAR(NT, 2, 4);                                            \
     }                                                                               \
   } while (0)
   if (f.nt == 4) GNNRAG_GEMM_CASE(4);
   else if (f.nt == 8) GNNRAG_GEMM_CASE(8);
   else GNNRAG_GEMM_CASE(13);
 #undef GNNRAG_GEMM_CASE
+#undef GNNRAG_GEMM_SCALAR
 #undef GNNRAG_GEMM_LAUNCH
   GNNRAG_LAUNCH_CHECK();
   return 0;
@@ -1057,9 +1109,154 @@ static GemmArgs update_fused_args(const float* h, const float* nbr, const uint8_
   return g;
 }
 
+// ---- the concatenated update under dropout (gnnrag_update_drop_train / _backward) ------------------------------------
+// forward: pre = xd . W^T + b over the split operand [h | agg], the dropout formed in the tile loader
+static GemmArgs drop_fwd_args(const float* h, const float* agg, const uint8_t* keep, float scale, const float* W,
+                              const float* b, float* pre, int64_t BN, int32_t D, int32_t I) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A0 = h; g.A1 = agg; g.W = W; g.bias = b; g.C = pre;
+  g.M = (int32_t)BN; g.K = (2 * I + 1) * D; g.K0 = D; g.Nout = D; g.ldw = g.K;
+  g.keep = keep; g.ldkeep = g.K; g.scale = keep ? scale : 1.f;
+  return g;
+}
+
+// backward, input gradient: columns [c0, c0 + ncols) of g_x = keep ? scale * (g_pre . W) : +0 as one product against rows
+// c0.. of the transposed weight Wt [K, D]; `out` [BN, ncols] is g_h (c0 = 0) or g_agg (c0 = D), keep keeps its stride K
+static GemmArgs drop_dx_args(const float* g_pre, const float* Wt, const uint8_t* keep, float scale, float* out, int64_t BN,
+                             int32_t D, int32_t I, int32_t c0, int32_t ncols) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A0 = g_pre; g.W = Wt + (size_t)c0 * D; g.C = out;
+  g.M = (int32_t)BN; g.K = D; g.K0 = D; g.Nout = ncols; g.ldw = D;
+  g.keep = keep ? keep + c0 : nullptr; g.ldkeep = (2 * I + 1) * D; g.scale = keep ? scale : 1.f;
+  return g;
+}
+
+// the limits both entries share (after the argument rules): what the float4 loaders and the 4-byte keep loads need
+static bool drop_shape_ok(int64_t BN, int32_t D, int32_t I) {
+  return D % 4 == 0 && BN < ((int64_t)1 << 31) && (int64_t)(2 * (int64_t)I + 1) * D < ((int64_t)1 << 31);
+}
+
+// db: k_colsum gives one job 8 row slices per 32 columns - seven workgroups for a whole node range at D = 200, each
+// thread adding thousands of rows one after the other.  Two things spread the rows: g_pre [BN, D] is read as
+// [BN / r, r D] (r = kDropDbFold consecutive rows side by side: r times the columns, 1 / r of the rows, the sums of the
+// rows = i mod r come out as r partial rows), and the folded rows are cut into up to GNNRAG_MAX_INS + 2 jobs of one
+// launch.  The rows left over by the fold are copied behind the partial rows, and one more job adds all of them.  Fixed by
+// (BN, D) alone.
+constexpr int kDropDbFold = 16;
+constexpr int kDropDbJobs = GNNRAG_MAX_INS + 2;
+constexpr int kDropDbPartRows = kDropDbJobs * kDropDbFold + kDropDbFold;
+struct DropDbPlan {
+  int r, jobs;            // fold, colsum jobs of the first launch
+  int64_t q, rows, rem;   // folded rows, folded rows per job, rows left over by the fold
+};
+static DropDbPlan drop_db_plan(int64_t BN, int32_t D) {
+  DropDbPlan p;
+  p.r = (BN >= (int64_t)kDropDbFold * 32 * kDropDbJobs && (int64_t)kDropDbFold * D < (1 << 30)) ? kDropDbFold : 1;
+  p.q = BN / p.r;
+  p.rem = BN - p.q * p.r;
+  int64_t n = p.q / 32;                               // at least 32 folded rows per job
+  n = n < 1 ? 1 : n > kDropDbJobs ? kDropDbJobs : n;
+  p.rows = (p.q + n - 1) / n;
+  p.jobs = (int)((p.q + p.rows - 1) / p.rows);
+  return p;
+}
+
+struct DropBwdLayout {
+  size_t wt, tn, tn_bytes, dbp, total;
+};
+
+static DropBwdLayout drop_bwd_layout(int64_t BN, int32_t D, int32_t I) {
+  DropBwdLayout l;
+  const int32_t K = (2 * I + 1) * D;
+  Carve cv;
+  l.wt = cv.take((size_t)K * D * sizeof(float));
+  l.tn_bytes = gnnrag_gemm_tn_workspace_bytes(BN, D, K);
+  l.tn = cv.take(l.tn_bytes);
+  l.dbp = cv.take((size_t)kDropDbPartRows * D * sizeof(float));
+  l.total = cv.off;
+  return l;
+}
+
 }  // namespace gnnrag
 
 using namespace gnnrag;
+
+extern "C" int gnnrag_update_drop_train(const float* h, const float* agg, const uint8_t* keep, float scale, const float* W,
+                                        const float* b, int64_t BN, int32_t D, int32_t I, float* pre, int32_t math,
+                                        gnnrag_stream_t stream) {
+  if (!h || !agg || !W || !b || !pre || BN <= 0 || D <= 0 || I <= 0 || !math_ok(math)) return GNNRAG_E_BADARG;
+  if (!drop_shape_ok(BN, D, I) || !aligned16(h, agg, W, pre) || ((uintptr_t)keep & 3)) return GNNRAG_E_UNSUPPORTED;
+  GemmArgs g = drop_fwd_args(h, agg, keep, scale, W, b, pre, BN, D, I);
+  for (int n0 = 0; n0 < D; n0 += 208) {
+    g.n0 = n0;
+    GNNRAG_RC((launch_gemm<EPI_LINEAR, AMODE_DROP>(g, (hipStream_t)stream, math)));
+  }
+  return 0;
+}
+
+extern "C" size_t gnnrag_update_drop_backward_workspace_bytes(int64_t BN, int32_t D, int32_t I) {
+  if (BN <= 0 || D <= 0 || I <= 0 || !drop_shape_ok(BN, D, I)) return 0;
+  return drop_bwd_layout(BN, D, I).total;
+}
+
+extern "C" int gnnrag_update_drop_backward(const float* g_pre, const float* h, const float* agg, const uint8_t* keep,
+                                           float scale, const float* W, int64_t BN, int32_t D, int32_t I, float* g_h,
+                                           float* g_agg, float* dW, float* db, void* workspace, size_t workspace_bytes,
+                                           int32_t math, gnnrag_stream_t stream_) {
+  if (!g_pre || BN <= 0 || D <= 0 || I <= 0 || !math_ok(math)) return GNNRAG_E_BADARG;
+  if (!g_h && !g_agg && !dW && !db) return GNNRAG_E_BADARG;
+  if (((g_h || g_agg) && !W) || (dW && (!h || !agg))) return GNNRAG_E_BADARG;
+  if (!drop_shape_ok(BN, D, I) || !aligned16(g_pre, h, agg, W, g_h, g_agg, dW, workspace) || ((uintptr_t)keep & 3))
+    return GNNRAG_E_UNSUPPORTED;
+  const DropBwdLayout l = drop_bwd_layout(BN, D, I);
+  if (!workspace || workspace_bytes < l.total) return GNNRAG_E_WORKSPACE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int32_t K = (2 * I + 1) * D;
+  if (!keep) scale = 1.f;
+  if (g_h || g_agg) {
+    float* Wt = (float*)((char*)workspace + l.wt);
+    GNNRAG_RC(transpose_launch(W, Wt, D, K, stream));
+    // two launch loops: a block of 208 does not end on a multiple of D, and each output is contiguous on its own
+    float* const outs[2] = {g_h, g_agg};
+    const int32_t c0s[2] = {0, D}, ncs[2] = {D, K - D};
+    for (int o = 0; o < 2; ++o) {
+      if (!outs[o]) continue;
+      GemmArgs g = drop_dx_args(g_pre, Wt, keep, scale, outs[o], BN, D, I, c0s[o], ncs[o]);
+      for (int n0 = 0; n0 < ncs[o]; n0 += 208) {
+        g.n0 = n0;
+        GNNRAG_RC((launch_gemm<EPI_KEEP, AMODE_PLAIN>(g, stream, math)));
+      }
+    }
+  }
+  if (dW)
+    GNNRAG_RC(gemm_tn_drop(g_pre, h, agg, keep, scale, BN, D, D, K, dW, (char*)workspace + l.tn, l.tn_bytes, stream));
+  if (db) {
+    const DropDbPlan p = drop_db_plan(BN, D);
+    float* part = (float*)((char*)workspace + l.dbp);
+    const bool direct = p.r == 1 && p.jobs == 1;        // a few rows: one job, straight into db
+    ColsumJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    jobs.cols = p.r * D;
+    for (int j = 0; j < p.jobs; ++j) {
+      const int64_t r0 = (int64_t)j * p.rows;            // in folded rows
+      jobs.src[j] = g_pre + (size_t)r0 * p.r * D;
+      jobs.dst[j] = direct ? db : part + (size_t)j * p.r * D;
+      jobs.rows[j] = p.q - r0 < p.rows ? p.q - r0 : p.rows;
+      jobs.ld[j] = p.r * D;
+    }
+    GNNRAG_RC(colsum_launch(jobs, p.jobs, stream));
+    if (!direct) {
+      const int64_t prow = (int64_t)p.jobs * p.r;
+      if (p.rem) GNNRAG_RC(unpad_launch(g_pre + (size_t)p.q * p.r * D, part + (size_t)prow * D, (int)p.rem, D, D, stream));
+      memset(&jobs, 0, sizeof(jobs));
+      jobs.src[0] = part; jobs.dst[0] = db; jobs.rows[0] = prow + p.rem; jobs.ld[0] = D; jobs.cols = D;
+      GNNRAG_RC(colsum_launch(jobs, 1, stream));
+    }
+  }
+  return 0;
+}
 
 
 extern "C" int gnnrag_linear(const float* A, int64_t M, int32_t K, const float* W, const float* bias,
@@ -1217,6 +1414,32 @@ extern "C" int gnnrag_dense_form(int32_t entry, int64_t M, int32_t K, int32_t No
       }
     } else if (block) {
       return GNNRAG_E_BADARG;
+    }
+  } else if (entry == GNNRAG_DENSE_ENTRY_UPDATE_DROP || entry == GNNRAG_DENSE_ENTRY_UPDATE_DROP_DX ||
+             entry == GNNRAG_DENSE_ENTRY_UPDATE_DROP_DW) {
+    // (BN, D, I) in place of (M, K, Nout); stand-ins: A = h (DX: g_pre), A1 = agg, W (DX: the transposed copy in the
+    // workspace, aligned with it), C = pre / g_h / g_agg / dW
+    const int64_t BN = M;
+    const int32_t D = K, I = Nout;
+    memset(&f, 0, sizeof(f));
+    const bool ok = drop_shape_ok(BN, D, I) && aligned16(A, A1, W, C);
+    const int nb_h = (D + 207) / 208, nb_agg = (2 * I * D + 207) / 208;
+    if (entry == GNNRAG_DENSE_ENTRY_UPDATE_DROP_DW) {
+      if (block) return GNNRAG_E_BADARG;
+      if (ok) f.family = f.block_family = GNNRAG_DENSE_GEMM_TN;
+      f.v4 = ok;
+    } else {
+      const bool dx = entry == GNNRAG_DENSE_ENTRY_UPDATE_DROP_DX;
+      launches = dx ? nb_h + nb_agg : nb_h;
+      if (block >= launches) return GNNRAG_E_BADARG;
+      if (ok) {
+        GemmArgs g;
+        if (!dx) g = drop_fwd_args(A, A1, nullptr, 1.f, W, other, C, BN, D, I);
+        else if (block < nb_h) g = drop_dx_args(A, W, nullptr, 1.f, C, BN, D, I, 0, D);
+        else g = drop_dx_args(A, W, nullptr, 1.f, C, BN, D, I, D, 2 * I * D);
+        g.n0 = 208 * (dx && block >= nb_h ? block - nb_h : block);
+        f = dx ? gemm_form(g, EPI_KEEP, AMODE_PLAIN, math) : gemm_form(g, EPI_LINEAR, AMODE_DROP, math);
+      }
     }
   } else {
     return GNNRAG_E_BADARG;

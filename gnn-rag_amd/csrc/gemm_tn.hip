@@ -9,7 +9,13 @@
 // wave.  Workgroup = 4 waves = 4 output blocks over the same row chunk (shared operand lines hit L1); grid = row
 // chunks x groups of output blocks.  Every chunk writes its partial block; k_tn_reduce adds the chunks in chunk order
 // (no atomics: one fixed summation order).
+//
+// Masked form (gnnrag_update_drop_backward): B is the split operand [B0 | B1] under dropout, keep ? b * scale : +0 formed
+// on the loaded piece - the weight gradient of a product whose dropped operand was never stored.
+#include <type_traits>
+
 #include "gnnrag_common.h"
+#include "dense_internal.h"
 
 namespace gnnrag {
 
@@ -23,7 +29,20 @@ struct TnArgs {
   int32_t N1, N2, nb1, nb2, chunk_rows;
 };
 
-__global__ __launch_bounds__(256) void k_gemm_tn(TnArgs g) {
+// B = [B0 | B1] (B0 = TnArgs::B [M, K0], B1 [M, N2 - K0]; K0 % 4 == 0: a float4 piece lies in one of them) gated by
+// keep [M, N2] 0/1 bytes (null: everything kept) and multiplied by scale
+struct TnMaskArgs : TnArgs {
+  const float* B1;
+  const uint8_t* keep;
+  int32_t K0;
+  float scale;
+};
+
+// Args = TnArgs: the plain product.  Args = TnMaskArgs: the masked B operand (the plain instantiation keeps its own
+// argument block, so its code does not move with the masked form's fields).
+template <typename Args>
+__global__ __launch_bounds__(256) void k_gemm_tn(Args g) {
+  constexpr bool MASKB = std::is_same<Args, TnMaskArgs>::value;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fg = lane >> 4;
   const int blk = blockIdx.x * 4 + wave;                      // this wave's 64 x 64 output block
@@ -41,12 +60,28 @@ __global__ __launch_bounds__(256) void k_gemm_tn(TnArgs g) {
     for (int y = 0; y < 4; ++y) acc[x][y] = zero4;
   for (int64_t m0 = m_beg; m0 < m_end; m0 += 4 * kTnUnroll) {
     f32x4 av[kTnUnroll], bv[kTnUnroll];
+    unsigned kb[kTnUnroll];
 #pragma unroll
     for (int u = 0; u < kTnUnroll; ++u) {
       const int64_t m = m0 + 4 * u + fg;
       const int64_t mc = m < g.M ? m : g.M - 1;               // clamped address: no branch around a load
       av[u] = *reinterpret_cast<const f32x4*>(g.A + mc * g.N1 + ca);
-      bv[u] = *reinterpret_cast<const f32x4*>(g.B + mc * g.N2 + cb);
+      if constexpr (MASKB) {
+        bv[u] = cb < g.K0 ? *reinterpret_cast<const f32x4*>(g.B + mc * g.K0 + cb)
+                          : *reinterpret_cast<const f32x4*>(g.B1 + mc * (g.N2 - g.K0) + (cb - g.K0));
+        kb[u] = g.keep ? *reinterpret_cast<const unsigned*>(g.keep + mc * g.N2 + cb) : 0x01010101u;
+      } else {
+        bv[u] = *reinterpret_cast<const f32x4*>(g.B + mc * g.N2 + cb);
+      }
+    }
+    if constexpr (MASKB) {
+#pragma unroll
+      for (int u = 0; u < kTnUnroll; ++u) {
+        bv[u] *= g.scale;                                     // one fp32 multiply, then a select: a dropped Inf leaves +0
+#pragma unroll
+        for (int y = 0; y < 4; ++y)
+          if (((kb[u] >> (8 * y)) & 0xffu) == 0u) bv[u][y] = 0.f;
+      }
     }
 #pragma unroll
     for (int u = 0; u < kTnUnroll; ++u) {
@@ -99,6 +134,34 @@ static int tn_chunks(int64_t M, int32_t N1, int32_t N2, int* chunk_rows) {
   return (int)((M + rows - 1) / rows);
 }
 
+static int tn_launch(const float* A, const float* B, const float* B1, const uint8_t* keep, float scale, bool masked,
+                     int64_t M, int32_t N1, int32_t K0, int32_t N2, float* C, void* workspace, size_t workspace_bytes,
+                     hipStream_t stream) {
+  TnMaskArgs g;
+  memset(&g, 0, sizeof(g));
+  int rows = 0;
+  const int chunks = tn_chunks(M, N1, N2, &rows);
+  if (!workspace || workspace_bytes < (size_t)chunks * N1 * N2 * sizeof(float)) return GNNRAG_E_WORKSPACE;
+  g.A = A; g.B = B; g.part = (float*)workspace; g.M = M; g.N1 = N1; g.N2 = N2;
+  g.nb1 = (N1 + 63) / 64; g.nb2 = (N2 + 63) / 64; g.chunk_rows = rows;
+  g.B1 = B1; g.keep = keep; g.K0 = K0; g.scale = scale;
+  const dim3 grid((unsigned)((g.nb1 * g.nb2 + 3) / 4), (unsigned)chunks);
+  if (masked) hipLaunchKernelGGL(k_gemm_tn<TnMaskArgs>, grid, dim3(256), 0, stream, g);
+  else hipLaunchKernelGGL(k_gemm_tn<TnArgs>, grid, dim3(256), 0, stream, static_cast<const TnArgs&>(g));
+  GNNRAG_LAUNCH_CHECK();
+  const int64_t n4 = (int64_t)N1 * N2 / 4;
+  hipLaunchKernelGGL(k_tn_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, (const f32x4*)workspace,
+                     (f32x4*)C, n4, chunks);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the caller has checked the shapes and the alignment (gnnrag_update_drop_backward); M > 0
+int gemm_tn_drop(const float* A, const float* B0, const float* B1, const uint8_t* keep, float scale, int64_t M, int32_t N1,
+                 int32_t K0, int32_t N2, float* C, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+  return tn_launch(A, B0, B1, keep, keep ? scale : 1.f, true, M, N1, K0, N2, C, workspace, workspace_bytes, stream);
+}
+
 }  // namespace gnnrag
 
 using namespace gnnrag;
@@ -119,19 +182,5 @@ extern "C" int gnnrag_gemm_tn(const float* A, const float* B, int64_t M, int32_t
     GNNRAG_HIP(hipMemsetAsync(C, 0, (size_t)N1 * N2 * sizeof(float), (hipStream_t)stream));
     return 0;
   }
-  TnArgs g;
-  memset(&g, 0, sizeof(g));
-  int rows = 0;
-  const int chunks = tn_chunks(M, N1, N2, &rows);
-  if (!workspace || workspace_bytes < (size_t)chunks * N1 * N2 * sizeof(float)) return GNNRAG_E_WORKSPACE;
-  g.A = A; g.B = B; g.part = (float*)workspace; g.M = M; g.N1 = N1; g.N2 = N2;
-  g.nb1 = (N1 + 63) / 64; g.nb2 = (N2 + 63) / 64; g.chunk_rows = rows;
-  const int groups = (g.nb1 * g.nb2 + 3) / 4;
-  hipLaunchKernelGGL(k_gemm_tn, dim3((unsigned)groups, (unsigned)chunks), dim3(256), 0, (hipStream_t)stream, g);
-  GNNRAG_LAUNCH_CHECK();
-  const int64_t n4 = (int64_t)N1 * N2 / 4;
-  hipLaunchKernelGGL(k_tn_reduce, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const f32x4*)workspace, (f32x4*)C, n4, chunks);
-  GNNRAG_LAUNCH_CHECK();
-  return 0;
+  return tn_launch(A, B, nullptr, nullptr, 1.f, false, M, N1, N2, N2, C, workspace, workspace_bytes, (hipStream_t)stream);
 }

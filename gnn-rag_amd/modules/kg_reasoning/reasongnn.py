@@ -21,7 +21,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ...autograd import AggregateFn, FusedAggregateFn, LayerTailFn, linear as ag_linear, relation_tables_dense
+from ...autograd import (AggregateFn, FusedAggregateFn, LayerTailFn, UpdateDropFn, linear as ag_linear,
+                         relation_tables_dense)
 from .base_gnn import BaseGNNLayer
 
 VERY_NEG_NUMBER = -100000000000
@@ -289,12 +290,19 @@ class ReasonGNNLayer(BaseGNNLayer):
             # e2e_linear over cat(h, agg) as two products (no [BN, (2I+1)D] copy of the concatenation): dropout acts
             # elementwise, so dropping the two parts separately is the same operator (reasongnn.py:161-163)
             W = e2e_linear.weight
-            pre_self = ag_linear(self.linear_drop(self.local_entity_emb.float()).reshape(B * N, D), W[:, :D], e2e_linear.bias)
-            pre_nbr = ag_linear(self.linear_drop(agg), W[:, D:], None)
-            got = self._layer_tail(pre_self, pre_nbr, return_score)
-            if got is not None:
-                return got
-            pre = pre_self + pre_nbr
+            pre = self._update_drop(agg, e2e_linear) if drop_active else None
+            if pre is not None:          # one product over [h | agg] with the dropout inside its tile loader
+                got = self._layer_tail(pre, None, return_score)
+                if got is not None:
+                    return got
+            else:
+                pre_self = ag_linear(self.linear_drop(self.local_entity_emb.float()).reshape(B * N, D), W[:, :D],
+                                     e2e_linear.bias)
+                pre_nbr = ag_linear(self.linear_drop(agg), W[:, D:], None)
+                got = self._layer_tail(pre_self, pre_nbr, return_score)
+                if got is not None:
+                    return got
+                pre = pre_self + pre_nbr
             self.local_entity_emb = F.relu(pre).view(B, N, D)
         else:
             state = torch.cat((self.local_entity_emb.float(), agg.view(B, N, -1)), dim=2)  # [h | fwd_0 | inv_0 | ...]
@@ -308,6 +316,30 @@ class ReasonGNNLayer(BaseGNNLayer):
         score = self.score_func(self.linear_drop(self.local_entity_emb)).squeeze(dim=2) + (1 - mask) * VERY_NEG_NUMBER
         new_dist = self.softmax_d1(score)
         return (score, new_dist) if return_score else (new_dist, self.local_entity_emb)
+
+    def _draw_update_keep(self, rows, cols, p, device):
+        """Keep flags [rows, cols] (uint8 0/1, kept with probability 1 - p) of the dropout in front of ``e2e_linear``, in the
+        column order of cat(h, agg), from torch's generator of the device."""
+        return torch.empty((rows, cols), dtype=torch.uint8, device=device).bernoulli_(1 - p)
+
+    def _update_drop(self, agg, e2e_linear):
+        """``e2e_linear(linear_drop(cat(h, agg)))`` (reasongnn.py:161-163) as ONE autograd node on the library
+        (``autograd.UpdateDropFn``: the dropped operand is formed inside the products and never stored) when
+        ``GNNRAG_HIP_UPDATE_DROP_TRAIN=1`` (read at every call, default off), the dense projections run on the library and
+        ``linear_drop`` is active with 0 < p < 1; None otherwise - the caller then runs the two products behind torch's
+        dropout, exactly as without the switch.  The keep flags are drawn by :meth:`_draw_update_keep`: not the draws
+        ``F.dropout`` would have made - a loss curve is comparable, not equal."""
+        if os.environ.get("GNNRAG_HIP_UPDATE_DROP_TRAIN", "0") != "1":
+            return None
+        B, N, D, I, p = self.batch_size, self.max_local_entity, self.entity_dim, self.num_ins, self.linear_dropout
+        if not (self.training and 0 < p < 1 and e2e_linear.bias is not None and ops.update_drop_supported(D, I)):
+            return None
+        h = self.local_entity_emb.float().reshape(B * N, D)
+        for t in (h, agg, e2e_linear.weight, e2e_linear.bias):
+            if not (t.is_cuda and t.dtype == torch.float32):
+                return None
+        keep = self._draw_update_keep(B * N, (2 * I + 1) * D, p, agg.device)
+        return UpdateDropFn.apply(h, agg, keep, 1.0 / (1.0 - p), e2e_linear.weight, e2e_linear.bias)
 
     def _layer_tail(self, pre_a, pre_b, return_score):
         """The rest of the layer (reasongnn.py:163-169: add, relu, dropout, score_func, mask, softmax) as ONE autograd node on

@@ -567,20 +567,24 @@ def aggregate_fused_variant(plan: CsrPlan, D: int) -> int:
     return v
 
 
-DENSE_ENTRIES = {"linear": 0, "linear_pair": 1, "update_score": 2, "update_score_fused": 3}
+DENSE_ENTRIES = {"linear": 0, "linear_pair": 1, "update_score": 2, "update_score_fused": 3,
+                 # gnnrag_update_drop_train, and the masked input / weight gradient products of its backward
+                 "update_drop": 4, "update_drop_dx": 5, "update_drop_dw": 6}
 DENSE_MISALIGNED_A, DENSE_MISALIGNED_W, DENSE_MISALIGNED_C, DENSE_MISALIGNED_ADD, DENSE_MISALIGNED_A1 = 1, 2, 4, 8, 16
 (DENSE_NONE, DENSE_SKINNY, DENSE_KTILED, DENSE_WRES, DENSE_UPDATE_SKINNY, DENSE_UPDATE_B3,
- DENSE_WIDE) = range(7)
+ DENSE_WIDE, DENSE_GEMM_TN) = range(8)
+DENSE_EPI_LINEAR, DENSE_EPI_UPDATE, DENSE_EPI_KEEP = 0, 1, 2
 DENSE_KERNEL_NAMES = {DENSE_NONE: "nothing launched", DENSE_SKINNY: "k_gemm_skinny", DENSE_KTILED: "k_gemm_f32",
                       DENSE_WRES: "k_gemm_wres", DENSE_UPDATE_SKINNY: "k_update_skinny", DENSE_UPDATE_B3: "k_update_b3",
-                      DENSE_WIDE: "EPI_LINEAR column blocks + k_score_rows"}
+                      DENSE_WIDE: "EPI_LINEAR column blocks + k_score_rows", DENSE_GEMM_TN: "k_gemm_tn (masked B)"}
 DenseForm = collections.namedtuple("DenseForm", [n for n, _ in _lib.DenseFormStruct._fields_])
 
 
 def dense_form(entry: str, M: int, K: int, Nout: int, math: Optional[int] = None, add_rows: Optional[int] = None,
                misaligned: int = 0, block: int = 0) -> DenseForm:
     """Which kernel a dense call runs (``gnnrag_dense_form``: host only, the launchers' own decision function).
-    ``entry``: "linear", "linear_pair", "update_score" or "update_score_fused"; the update entry points pass
+    ``entry``: a key of DENSE_ENTRIES; the update entry points ("update_score", "update_score_fused", "update_drop" and
+    the two products of its backward, "update_drop_dx" - blocks of g_h, then those of g_agg - and "update_drop_dw") pass
     (BN, D, I) as (M, K, Nout).  ``add_rows=None``: no ``add``.  ``misaligned``: OR of DENSE_MISALIGNED_* (operands
     that are not 16-byte aligned).  ``block``: column block of a call that makes several launches.
     Returns a :class:`DenseForm`: ``family`` (DENSE_*), and for k_gemm_f32 its template arguments ``nt, mt, v4, epi,
@@ -1461,6 +1465,70 @@ def layer_tail_backward(h, dist, keep, scale, w, g_h, g_dist, need_dw: bool = Tr
                                                   _ptr(g_dist), B, N, D, out["g_pre"].data_ptr(), _ptr(out["dw"]),
                                                   _ptr(out["db"]), ws.data_ptr(), ws.numel(), _stream()),
                    "gnnrag_layer_tail_backward")
+    return out
+
+
+def update_drop_supported(D: int, I: int) -> bool:
+    """Whether ``gnnrag_update_drop_train`` / ``gnnrag_update_drop_backward`` take the hidden size and instruction count
+    (float4 loaders and 4-byte keep loads: D % 4 == 0; torch's allocations satisfy the alignment rules)."""
+    return D > 0 and I > 0 and D % 4 == 0 and (2 * I + 1) * D < 2 ** 31
+
+
+def _ud_args(h, agg, keep, scale, W, who: str):
+    h = _chk(h, "h")
+    if h.dim() != 2:
+        raise ValueError(who + ": h must be [B*N,D]")
+    BN, D = h.shape
+    agg = _chk(agg, "agg")
+    if agg.dim() != 2 or agg.shape[0] != BN or agg.shape[1] == 0 or agg.shape[1] % (2 * D):
+        raise ValueError(who + ": agg must be [B*N,2*I*D] for an h [B*N,D]")
+    I = agg.shape[1] // (2 * D)
+    K = (2 * I + 1) * D
+    W = _chk(W, "W", shape=(D, K))
+    if keep is None:
+        scale = 1.0
+    else:
+        keep, scale = _chk(keep, "keep", dtype=torch.uint8, shape=(BN, K)), float(scale)
+    return h, agg, keep, scale, W, BN, D, I, K
+
+
+def update_drop_train(h, agg, keep, scale, W, b, math: Optional[int] = None):
+    """``pre = linear_drop(cat(h, agg)) W^T + b`` (reasongnn.py:161-163 in training; ``gnnrag_update_drop_train``): h [B*N,D],
+    agg [B*N,2*I*D], ``keep`` [B*N,(2I+1)D] uint8 0/1 in the concatenation's column order with ``scale`` = 1/(1-p) (None: no
+    dropout, scale taken as 1), W [D,(2I+1)D], b [D].  The dropped operand is formed inside the product's tile loader and
+    never stored.  Returns pre [B*N,D]."""
+    lib = _lib.load()
+    h, agg, keep, scale, W, BN, D, I, K = _ud_args(h, agg, keep, scale, W, "update_drop_train")
+    b = _chk(b, "b", shape=(D,))
+    pre = _buf((BN, D), torch.float32, h.device, "update_drop_train: pre")
+    with torch.cuda.device(h.device):
+        _lib.check(lib.gnnrag_update_drop_train(h.data_ptr(), agg.data_ptr(), _ptr(keep), scale, W.data_ptr(), b.data_ptr(),
+                                                BN, D, I, pre.data_ptr(), _math(math), _stream()),
+                   "gnnrag_update_drop_train")
+    return pre
+
+
+def update_drop_backward(g_pre, h, agg, keep, scale, W, need_h: bool = True, need_agg: bool = True, need_dW: bool = True,
+                         need_db: bool = True, math: Optional[int] = None):
+    """Backward of :func:`update_drop_train` (``gnnrag_update_drop_backward``) from g_pre [B*N,D]; h / agg / keep / scale / W
+    as the forward was given them.  Returns a dict: ``g_h`` [B*N,D] and ``g_agg`` [B*N,2*I*D] (every element written, a
+    dropped one exactly +0), ``dW`` [D,(2I+1)D], ``db`` [D]; None where not wanted (its launches are then not made; all
+    four unwanted is refused by the library).  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    h, agg, keep, scale, W, BN, D, I, K = _ud_args(h, agg, keep, scale, W, "update_drop_backward")
+    g_pre = _chk(g_pre, "g_pre", shape=(BN, D))
+    dev, role = h.device, "update_drop_backward: "
+    out = {"g_h": _buf((BN, D), torch.float32, dev, role + "g_h") if need_h else None,
+           "g_agg": _buf((BN, K - D), torch.float32, dev, role + "g_agg") if need_agg else None,
+           "dW": _buf((D, K), torch.float32, dev, role + "dW") if need_dW else None,
+           "db": _buf((D,), torch.float32, dev, role + "db") if need_db else None}
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn's chunks inside): query it on h's device
+        ws = _buf(max(lib.gnnrag_update_drop_backward_workspace_bytes(BN, D, I), 16), torch.uint8, dev, role + "workspace")
+        _lib.check(lib.gnnrag_update_drop_backward(g_pre.data_ptr(), h.data_ptr(), agg.data_ptr(), _ptr(keep), scale,
+                                                   W.data_ptr(), BN, D, I, _ptr(out["g_h"]), _ptr(out["g_agg"]),
+                                                   _ptr(out["dW"]), _ptr(out["db"]), ws.data_ptr(), ws.numel(), _math(math),
+                                                   _stream()), "gnnrag_update_drop_backward")
     return out
 
 

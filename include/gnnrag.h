@@ -356,6 +356,13 @@ int gnnrag_update_score_fused(const float* h, const float* nbr, const float* W_e
 #define GNNRAG_DENSE_ENTRY_LINEAR_PAIR  1   /* above the skinny bound: two gnnrag_linear calls, the form is theirs       */
 #define GNNRAG_DENSE_ENTRY_UPDATE       2   /* gnnrag_update_score                                                     */
 #define GNNRAG_DENSE_ENTRY_UPDATE_FUSED 3   /* gnnrag_update_score_fused                                               */
+/* gnnrag_update_drop_train / _backward, (BN, D, I) as (M, K, Nout); has_add / add_rows are ignored.  _DX: the masked input
+ * gradient, blocks 0 .. ceil(D / 208) - 1 are the launches of g_h, the following ceil(2 I D / 208) those of g_agg.
+ * _DW: the masked weight gradient (GNNRAG_DENSE_GEMM_TN).  A shape or alignment outside the entries' limits:
+ * GNNRAG_DENSE_NONE. */
+#define GNNRAG_DENSE_ENTRY_UPDATE_DROP    4
+#define GNNRAG_DENSE_ENTRY_UPDATE_DROP_DX 5
+#define GNNRAG_DENSE_ENTRY_UPDATE_DROP_DW 6
 #define GNNRAG_DENSE_MISALIGNED_A   1       /* A / A0 / h                                                              */
 #define GNNRAG_DENSE_MISALIGNED_W   2
 #define GNNRAG_DENSE_MISALIGNED_C   4       /* C / C0 / h_out                                                          */
@@ -368,11 +375,12 @@ int gnnrag_update_score_fused(const float* h, const float* nbr, const float* W_e
 #define GNNRAG_DENSE_UPDATE_SKINNY 4        /* k_update_skinny                                                         */
 #define GNNRAG_DENSE_UPDATE_B3     5        /* k_update_b3 (tables_b3.hip)                                             */
 #define GNNRAG_DENSE_WIDE          6        /* D > 208: EPI_LINEAR column blocks, then k_score_rows                    */
+#define GNNRAG_DENSE_GEMM_TN       7        /* k_gemm_tn with the masked split B operand, then k_tn_reduce             */
 typedef struct gnnrag_dense_form_t {
   int32_t family;        /* GNNRAG_DENSE_*                                                                               */
   int32_t block_family;  /* family of the described GEMM launch: = family, except WIDE (SKINNY or KTILED)                */
   int32_t launches;      /* GEMM launches of the call (column blocks; x 2 for a pair above the skinny bound)             */
-  int32_t epi;           /* KTILED: 0 = EPI_LINEAR, 1 = EPI_UPDATE                                                       */
+  int32_t epi;           /* KTILED: 0 = EPI_LINEAR, 1 = EPI_UPDATE, 2 = EPI_KEEP (UPDATE_DROP_DX)                        */
   int32_t nt, mt, v4, math, nw;   /* KTILED template arguments (nt also WRES; v4 also SKINNY)                            */
   int32_t v4out, n0;     /* KTILED runtime: float4 epilogue, first output column of the block                            */
   int32_t nc, has_add, kguard;    /* WRES template arguments                                                             */
@@ -647,6 +655,40 @@ int gnnrag_layer_tail_backward(const float* h, const float* dist, const uint8_t*
                                const float* g_h, const float* g_dist, int32_t B, int32_t N, int32_t D, float* g_pre,
                                float* dw_score, float* db_score, void* workspace, size_t workspace_bytes,
                                gnnrag_stream_t stream);
+
+/* ---- The concatenated update under dropout, for training (additive to ABI 16; gemm_f32.hip, gemm_tn.hip) -----------------
+ * gnn/modules/kg_reasoning/reasongnn.py:161-163 at --linear_dropout > 0: e2e_linear(linear_drop(cat(h, agg))).  Let
+ * x = [h | agg] (rows r < BN, columns k < K = (2I+1) D, h = columns < D), keep [BN, K] uint8 0/1 in that concatenation
+ * order and xd[r,k] = keep[r,k] ? x[r,k] * scale : +0; keep NULL: no dropout, scale is taken as 1 (the convention of
+ * gnnrag_layer_tail_train).  xd is formed inside the products' tile loaders and never stored.
+ *   pre [BN, D] = xd . W^T + b          W [D, K] = e2e_linear.weight, b [D]
+ * The product xd is one fp32 multiply per element, made before the bf16 split of the bf16x3 form, so pre carries the bits
+ * gnnrag_linear gives on a materialised xd wherever the two calls run the same kernel form (gnnrag_dense_form).  One launch
+ * per column block of 208; no relu and no score (gnnrag_layer_tail_train follows).
+ * Common rules of the forward and the backward: no atomics, no allocation, nothing waits for the stream; the grid and
+ * every summation order depend on (BN, D, I, math) only, so a second call gives the same bits.  A missing required pointer
+ * or a size <= 0 is GNNRAG_E_BADARG; then D % 4 == 0, 16-byte aligned float operands, a 4-byte aligned keep and BN < 2^31,
+ * else GNNRAG_E_UNSUPPORTED; then a short workspace is GNNRAG_E_WORKSPACE.  All are answered before anything is launched. */
+int gnnrag_update_drop_train(const float* h, const float* agg, const uint8_t* keep, float scale, const float* W,
+                             const float* b, int64_t BN, int32_t D, int32_t I, float* pre, int32_t math,
+                             gnnrag_stream_t stream);
+
+/* Backward of gnnrag_update_drop_train from g_pre [BN, D]; h / agg / keep / scale / W as the forward was given them.
+ *   g_h [BN, D], g_agg [BN, 2I D]   element (r,k) of [g_h | g_agg] = keep[r,k] ? scale * sum_o g_pre[r,o] W[o,k] : +0.
+ *                                   Each is contiguous and written by the product's own epilogue, EVERY element; a dropped
+ *                                   one is a select, not a multiply (an Inf beside it does not become NaN).  One launch per
+ *                                   column block of 208 of each output, against the transposed weight in the workspace
+ *   dW [D, K] = g_pre^T . xd        the chunking and the chunk-order reduce of gnnrag_gemm_tn, the mask applied to its
+ *                                   B operand as it is loaded: the bits of gnnrag_gemm_tn on a materialised xd
+ *   db [D]                          column sums of g_pre in one fixed order (partial sums over row blocks and over the
+ *                                   rows' index mod 16 in a first launch, the partial rows added by a second)
+ * Any output NULL: not wanted, and its launches are not made; all four NULL is GNNRAG_E_BADARG.  W is required for g_h /
+ * g_agg, h and agg for dW.  workspace: gnnrag_update_drop_backward_workspace_bytes(BN, D, I) bytes, 16-byte aligned (0 for
+ * a shape outside the limits; like gnnrag_gemm_tn_workspace_bytes it depends on the current device). */
+size_t gnnrag_update_drop_backward_workspace_bytes(int64_t BN, int32_t D, int32_t I);
+int gnnrag_update_drop_backward(const float* g_pre, const float* h, const float* agg, const uint8_t* keep, float scale,
+                                const float* W, int64_t BN, int32_t D, int32_t I, float* g_h, float* g_agg, float* dW,
+                                float* db, void* workspace, size_t workspace_bytes, int32_t math, gnnrag_stream_t stream);
 
 /* ---- Training loss and batch metrics (additive to ABI 16; train_tail.hip) -------------------------------------------------
  * What follows the last dist of a training forward (gnn/models/ReaRev/rearev.py:227-243, gnn/models/NSM/nsm.py:242-250).

@@ -5,7 +5,8 @@
     python tools/asm_diff.py OLD.s NEW.s [--rename REGEX=REPL ...]
 
 A kernel is the text from its label to .Lfunc_end, comments dropped, its own symbol and the function ordinal inside
-block labels (.LBB<ordinal>_<n>) normalised, plus its .amdhsa_ descriptor (registers, LDS, scratch).  --rename rewrites
+block labels (.LBB<ordinal>_<n>) normalised, section directives dropped (a kernel that became a template instantiation
+moves from .text into a comdat group), plus its .amdhsa_ descriptor (registers, LDS, scratch).  --rename rewrites
 OLD's mangled kernel names before matching (a dropped template parameter).  Prints the kernels that differ, that
 disappeared and that are new; exit status 1 if any differ or are new.
 """
@@ -27,6 +28,8 @@ def kernels(path):
         for l in lines[beg + 1:end] + lines[d0 + 1:d1]:
             l = l.split(";")[0].strip().replace(name, "@self")
             l = re.sub(r"\.LBB\d+_", ".LBB_", l)
+            if l == ".text" or l.startswith(".section"):
+                continue        # where the linker puts the function (a template instantiation sits in a comdat group)
             if l:
                 body.append(l)
         out[name] = body

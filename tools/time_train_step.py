@@ -107,6 +107,12 @@ def main():
             lt_calls.append(1)
             return _lt_train(*args, **kw)
         ops.layer_tail_train = _lt_counted
+        _ud_train = ops.update_drop_train
+
+        def _ud_counted(*args, **kw):
+            ud_calls.append(1)
+            return _ud_train(*args, **kw)
+        ops.update_drop_train = _ud_counted
         # the KL loss and the step's H@1 / F1; act only with GNNRAG_HIP_LOSS_METRICS=1
         install.patch_loss_metrics(tr.model)
         _kl_train, _metrics = ops.kl_loss_train, ops.train_metrics
@@ -125,6 +131,7 @@ def main():
         fused_optim = hip_optim.enabled()
     qr_calls = []                # reforms per ops.query_reform_train call (none with the switch off)
     lt_calls = []                # ops.layer_tail_train calls (none without GNNRAG_HIP_LAYER_TAIL_TRAIN=1)
+    ud_calls = []                # ops.update_drop_train calls (none without GNNRAG_HIP_UPDATE_DROP_TRAIN=1)
     lm_calls = {"kl_loss_train": 0, "train_metrics": 0}     # none without GNNRAG_HIP_LOSS_METRICS=1
     sync =(lambda: torch.cuda.synchronize()) if args.use_cuda else (lambda: None)
     # the body of Trainer_KBQA.train_epoch (train_model.py:209-233), statement for statement, with clocks at its seams
@@ -174,6 +181,8 @@ def main():
            "reforms_per_query_reform_train_call": sorted(set(qr_calls)),
            "hip_layer_tail_train": None if a.pure else os.environ.get("GNNRAG_HIP_LAYER_TAIL_TRAIN", "default"),
            "layer_tail_train_calls_per_step": len(lt_calls) / float(a.warm + a.steps),
+           "hip_update_drop_train": None if a.pure else os.environ.get("GNNRAG_HIP_UPDATE_DROP_TRAIN", "default"),
+           "update_drop_train_calls_per_step": len(ud_calls) / float(a.warm + a.steps),
            "hip_loss_metrics": None if a.pure else os.environ.get("GNNRAG_HIP_LOSS_METRICS", "default"),
            "kl_loss_train_calls_per_step": lm_calls["kl_loss_train"] / float(a.warm + a.steps),
            "train_metrics_calls_per_step": lm_calls["train_metrics"] / float(a.warm + a.steps),
