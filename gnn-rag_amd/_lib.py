@@ -198,6 +198,10 @@ SIGNATURES = {
     "gnnrag_update_drop_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "gnnrag_update_drop_backward": (C.c_int, [_VP] * 4 + [C.c_float, _VP, C.c_int64, C.c_int32, C.c_int32] + [_VP] * 5 +
                                     [C.c_size_t, C.c_int32, _VP]),
+    # backward of the per-question relation tables (additive to ABI 16)
+    "gnnrag_relation_tables_backward_workspace_bytes": (C.c_size_t, [C.POINTER(CsrStruct), C.c_int32, C.c_int32]),
+    "gnnrag_relation_tables_backward": (C.c_int, [C.POINTER(CsrStruct)] + [_VP] * 9 + [C.c_int32] * 3 +
+                                        [_VP, C.c_size_t, _VP]),
     # training loss and batch metrics (additive to ABI 16)
     "gnnrag_kl_loss_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gnnrag_kl_loss_train": (C.c_int, [_VP] * 3 + [C.c_int32] * 2 + [_VP] * 3 + [C.c_size_t, _VP]),

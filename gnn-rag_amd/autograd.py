@@ -12,7 +12,8 @@ features on :class:`RelTextPoolFn` (``gnnrag_rel_text_pool`` / ``gnnrag_rel_text
 two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnrag_query_reform_backward``), the tail of the
 reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``), the concatenated update under
 dropout on :class:`UpdateDropFn` (``gnnrag_update_drop_train`` / ``gnnrag_update_drop_backward``), the KL loss behind
-the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``)."""
+the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``), the relation tables of
+the fused training form on :class:`RelationTablesFn` (``gnnrag_relation_tables`` / ``gnnrag_relation_tables_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -77,6 +78,33 @@ def relation_tables_dense(plan, T_fwd, T_inv, ins, W_e2e):
         Wd = torch.stack([W_e2e[:, (1 + 2 * i + d) * D:(2 + 2 * i + d) * D] for i in range(I)])    # [I, D_out, D]
         out.append(torch.einsum("mik,iok->mo", z, Wd))
     return torch.stack(out)
+
+
+class RelationTablesFn(torch.autograd.Function):
+    """P [2, rel_total, D] = the per-question relation tables of the fused form on ``gnnrag_relation_tables`` (the bits of
+    inference) / ``gnnrag_relation_tables_backward``: what :func:`relation_tables_dense` spells in torch ops, as ONE autograd
+    node.  Saves T_fwd, T_inv, ins and W_e2e only - relu(T * ins) [M, I, D] is formed inside the products of both directions
+    and never stored; an input that needs no gradient gets none computed."""
+
+    @staticmethod
+    def forward(ctx, plan, T_fwd, T_inv, ins, W_e2e):
+        T_fwd, T_inv = T_fwd.detach().float().contiguous(), T_inv.detach().float().contiguous()
+        ins, W_e2e = ins.detach().float().contiguous(), W_e2e.detach().float().contiguous()
+        ctx.plan = plan
+        ctx.save_for_backward(T_fwd, T_inv, ins, W_e2e)
+        return ops.relation_tables(plan, T_fwd, T_inv, ins, W_e2e)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_P):
+        T_fwd, T_inv, ins, W_e2e = ctx.saved_tensors
+        nig = ctx.needs_input_grad
+        if not any(nig[1:5]):
+            return (None,) * 5
+        # .contiguous() inside ops._chk also copies an expanded (stride-0) gradient, as P.sum().backward() delivers
+        g = ops.relation_tables_backward(ctx.plan, T_fwd, T_inv, ins, W_e2e, g_P.float(), need_T_fwd=nig[1],
+                                         need_T_inv=nig[2], need_ins=nig[3], need_W=nig[4])
+        return None, g["g_T_fwd"], g["g_T_inv"], g["g_ins"], g["g_W"]
 
 
 class TypeAggFn(torch.autograd.Function):

@@ -49,6 +49,14 @@ int frontier_args(const gnnrag_csr* csr, const float* dist, void* fws, size_t fw
 int gemm_tn_drop(const float* A, const float* B0, const float* B1, const uint8_t* keep, float scale, int64_t M, int32_t N1,
                  int32_t K0, int32_t N2, float* C, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+// gemm_tn.hip: the chunks' partial blocks part [chunks][N1][I D] of A^T . Z with Z[m, i D + k] = relu(T[r_m, k] *
+// ins[b_m, i, k]), (b_m, r_m) = rows[m], formed as B is loaded (gnnrag_relation_tables' generated operand); chunks =
+// gemm_tn_gen_chunks(M, N1, I D), gnnrag_gemm_tn's.  The caller adds the chunks in chunk order (rel_tables_bwd.hip) and has
+// checked N1 % 4 == D % 4 == 0 and 16-byte aligned float operands.
+int gemm_tn_gen_chunks(int64_t M, int32_t N1, int32_t N2);
+int gemm_tn_gen_partials(const float* A, const float* T, const float* ins, const int32_t* rows, int64_t M, int32_t N1,
+                         int32_t D, int32_t I, float* part, hipStream_t stream);
+
 // gnnrag_update_score_fused with the promise that `score` already holds zeros
 int update_score_fused_z(const float* h, const float* nbr, const float* W, const float* b, const float* w_s,
                          const float* b_s, const float* mask, float* h_out, float* score, int64_t BN, int32_t D,

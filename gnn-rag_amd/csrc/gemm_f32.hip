@@ -1441,6 +1441,28 @@ extern "C" int gnnrag_dense_form(int32_t entry, int64_t M, int32_t K, int32_t No
         f = dx ? gemm_form(g, EPI_KEEP, AMODE_PLAIN, math) : gemm_form(g, EPI_LINEAR, AMODE_DROP, math);
       }
     }
+  } else if (entry == GNNRAG_DENSE_ENTRY_REL_TABLES_DX || entry == GNNRAG_DENSE_ENTRY_REL_TABLES_DW) {
+    // (rel_total, D, I) in place of (M, K, Nout); stand-ins: A = g_P, W = the transposed copy in the workspace, C = the
+    // product's block in the workspace / g_W
+    const int32_t D = K, I = Nout;
+    memset(&f, 0, sizeof(f));
+    const bool ok = D % 4 == 0 && D <= 1024 && I <= GNNRAG_MAX_INS && aligned16(A, W, C);
+    if (entry == GNNRAG_DENSE_ENTRY_REL_TABLES_DW) {
+      if (block) return GNNRAG_E_BADARG;
+      if (ok) f.family = f.block_family = GNNRAG_DENSE_GEMM_TN;
+      f.v4 = ok;
+    } else if (ok) {
+      GemmArgs g = linear_args(A, M, D, W, nullptr, nullptr, 0, 0, C, D);
+      f = gemm_form(g, EPI_LINEAR, AMODE_PLAIN, math);
+      launches = f.block_family == GNNRAG_DENSE_SKINNY ? 1 : (D + 207) / 208;
+      if (block >= launches) return GNNRAG_E_BADARG;
+      if (block) {
+        g.n0 = 208 * block;
+        f = gemm_form(g, EPI_LINEAR, AMODE_PLAIN, math);
+      }
+    } else if (block) {
+      return GNNRAG_E_BADARG;
+    }
   } else {
     return GNNRAG_E_BADARG;
   }

@@ -12,6 +12,10 @@
 //
 // Masked form (gnnrag_update_drop_backward): B is the split operand [B0 | B1] under dropout, keep ? b * scale : +0 formed
 // on the loaded piece - the weight gradient of a product whose dropped operand was never stored.
+//
+// Generated form (gnnrag_relation_tables_backward): B[m, (i, k)] = relu(T[r_m, k] * ins[b_m, i, k]) over the compact rows
+// (b_m, r_m) of a structure - the operand gnnrag_relation_tables forms in its tile loader, formed here on the loaded pieces;
+// the chunks' partial blocks are left to the caller's own reduce.
 #include <type_traits>
 
 #include "gnnrag_common.h"
@@ -38,11 +42,21 @@ struct TnMaskArgs : TnArgs {
   float scale;
 };
 
-// Args = TnArgs: the plain product.  Args = TnMaskArgs: the masked B operand (the plain instantiation keeps its own
-// argument block, so its code does not move with the masked form's fields).
+// B[m, i * D + k] = relu(T[rows[m].y, k] * ins[rows[m].x, i, k]) (N2 = I * D, D % 4 == 0: a float4 piece lies in one
+// instruction); TnArgs::B is not read
+struct TnGenArgs : TnArgs {
+  const float* T;        // [R1, D]
+  const float* ins;      // [B, I, D]
+  const int2* rows;      // [M] (question, relation)
+  int32_t gD, gI;
+};
+
+// Args = TnArgs: the plain product.  Args = TnMaskArgs: the masked B operand.  Args = TnGenArgs: the generated B operand
+// (every instantiation keeps its own argument block, so its code does not move with another form's fields).
 template <typename Args>
 __global__ __launch_bounds__(256) void k_gemm_tn(Args g) {
   constexpr bool MASKB = std::is_same<Args, TnMaskArgs>::value;
+  constexpr bool GENB = std::is_same<Args, TnGenArgs>::value;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fg = lane >> 4;
   const int blk = blockIdx.x * 4 + wave;                      // this wave's 64 x 64 output block
@@ -58,6 +72,12 @@ __global__ __launch_bounds__(256) void k_gemm_tn(Args g) {
   for (int x = 0; x < 4; ++x)
 #pragma unroll
     for (int y = 0; y < 4; ++y) acc[x][y] = zero4;
+  size_t gen_t = 0, gen_q = 0;                                // GENB: this lane's piece inside a row of T / of a question's ins
+  if constexpr (GENB) {
+    const int i = cb / g.gD;
+    gen_t = (size_t)(cb - i * g.gD);
+    gen_q = (size_t)i * g.gD + gen_t;
+  }
   for (int64_t m0 = m_beg; m0 < m_end; m0 += 4 * kTnUnroll) {
     f32x4 av[kTnUnroll], bv[kTnUnroll];
     unsigned kb[kTnUnroll];
@@ -70,6 +90,11 @@ __global__ __launch_bounds__(256) void k_gemm_tn(Args g) {
         bv[u] = cb < g.K0 ? *reinterpret_cast<const f32x4*>(g.B + mc * g.K0 + cb)
                           : *reinterpret_cast<const f32x4*>(g.B1 + mc * (g.N2 - g.K0) + (cb - g.K0));
         kb[u] = g.keep ? *reinterpret_cast<const unsigned*>(g.keep + mc * g.N2 + cb) : 0x01010101u;
+      } else if constexpr (GENB) {
+        const int2 br = g.rows[mc];
+        const f32x4 tv = *reinterpret_cast<const f32x4*>(g.T + (size_t)br.y * g.gD + gen_t);
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(g.ins + (size_t)br.x * g.gI * g.gD + gen_q);
+        bv[u] = __builtin_elementwise_max(tv * qv, zero4);   // one fp32 multiply, then the relu: the forward's loader
       } else {
         bv[u] = *reinterpret_cast<const f32x4*>(g.B + mc * g.N2 + cb);
       }
@@ -160,6 +185,28 @@ static int tn_launch(const float* A, const float* B, const float* B1, const uint
 int gemm_tn_drop(const float* A, const float* B0, const float* B1, const uint8_t* keep, float scale, int64_t M, int32_t N1,
                  int32_t K0, int32_t N2, float* C, void* workspace, size_t workspace_bytes, hipStream_t stream) {
   return tn_launch(A, B0, B1, keep, keep ? scale : 1.f, true, M, N1, K0, N2, C, workspace, workspace_bytes, stream);
+}
+
+int gemm_tn_gen_chunks(int64_t M, int32_t N1, int32_t N2) {
+  int rows = 0;
+  return tn_chunks(M, N1, N2, &rows);
+}
+
+// the caller has checked the shapes and the alignment (gnnrag_relation_tables_backward); M > 0
+int gemm_tn_gen_partials(const float* A, const float* T, const float* ins, const int32_t* rows, int64_t M, int32_t N1,
+                         int32_t D, int32_t I, float* part, hipStream_t stream) {
+  TnGenArgs g;
+  memset(&g, 0, sizeof(g));
+  int chunk_rows = 0;
+  const int32_t N2 = I * D;
+  const int chunks = tn_chunks(M, N1, N2, &chunk_rows);
+  g.A = A; g.part = part; g.M = M; g.N1 = N1; g.N2 = N2;
+  g.nb1 = (N1 + 63) / 64; g.nb2 = (N2 + 63) / 64; g.chunk_rows = chunk_rows;
+  g.T = T; g.ins = ins; g.rows = (const int2*)rows; g.gD = D; g.gI = I;
+  const dim3 grid((unsigned)((g.nb1 * g.nb2 + 3) / 4), (unsigned)chunks);
+  hipLaunchKernelGGL(k_gemm_tn<TnGenArgs>, grid, dim3(256), 0, stream, g);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
 }
 
 }  // namespace gnnrag

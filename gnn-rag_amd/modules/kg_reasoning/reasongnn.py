@@ -21,7 +21,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ... import ops
-from ...autograd import (AggregateFn, FusedAggregateFn, LayerTailFn, UpdateDropFn, linear as ag_linear,
+from ...autograd import (AggregateFn, FusedAggregateFn, LayerTailFn, RelationTablesFn, UpdateDropFn, linear as ag_linear,
                          relation_tables_dense)
 from .base_gnn import BaseGNNLayer
 
@@ -272,7 +272,9 @@ class ReasonGNNLayer(BaseGNNLayer):
         # (the fused walk's backward gathers whole rows: D <= 1024; beyond that the unfused form below keeps its LDS-sum backward)
         if native and self.train_fused and not drop_active and self.plan.rel_total > 0 and D <= 1024:
             W = e2e_linear.weight
-            P = relation_tables_dense(self.plan, T_fwd, T_inv, relational_ins.float(), W)
+            P = self._relation_tables(T_fwd, T_inv, relational_ins.float(), W)
+            if P is None:
+                P = relation_tables_dense(self.plan, T_fwd, T_inv, relational_ins.float(), W)
             nbr = FusedAggregateFn.apply(self.plan, current_dist.float(), P)
             pre_self = ag_linear(self.local_entity_emb.float().reshape(B * N, D), W[:, :D], e2e_linear.bias)
             got = self._layer_tail(pre_self, nbr, return_score)
@@ -316,6 +318,21 @@ class ReasonGNNLayer(BaseGNNLayer):
         score = self.score_func(self.linear_drop(self.local_entity_emb)).squeeze(dim=2) + (1 - mask) * VERY_NEG_NUMBER
         new_dist = self.softmax_d1(score)
         return (score, new_dist) if return_score else (new_dist, self.local_entity_emb)
+
+    def _relation_tables(self, T_fwd, T_inv, ins, W):
+        """The per-question relation tables of the fused training form as ONE autograd node on the library
+        (``autograd.RelationTablesFn``: the forward is inference's ``gnnrag_relation_tables``, the backward
+        ``gnnrag_relation_tables_backward``; relu(T * ins) is never stored) when ``GNNRAG_HIP_REL_TABLES_TRAIN=1`` (read at
+        every call, default off) and the call is eligible; None otherwise - the caller then runs the torch expression
+        ``relation_tables_dense``, exactly as without the switch."""
+        if os.environ.get("GNNRAG_HIP_REL_TABLES_TRAIN", "0") != "1":
+            return None
+        if self.plan.rel_total <= 0 or ins.dim() != 3 or not ops.relation_tables_backward_supported(ins.shape[2], ins.shape[1]):
+            return None
+        for t in (T_fwd, T_inv, ins, W):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                return None
+        return RelationTablesFn.apply(self.plan, T_fwd, T_inv, ins, W)
 
     def _draw_update_keep(self, rows, cols, p, device):
         """Keep flags [rows, cols] (uint8 0/1, kept with probability 1 - p) of the dropout in front of ``e2e_linear``, in the

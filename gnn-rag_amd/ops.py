@@ -553,6 +553,50 @@ def relation_tables(plan: CsrPlan, T_fwd: torch.Tensor, T_inv: torch.Tensor, ins
     return P
 
 
+def relation_tables_backward_supported(D: int, I: int) -> bool:
+    """Whether ``gnnrag_relation_tables_backward`` takes the hidden size and instruction count (float4 loaders and one
+    float4 column per thread of its reductions; torch's allocations satisfy the alignment rules)."""
+    return 0 < D <= 1024 and D % 4 == 0 and 0 < I <= 8
+
+
+def relation_tables_backward(plan: CsrPlan, T_fwd: torch.Tensor, T_inv: torch.Tensor, ins: torch.Tensor,
+                             W_e2e: torch.Tensor, g_P: torch.Tensor, math: Optional[int] = None, need_T_fwd: bool = True,
+                             need_T_inv: bool = True, need_ins: bool = True, need_W: bool = True) -> dict:
+    """Backward of :func:`relation_tables` (``gnnrag_relation_tables_backward``) from g_P [2,rel_total,D]; the other
+    operands as the forward was given them.  Returns a dict: ``g_T_fwd`` / ``g_T_inv`` [R1,D] (a relation no question
+    uses: +0), ``g_ins`` [B,I,D] (a question without facts: +0), ``g_W`` [D,(2I+1)D] (the self block, columns < D: +0);
+    None where not wanted (its launches are then not made; all four unwanted is refused by the library).  relu(T * ins)
+    is never stored, the gate is the product > 0.  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    ins = _chk(ins, "ins")
+    if ins.dim() != 3 or ins.shape[0] != plan.B:
+        raise ValueError("ins is %s, the plan has %d questions" % (tuple(ins.shape), plan.B))
+    B, I, D = ins.shape
+    _on_plan_device(plan, ins, "ins")
+    K = (2 * I + 1) * D
+    T_fwd = _chk(T_fwd, "T_fwd", shape=(plan.R1, D))
+    T_inv = _chk(T_inv, "T_inv", shape=(plan.R1, D))
+    W_e2e = _chk(W_e2e, "e2e_linear.weight", shape=(D, K))
+    g_P = _chk(g_P, "g_P", shape=(2, plan.rel_total, D))
+    dev, role = ins.device, "relation_tables_backward: "
+    out = {"g_T_fwd": _buf((plan.R1, D), torch.float32, dev, role + "g_T_fwd") if need_T_fwd else None,
+           "g_T_inv": _buf((plan.R1, D), torch.float32, dev, role + "g_T_inv") if need_T_inv else None,
+           "g_ins": _buf((B, I, D), torch.float32, dev, role + "g_ins") if need_ins else None,
+           "g_W": _buf((D, K), torch.float32, dev, role + "g_W") if need_W else None}
+    if plan.rel_total == 0:                 # real pointers also where nothing is read (as for aggregate_fused)
+        g_P = _buf((2, 1, D), torch.float32, dev, role + "g_P (empty batch)", fill=0)
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn's chunks inside): query it on ins' device
+        ws = _buf(max(lib.gnnrag_relation_tables_backward_workspace_bytes(C.byref(plan.c), D, I), 16), torch.uint8, dev,
+                  role + "workspace")
+        _lib.check(lib.gnnrag_relation_tables_backward(C.byref(plan.c), T_fwd.data_ptr(), T_inv.data_ptr(), ins.data_ptr(),
+                                                       W_e2e.data_ptr(), g_P.data_ptr(), _ptr(out["g_T_fwd"]),
+                                                       _ptr(out["g_T_inv"]), _ptr(out["g_ins"]), _ptr(out["g_W"]), D, I,
+                                                       _math(math), ws.data_ptr(), ws.numel(), _stream()),
+                   "gnnrag_relation_tables_backward")
+    return out
+
+
 WALK_L2_GATHER, WALK_LDS_16, WALK_LDS_32 = 0, 1, 2
 WALK_KERNEL_NAMES = {WALK_L2_GATHER: "k_walk_light_q / k_walk_light<FUSED> + hub kernels (table rows gathered from L2)",
                      WALK_LDS_16: "k_fact_prior_merged + k_walk_slice<FUSED,1> (16-column table slices in LDS, merged rows)",
@@ -569,7 +613,10 @@ def aggregate_fused_variant(plan: CsrPlan, D: int) -> int:
 
 DENSE_ENTRIES = {"linear": 0, "linear_pair": 1, "update_score": 2, "update_score_fused": 3,
                  # gnnrag_update_drop_train, and the masked input / weight gradient products of its backward
-                 "update_drop": 4, "update_drop_dx": 5, "update_drop_dw": 6}
+                 "update_drop": 4, "update_drop_dx": 5, "update_drop_dw": 6,
+                 # gnnrag_relation_tables_backward, (rel_total, D, I) as (M, K, Nout): one of its 2 I equal products in
+                 # front of the gate, and the weight gradient with the generated operand
+                 "rel_tables_dx": 7, "rel_tables_dw": 8}
 DENSE_MISALIGNED_A, DENSE_MISALIGNED_W, DENSE_MISALIGNED_C, DENSE_MISALIGNED_ADD, DENSE_MISALIGNED_A1 = 1, 2, 4, 8, 16
 (DENSE_NONE, DENSE_SKINNY, DENSE_KTILED, DENSE_WRES, DENSE_UPDATE_SKINNY, DENSE_UPDATE_B3,
  DENSE_WIDE, DENSE_GEMM_TN) = range(8)

@@ -296,7 +296,8 @@ int gnnrag_aggregate_backward(const gnnrag_csr* csr, const gnnrag_relorder* relo
  *   g_dist[s]        = sum_d sum_{f: src_d(f)=s} w_f * < g_nbr[dst_d(f), :], P[d, row(b, rel_f), :] >
  *   g_P[d, row, :]   = sum_{f in row} w_f * dist[src_d(f)] * g_nbr[dst_d(f), :]
  * both fully written; the relation tables P themselves are a differentiable dense expression of a few ten thousand
- * rows on the caller's side (gnn-rag_amd/autograd.py: relation_tables_dense).  P and g_P must be real pointers also for
+ * rows on the caller's side (gnn-rag_amd/autograd.py: relation_tables_dense) or gnnrag_relation_tables with its own
+ * backward, gnnrag_relation_tables_backward.  P and g_P must be real pointers also for
  * a batch without facts (rel_total == 0: nothing is read or written there; NULL is GNNRAG_E_BADARG, as for
  * gnnrag_aggregate_fused).  Needs the (question, relation) ordering
  * (gnnrag_relorder) and D % 4 == 0; gather kernels, chunk partials summed in a fixed order, no atomics.
@@ -363,6 +364,12 @@ int gnnrag_update_score_fused(const float* h, const float* nbr, const float* W_e
 #define GNNRAG_DENSE_ENTRY_UPDATE_DROP    4
 #define GNNRAG_DENSE_ENTRY_UPDATE_DROP_DX 5
 #define GNNRAG_DENSE_ENTRY_UPDATE_DROP_DW 6
+/* gnnrag_relation_tables_backward, (rel_total, D, I) as (M, K, Nout); has_add / add_rows are ignored.  _DX: ONE of the 2 I
+ * equal gnnrag_linear products [rel_total, D] x [D, D] in front of G (blocks 0 .. ceil(D / 208) - 1 above the skinny bound).
+ * _DW: the weight gradient with the generated B operand (GNNRAG_DENSE_GEMM_TN).  Outside the entry's limits:
+ * GNNRAG_DENSE_NONE. */
+#define GNNRAG_DENSE_ENTRY_REL_TABLES_DX  7
+#define GNNRAG_DENSE_ENTRY_REL_TABLES_DW  8
 #define GNNRAG_DENSE_MISALIGNED_A   1       /* A / A0 / h                                                              */
 #define GNNRAG_DENSE_MISALIGNED_W   2
 #define GNNRAG_DENSE_MISALIGNED_C   4       /* C / C0 / h_out                                                          */
@@ -375,7 +382,8 @@ int gnnrag_update_score_fused(const float* h, const float* nbr, const float* W_e
 #define GNNRAG_DENSE_UPDATE_SKINNY 4        /* k_update_skinny                                                         */
 #define GNNRAG_DENSE_UPDATE_B3     5        /* k_update_b3 (tables_b3.hip)                                             */
 #define GNNRAG_DENSE_WIDE          6        /* D > 208: EPI_LINEAR column blocks, then k_score_rows                    */
-#define GNNRAG_DENSE_GEMM_TN       7        /* k_gemm_tn with the masked split B operand, then k_tn_reduce             */
+#define GNNRAG_DENSE_GEMM_TN       7        /* k_gemm_tn with the masked split B operand, then k_tn_reduce (REL_TABLES_DW:
+                                               the generated B operand, then k_rtb_w_reduce)                           */
 typedef struct gnnrag_dense_form_t {
   int32_t family;        /* GNNRAG_DENSE_*                                                                               */
   int32_t block_family;  /* family of the described GEMM launch: = family, except WIDE (SKINNY or KTILED)                */
@@ -689,6 +697,34 @@ size_t gnnrag_update_drop_backward_workspace_bytes(int64_t BN, int32_t D, int32_
 int gnnrag_update_drop_backward(const float* g_pre, const float* h, const float* agg, const uint8_t* keep, float scale,
                                 const float* W, int64_t BN, int32_t D, int32_t I, float* g_h, float* g_agg, float* dW,
                                 float* db, void* workspace, size_t workspace_bytes, int32_t math, gnnrag_stream_t stream);
+
+/* ---- Backward of gnnrag_relation_tables, for training on the fused form (additive to ABI 16; rel_tables_bwd.hip) ----------
+ * M = rel_total, (b_m, r_m) = csr->rel_rows[m], blk(i,d) = (1 + 2 i + d) D, a[d,m,i,k] = T_d[r_m,k] * ins[b_m,i,k] (one fp32
+ * multiply, as the forward's loader forms it), z = relu(a).  From g_P [2, rel_total, D]:
+ *   G[d,m,i,k]         = ( sum_o g_P[d,m,o] W_e2e[o, blk(i,d)+k] ) * [a[d,m,i,k] > 0]
+ *   g_W[o, blk(i,d)+k] = sum_m g_P[d,m,o] z[d,m,i,k]                 [D, (2I+1) D], columns 0 .. D-1 exactly +0
+ *   g_T_d[r,k]         = sum_{m: r_m = r} sum_i G[d,m,i,k] ins[b_m,i,k]     [R1, D]; a relation no question uses: +0
+ *   g_ins[b,i,k]       = sum_d sum_{m: b_m = b} G[d,m,i,k] T_d[r_m,k]       [B, I, D]; a question without facts: +0
+ * The gate is a > 0 (torch's relu rule: a product that is 0, -0 or negative passes nothing).  z is never stored: the weight
+ * gradient forms it on the loaded pieces of k_gemm_tn's B operand (gnnrag_gemm_tn's chunks, added in chunk order).  The
+ * ungated product in front of G is 2 I gnnrag_linear calls (`math` selects their form; gnnrag_dense_form:
+ * GNNRAG_DENSE_ENTRY_REL_TABLES_DX) against one transposed copy of W_e2e, kept in the workspace [2, I, M, D]; its two
+ * readers apply the gate.  g_ins is a segmented column sum over a question's contiguous rows, g_T one workgroup per
+ * (relation, direction) over the questions in ascending order; every reduction is fp32.  No atomics, no allocation, nothing
+ * waits for the stream; each output element has one writer and one summation order that depends on the structure and
+ * (D, I, math) only: a second call gives the same bits.  Every wanted output is fully written.
+ * Any output NULL: not wanted, and its launches are not made; all four NULL is GNNRAG_E_BADARG, as are a NULL csr or input.
+ * Then D % 4 == 0, D <= 1024, I <= GNNRAG_MAX_INS and 16-byte aligned operands, else GNNRAG_E_UNSUPPORTED; then a short
+ * workspace is GNNRAG_E_WORKSPACE.  All are answered before anything is launched.  rel_total == 0: every wanted output is
+ * zero-filled, nothing else is touched and no workspace is needed (pointers must still be real).
+ * workspace: gnnrag_relation_tables_backward_workspace_bytes(csr, D, I) bytes, 16-byte aligned (0 for a shape outside the
+ * limits or a structure without facts; like gnnrag_gemm_tn_workspace_bytes it depends on the current device). */
+size_t gnnrag_relation_tables_backward_workspace_bytes(const gnnrag_csr* csr, int32_t D, int32_t I);
+int gnnrag_relation_tables_backward(const gnnrag_csr* csr,
+                                    const float* T_fwd, const float* T_inv, const float* ins, const float* W_e2e,
+                                    const float* g_P, float* g_T_fwd, float* g_T_inv, float* g_ins, float* g_W,
+                                    int32_t D, int32_t I, int32_t math,
+                                    void* workspace, size_t workspace_bytes, gnnrag_stream_t stream);
 
 /* ---- Training loss and batch metrics (additive to ABI 16; train_tail.hip) -------------------------------------------------
  * What follows the last dist of a training forward (gnn/models/ReaRev/rearev.py:227-243, gnn/models/NSM/nsm.py:242-250).

@@ -183,6 +183,7 @@ def main():
            "layer_tail_train_calls_per_step": len(lt_calls) / float(a.warm + a.steps),
            "hip_update_drop_train": None if a.pure else os.environ.get("GNNRAG_HIP_UPDATE_DROP_TRAIN", "default"),
            "update_drop_train_calls_per_step": len(ud_calls) / float(a.warm + a.steps),
+           "hip_rel_tables_train": None if a.pure else os.environ.get("GNNRAG_HIP_REL_TABLES_TRAIN", "default"),
            "hip_loss_metrics": None if a.pure else os.environ.get("GNNRAG_HIP_LOSS_METRICS", "default"),
            "kl_loss_train_calls_per_step": lm_calls["kl_loss_train"] / float(a.warm + a.steps),
            "train_metrics_calls_per_step": lm_calls["train_metrics"] / float(a.warm + a.steps),
