@@ -1114,55 +1114,105 @@ constexpr int kSliceTeamDeg = 4096;
 constexpr int kSliceBigCap = 72;    // big nodes of one question kept in LDS; a question with more is walked
                                     // entirely by lane groups (slow, correct)
 
+// Global addresses of the LDS walk: UNIFORM BASE + LANE BYTE OFFSET + IMMEDIATE, through g_ld / g_st only.  A32 (the
+// launcher admits the shape: every array of the call stays below 2^32 bytes): the offset is an unsigned 32-bit lane
+// value, an access is SGPR base + VGPR offset + immediate with no 64-bit lane arithmetic in front of it (the form
+// update_b3_part and k_tables_vq use, tables_b3.hip); else the same text with 64-bit offsets.
+template <bool A32> struct WalkOff { typedef unsigned type; };
+template <> struct WalkOff<false> { typedef size_t type; };
+template <typename T, typename O>
+__device__ __forceinline__ T g_ld(const void* base, O off, int imm = 0) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(base) + off + imm);
+}
+template <typename T, typename O>
+__device__ __forceinline__ void g_st(void* base, O off, int imm, T v) {
+  *reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(base) + off + imm) = v;
+}
+template <typename O>
+__device__ __forceinline__ O off_min(O a, O b) { return a < b ? a : b; }
+// One (p, rel) pair, or (0, zr) where the slot holds no fact.  The record is read and selected as ONE 64-bit value: read
+// as an int2, the compiler moves the load of .y behind the branch of the step that consumes it (a dependent round trip
+// with a 64-bit address of its own).
+template <typename O>
+__device__ __forceinline__ int2 ld_pair(const void* base, O off, int imm, bool has, int zr) {
+  unsigned long long v = g_ld<unsigned long long>(base, off, imm);
+  v = has ? v : (unsigned long long)(unsigned)zr << 32;
+  return make_int2((int)(unsigned)v, (int)(unsigned)(v >> 32));
+}
+
+// What the walk reads the prior pairs of one stream with.  Loads are UNCONDITIONAL: a slot's byte offset is clamped so
+// that offset + immediate stays inside the stream's workspace region (hi[h] = max(last - 32 h, 0) for the immediates
+// 32 h; the region holds at least 256 bytes, prior_bytes), and a slot that holds no fact is then given (0, zr) by a select.
+// A slot that holds a fact is never clamped: its record lies inside the stream.
+template <typename O> struct PairStream {
+  const void* base[2];  // direction d's pairs (merged rows: [0] is the one stream)
+  O hi[4];
+  O last;               // byte offset of the stream's last record
+};
+
 // one node's rows in both directions + its first 8 (p, rel) pairs per direction
-struct SetRows {
-  int beg[2], len[2];
+template <typename O> struct SetRows {
+  int rp[2][2];       // row_ptr[d][n], row_ptr[d][n + 1] as requested by set_load_rows; not touched before set_load_first
+  int len[2];
+  O ob[2];            // byte offset of the lane's own first pair, (beg + sub) * 8
   int2 first[2][2];
   int2 second[2];     // merged rows: the pairs 8..15 of the node's run, requested with the first ones (a set ahead)
-  int n;
   bool valid, big;
 };
 
-// MG (compile time): merged rows - direction 1's members are constants, the compiler drops them
-template <bool MG>
-__device__ __forceinline__ void set_load_rows(SetRows& s, const WalkArgs& a, int g, int set, int nsets, int grp) {
-  const int nl = set * 16 + grp;
-  s.valid = set < nsets && nl < a.N;
-  s.n = g * a.N + (s.valid ? nl : 0);
-  s.big = false;
+// The row pointers of a set's node, four loads back to back and nothing that waits for them: beg, len and big are formed
+// by set_load_first one set later.  A lane without a node (past N, or no set left) reads the question's first node.
+template <typename O>
+__device__ __forceinline__ void set_load_rows(SetRows<O>& s, const WalkArgs& a, int g, int set, int nsets, int grp) {
+  const int lim = set < nsets ? a.N - set * 16 : 0;                       // (uniform)
+  s.valid = grp < lim;
+  const O q4 = (O)(unsigned)(g * a.N) * 4u;
+  const O ro = s.valid ? q4 + (O)(unsigned)(set * 16) * 4u + (O)(unsigned)(grp * 4) : q4;
 #pragma unroll
   for (int d = 0; d < 2; ++d) {
-    s.beg[d] = 0;
-    s.len[d] = 0;
-    if (s.valid) {
-      s.beg[d] = a.row_ptr[d][s.n];
-      s.len[d] = a.skip_dir == d + 1 ? 0 : a.row_ptr[d][s.n + 1] - s.beg[d];
-      s.big |= s.len[d] > a.big_deg;
-    }
-  }
-  if (MG) {                 // both directions as one run: [rp0[n] + rp1[n], rp0[n+1] + rp1[n+1])
-    s.beg[0] += s.beg[1];
-    s.len[0] += s.len[1];
-    s.beg[1] = 0;
-    s.len[1] = 0;
+    s.rp[d][0] = g_ld<int>(a.row_ptr[d], ro);
+    s.rp[d][1] = g_ld<int>(a.row_ptr[d], ro, 4);
   }
 }
 
-template <bool MG>
-__device__ __forceinline__ void set_load_first(SetRows& s, const int2* const (&prd)[2], int sub, int zr) {
+// MG (compile time): merged rows - direction 1's members are constants, the compiler drops them.
+// keep[d]: 0 for the direction the launch leaves out (skip_dir), else -1 (uniform).  listed: the question has a
+// big-node list; without one no node is big and the lane groups walk every row.
+template <bool MG, typename O>
+__device__ __forceinline__ void set_load_first(SetRows<O>& s, const PairStream<O>& ps, const int (&keep)[2], int big_deg,
+                                               bool listed, int sub, int zr) {
+  int beg[2];
 #pragma unroll
-  for (int d = 0; d < (MG ? 1 : 2); ++d)
+  for (int d = 0; d < 2; ++d) {
+    beg[d] = s.rp[d][0];
+    s.len[d] = (s.rp[d][1] - beg[d]) & keep[d];
+  }
+  s.big = listed && (s.len[0] > big_deg || s.len[1] > big_deg);
+  if (MG) {                 // both directions as one run: [rp0[n] + rp1[n], rp0[n+1] + rp1[n+1])
+    beg[0] += beg[1];
+    s.len[0] += s.len[1];
+    beg[1] = 0;
+    s.len[1] = 0;
+  }
+  const bool ok = s.valid && !s.big;
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
-      s.first[d][h] = (s.valid && !s.big && 4 * h + sub < s.len[d])
-                          ? prd[d][s.beg[d] + 4 * h + sub]
-                          : make_int2(0, zr);          // no fact: prior 0, the table's zero row
+  for (int d = 0; d < (MG ? 1 : 2); ++d) {
+    s.ob[d] = (O)(unsigned)(beg[d] + sub) * 8u;
+    const int have = (ok ? s.len[d] : 0) - sub;        // slot 4 h of the lane holds a fact iff 4 h < have
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      s.first[d][h] = ld_pair(ps.base[d], off_min(s.ob[d], ps.hi[h]), 32 * h, 4 * h < have, zr);   // no fact: prior 0, the zero row
+    }
+    if (MG) {
+      // a merged run holds ~12 records on average: nearly every 16-node set has a node with more than 8, and the second
+      // step's pairs, requested only when the first step starts, arrived after ~60 instructions of cover - a stall per set
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        s.second[h] = ld_pair(ps.base[0], off_min(s.ob[0], ps.hi[2 + h]), 64 + 32 * h, 8 + 4 * h < have, zr);
+    }
+  }
   if (MG) {
-    // a merged run holds ~12 records on average: nearly every 16-node set has a node with more than 8, and the second
-    // step's pairs, requested only when the first step starts, arrived after ~60 instructions of cover - a stall per set
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-      s.second[h] = (s.valid && !s.big && 8 + 4 * h + sub < s.len[0]) ? prd[0][s.beg[0] + 8 + 4 * h + sub] : make_int2(0, zr);
+    s.ob[1] = 0;
 #pragma unroll
     for (int h = 0; h < 2; ++h) s.first[1][h] = make_int2(0, zr);
   }
@@ -1216,17 +1266,19 @@ __device__ __forceinline__ void slice_fma4(SliceAcc<NI>& acc, int2 pairs, const 
 
 // one row (merged: both directions; else one direction of it), walked by a whole wave: 64 facts per step (lane group k
 // owns facts 4k..4k+3 of a step), steps first, first+stride, ...; up to 8 (wide slices: 4) steps requested before consuming
-template <int NI>
-__device__ __forceinline__ void slice_walk_wave(SliceAcc<NI>& acc, const int2* __restrict__ prd, int beg, int len,
+// (loads unconditional, offsets clamped to the stream's last record: see PairStream)
+template <int NI, typename O>
+__device__ __forceinline__ void slice_walk_wave(SliceAcc<NI>& acc, const void* __restrict__ prd, O last, int beg, int len,
                                                 int first, int stride, int lane, const float* __restrict__ Td, int zr) {
   const int nsteps = (len + 63) >> 6;
   constexpr int INF = NI > 1 ? 4 : 8;   // steps in flight (register budget)
+  const O ob = (O)(unsigned)(beg + lane) * 8u;
   for (int st = first; st < nsteps; st += stride * INF) {
     int2 pairs[INF];
 #pragma unroll
     for (int u = 0; u < INF; ++u) {
-      const int off = (st + stride * u) * 64 + lane;
-      pairs[u] = (off < len) ? prd[beg + off] : make_int2(0, zr);
+      const int step = st + stride * u;
+      pairs[u] = ld_pair(prd, off_min(ob + (O)(unsigned)step * 512u, last), 0, step * 64 + lane < len, zr);
     }
 #pragma unroll
     for (int u = 0; u < INF; ++u) slice_fma4<NI>(acc, pairs[u], Td);
@@ -1244,17 +1296,19 @@ __device__ __forceinline__ void slice_wave_reduce(SliceAcc<NI>& acc) {
     }
 }
 
-// where the float4 of node n at column col goes
-__device__ __forceinline__ float* slice_out(const WalkArgs& a, int n, int col) {
-  return a.out + (size_t)n * a.D + col;
+// where the float4 of node n at byte colB of its row goes: byte offset into out[]
+template <typename O>
+__device__ __forceinline__ O slice_out(int n, O rowB, O colB) {
+  return (O)(unsigned)n * rowB + colB;
 }
 
 // Two 1024-thread workgroups per CU need 8 waves per SIMD, i.e. <= 64 VGPRs: the accumulators (one or two float4
 // per lane) allow it.
-template <int NI, bool MG>
+template <int NI, bool MG, bool A32>
 __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(const WalkArgs a, const int2* __restrict__ pr,
                                                                                 int64_t F, int nslice, int nfull, int pl) {
   typedef SliceAcc<NI> Acc;
+  typedef typename WalkOff<A32>::type O;
   constexpr int NA = Acc::n;
   extern __shared__ __attribute__((aligned(16))) float s_mem[];
   float* Ts = s_mem;                                   // [2][Rg + 1][16] (room for [2][R1 + 1][16]); row Rg is zero
@@ -1291,15 +1345,16 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
   // the question's big nodes (listed at plan time) with their row bounds -> LDS
   const int nbig = a.big_cnt[g];
   const int nlist = nbig <= kSliceBigCap ? nbig : 0;   // 0: lane groups walk everything
+  const int keep[2] = {a.skip_dir == 1 ? 0 : -1, a.skip_dir == 2 ? 0 : -1};   // 0: the direction this launch leaves out
   if (tid < nlist) {
-    const int n = a.big_nodes[(size_t)g * N + tid];
+    const int n = g_ld<int>(a.big_nodes, (O)(unsigned)(g * N + tid) * 4u);
     int* e = blist + 5 * tid;
     e[0] = n;
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
-      const int beg = a.row_ptr[d][n];
+      const int beg = g_ld<int>(a.row_ptr[d], (O)(unsigned)n * 4u);
       e[1 + 2 * d] = beg;
-      e[2 + 2 * d] = a.skip_dir == d + 1 ? 0 : a.row_ptr[d][n + 1] - beg;
+      e[2 + 2 * d] = (g_ld<int>(a.row_ptr[d], (O)(unsigned)n * 4u, 4) - beg) & keep[d];
     }
     if (a.merged) {
       e[1] += e[3];
@@ -1315,6 +1370,9 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
   {
     constexpr int UN = 5;
     const int total = 2 * Rg * GR;
+    // both directions' rows as offsets from T[0] (a lane's direction differs inside a trip): T[1] lies dT bytes behind it
+    const O dT = (O)(reinterpret_cast<const unsigned char*>(a.T[1]) - reinterpret_cast<const unsigned char*>(a.T[0]));
+    const O trowB = (O)(unsigned)D * 4u;
     for (int base = 0; base < total; base += kSliceThreads * UN) {
       f32x4 v[UN];
       int dst[UN];
@@ -1328,8 +1386,8 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
         const bool live = idx < total && a.skip_dir != d + 1;      // (a direction that is not walked is never read)
         dst[u] = live ? (int)(((size_t)d * (Rg + 1) + r) * SW + 4 * k) : -1;
         v[u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* tab = a.T[d] + (size_t)roff * D;
-        if (live && col0 + 4 * k < D) v[u] = *reinterpret_cast<const f32x4*>(tab + (size_t)r * D + col0 + 4 * k);
+        const O to = (d ? dT : (O)0) + (O)(unsigned)(roff + r) * trowB + (O)(unsigned)(col0 + 4 * k) * 4u;
+        if (live && col0 + 4 * k < D) v[u] = g_ld<f32x4>(a.T[0], to);
       }
 #pragma unroll
       for (int u = 0; u < UN; ++u)
@@ -1348,7 +1406,21 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
   bool col_ok[NA];                                     // accumulator i covers columns col0 + 16 i + 4*sub .. +3
 #pragma unroll
   for (int i = 0; i < NA; ++i) col_ok[i] = col0 + kSliceW * i + 4 * sub < D;
-  const int2* const prd[2] = {pr, pr + F};
+  // the pair streams: merged rows one stream of 2 F records, else one of F records per direction
+  PairStream<O> ps;
+  ps.base[0] = pr;
+  ps.base[1] = MG ? pr : pr + F;
+  {
+    const int64_t nrec = MG ? 2 * F : F;
+    ps.last = (O)(nrec > 0 ? nrec - 1 : 0) * 8u;
+#pragma unroll
+    for (int h = 0; h < 4; ++h) ps.hi[h] = ps.last > (O)(32 * h) ? ps.last - (O)(32 * h) : (O)0;
+  }
+  // out[]: a row is rowB bytes; the lane's float4 of accumulator i lies colB + 64 i bytes into it.  A light set's nodes are
+  // consecutive: node 16 set + grp of question g is laneB behind the (uniform) offset of the set's first node
+  const O rowB = (O)(unsigned)D * 4u;
+  const O colB = (O)(unsigned)(col0 + 4 * sub) * 4u;
+  const O laneB = (O)(unsigned)grp * rowB + colB;
   const float* Td[2] = {Ts + 4 * sub, Ts + (size_t)(Rg + 1) * SW + 4 * sub};
 
   // ---- huge nodes first: the whole workgroup per node; wave w takes steps w, w+16, ...; wave sums
@@ -1362,7 +1434,7 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
       acc.zero();
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
-        slice_walk_wave<NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], wave, kSliceWaves, lane, Td[d], Rg);
+        slice_walk_wave<NI, O>(acc, ps.base[d], ps.last, e[1 + 2 * d], e[2 + 2 * d], wave, kSliceWaves, lane, Td[d], Rg);
         if (d == 1) {     // (inside the unrolled loop: behind it, the wide kernels' prologue is scheduled differently)
           slice_wave_reduce<NI>(acc);
           if (grp == 0) {
@@ -1376,7 +1448,7 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
 #pragma unroll
             for (int w = 0; w < kSliceWaves; ++w) t += *reinterpret_cast<const f32x4*>(red + (w * NA + i) * 16 + 4 * sb);
             const int cc = col0 + kSliceW * i + 4 * sb;
-            if (cc < D) *reinterpret_cast<f32x4*>(slice_out(a, e[0], cc)) = t;
+            if (cc < D) g_st<f32x4, O>(a.out, slice_out<O>(e[0], rowB, (O)(unsigned)cc * 4u), 0, t);
           }
           __syncthreads();
           acc.zero();
@@ -1403,30 +1475,29 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
       Acc acc;
       acc.zero();
 #pragma unroll
-      for (int d = 0; d < 2; ++d) slice_walk_wave<NI>(acc, prd[d], e[1 + 2 * d], e[2 + 2 * d], 0, 1, lane, Td[d], Rg);
+      for (int d = 0; d < 2; ++d)
+        slice_walk_wave<NI, O>(acc, ps.base[d], ps.last, e[1 + 2 * d], e[2 + 2 * d], 0, 1, lane, Td[d], Rg);
       slice_wave_reduce<NI>(acc);
       if (grp == 0) {
+        const O oo = slice_out<O>(e[0], rowB, colB);
 #pragma unroll
         for (int i = 0; i < NA; ++i)
-          if (col_ok[i]) *reinterpret_cast<f32x4*>(slice_out(a, e[0], col0 + kSliceW * i + 4 * sub)) = acc.v[i];
+          if (col_ok[i]) g_st<f32x4, O>(a.out, oo, 4 * kSliceW * i, acc.v[i]);
       }
     }
   };
   // the walk of one light set
-  auto walk_set = [&](SetRows& c) __attribute__((always_inline)) {
-    if (c.valid && c.big && nlist == 0) {     // no list for this question: the owner group walks it
-      c.big = false;
-      set_load_first<MG>(c, prd, sub, Rg);
-    }
+  auto walk_set = [&](SetRows<O>& c, int set) __attribute__((always_inline)) {
     if (c.valid && !c.big) {
       Acc acc;
       acc.zero();
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
         if (MG && d == 1) continue;             // merged rows: one run per node
-        const int beg = c.beg[d], len = c.len[d];
+        const int len = c.len[d];
         int2 c0 = c.first[d][0], c1 = c.first[d][1];
         int j = 0;
+        O oj = c.ob[d];                         // the lane's pair of step j: (beg + j + sub) * 8
         if (MG) {
           // first step peeled: its successor's pairs are already here (set_load_first requested them a set ago)
           if (len > 0) {
@@ -1436,11 +1507,11 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
           c0 = c.second[0];
           c1 = c.second[1];
           j = 8;
+          oj += 64u;
         }
-        for (; j < len; j += 8) {
-          int2 n0 = make_int2(0, Rg), n1 = make_int2(0, Rg);
-          if (j + 8 + sub < len) n0 = prd[d][beg + j + 8 + sub];
-          if (j + 12 + sub < len) n1 = prd[d][beg + j + 12 + sub];
+        for (; j < len; j += 8, oj += 64u) {
+          const int2 n0 = ld_pair(ps.base[d], off_min(oj, ps.hi[2]), 64, j + 8 + sub < len, Rg);
+          const int2 n1 = ld_pair(ps.base[d], off_min(oj, ps.hi[3]), 96, j + 12 + sub < len, Rg);
           slice_fma4<NI>(acc, c0, Td[d]);
           // second half of the step only if some node of the set still has facts there (most rows of the
           // inverse direction hold one or two facts)
@@ -1449,22 +1520,24 @@ __global__ __launch_bounds__(kSliceThreads, GNNRAG_SLICE_WPE) void k_walk_slice(
           c1 = n1;
         }
       }
+      const O oo = (O)(unsigned)(g * N + set * 16) * rowB + laneB;
 #pragma unroll
       for (int i = 0; i < NA; ++i)
-        if (col_ok[i]) *reinterpret_cast<f32x4*>(slice_out(a, c.n, col0 + kSliceW * i + 4 * sub)) = acc.v[i];
+        if (col_ok[i]) g_st<f32x4, O>(a.out, oo, 4 * kSliceW * i, acc.v[i]);
     }
   };
-  SetRows s0, s1, s2;
+  const bool listed = nlist != 0;
+  SetRows<O> s0, s1, s2;
   int t0 = next_set();
-  set_load_rows<MG>(s0, a, g, t0, nsets, grp);
+  set_load_rows<O>(s0, a, g, t0, nsets, grp);
   int t1 = t0 < nsets ? next_set() : nsets;
-  set_load_rows<MG>(s1, a, g, t1, nsets, grp);
-  set_load_first<MG>(s0, prd, sub, Rg);
+  set_load_rows<O>(s1, a, g, t1, nsets, grp);
+  set_load_first<MG, O>(s0, ps, keep, a.big_deg, listed, sub, Rg);
   while (t0 < nsets) {
     const int t2 = t1 < nsets ? next_set() : nsets;
-    set_load_rows<MG>(s2, a, g, t2, nsets, grp);
-    set_load_first<MG>(s1, prd, sub, Rg);
-    walk_set(s0);
+    set_load_rows<O>(s2, a, g, t2, nsets, grp);
+    set_load_first<MG, O>(s1, ps, keep, a.big_deg, listed, sub, Rg);
+    walk_set(s0, t0);
     s0 = s1; t0 = t1;
     s1 = s2; t1 = t2;
   }
@@ -1633,6 +1706,34 @@ static int fill_common(WalkArgs& a, const gnnrag_csr* csr, int D, void* ws, size
   return 0;
 }
 
+#ifndef GNNRAG_WALK_ADDR64
+#define GNNRAG_WALK_ADDR64 0          // 1: every LDS-walk launch takes the 64-bit offsets (experiment builds: tests of that form)
+#endif
+
+// Whether every global array of an LDS-walk launch can be addressed as base + unsigned 32-bit byte offset (k_walk_slice's
+// A32): the pair stream (a wave-walked row requests up to 8 x 16 steps of 64 records past its end before the clamp, and
+// a lane group 16 records), the row pointers and big-node lists, out[], and both directions' tables counted from T[0].
+static bool slice_addr32(const WalkArgs& a, const gnnrag_csr* csr) {
+  if (GNNRAG_WALK_ADDR64) return false;
+  const uint64_t lim = (uint64_t)1 << 32;
+  const uint64_t F = csr->F > 0 ? (uint64_t)csr->F : 0, BN1 = (uint64_t)a.BN + 1, D = (uint64_t)a.D;
+  const char* t0 = reinterpret_cast<const char*>(a.T[0]);
+  const char* t1 = reinterpret_cast<const char*>(a.T[1]);
+  return (2 * F + (1u << 14)) * 8 < lim && BN1 * 4 < lim && BN1 * D * 4 < lim && t1 >= t0 &&
+         (uint64_t)(t1 - t0) + ((uint64_t)csr->rel_total + 1) * D * 4 < lim;
+}
+
+template <int NI, bool MG, bool A32>
+static int launch_slice_kernel(const WalkArgs& a, const int2* pr, int64_t F, int nblk, size_t lds, int nslice, int nfull, int pl,
+                               hipStream_t stream) {
+  static DeviceMask cap_raised;    // per kernel instantiation, per device
+  const int rc = raise_lds_cap(k_walk_slice<NI, MG, A32>, cap_raised);
+  if (rc) return rc;
+  hipLaunchKernelGGL((k_walk_slice<NI, MG, A32>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, pr, F, nslice, nfull, pl);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
 // k_fact_prior + k_walk_slice<NI>: the LDS walk of one fused aggregation call.  The prior pairs follow the
 // partial-sum scratch of one accumulator in the workspace.
 template <int NI>
@@ -1654,13 +1755,6 @@ static int launch_slice(const WalkArgs& a, const gnnrag_csr* csr, void* workspac
   constexpr int SW = SliceAcc<NI>::width;
   const int nslice = (D + SW - 1) / SW;
   const size_t lds = slice_lds_bytes(a.R1, NI, SW);
-  static DeviceMask cap_raised, cap_raised_m;    // per kernel instantiation, per device
-  {
-    const int rc = raise_lds_cap(k_walk_slice<NI, false>, cap_raised);
-    if (rc) return rc;
-    const int rc2 = raise_lds_cap(k_walk_slice<NI, true>, cap_raised_m);
-    if (rc2) return rc2;
-  }
   // per XCD: items = (questions of the XCD) x slices, slots = 2 workgroups on each of its CUs
   int cus = 0;
   {
@@ -1680,14 +1774,13 @@ static int launch_slice(const WalkArgs& a, const gnnrag_csr* csr, void* workspac
     if (pl < 2) pl = 0;       // halves are what the tail split above already gives
     if (pl) nblk = 8 * (items_x << pl);
   }
-  if (a.merged)
-    hipLaunchKernelGGL((k_walk_slice<NI, true>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
-                       nslice, nfull, pl);
-  else
-    hipLaunchKernelGGL((k_walk_slice<NI, false>), dim3(nblk), dim3(kSliceThreads), lds, stream, a, (const int2*)pr, F,
-                       nslice, nfull, pl);
-  GNNRAG_LAUNCH_CHECK();
-  return 0;   // hubs were walked inside the kernel, nothing to add afterwards
+  // merged rows only with both directions walked (prepare_fused): the merged kernels never see a skip_dir
+  // (hubs are walked inside the kernel, nothing to add afterwards)
+  if (slice_addr32(a, csr))
+    return a.merged ? launch_slice_kernel<NI, true, true>(a, pr, F, nblk, lds, nslice, nfull, pl, stream)
+                    : launch_slice_kernel<NI, false, true>(a, pr, F, nblk, lds, nslice, nfull, pl, stream);
+  return a.merged ? launch_slice_kernel<NI, true, false>(a, pr, F, nblk, lds, nslice, nfull, pl, stream)
+                  : launch_slice_kernel<NI, false, false>(a, pr, F, nblk, lds, nslice, nfull, pl, stream);
 }
 
 }  // namespace gnnrag
