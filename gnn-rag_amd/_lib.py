@@ -66,6 +66,11 @@ class BertLayer(C.Structure):
                                           "ln2_g", "ln2_b")]
 
 
+class SplitkPlanStruct(C.Structure):
+    """Mirror of ``struct gnnrag_splitk_plan_t`` (include/gnnrag.h)."""
+    _fields_ = [("splits", C.c_int32), ("k_chunk", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
 class OptimSeg(C.Structure):
     """Mirror of ``struct gnnrag_optim_seg`` (include/gnnrag.h): 80 bytes, one entry per tensor of an optimiser step."""
     _fields_ = ([(n, C.c_void_p) for n in ("p", "g", "m", "v")] + [("n", C.c_int64), ("first_chunk", C.c_int64)] +
@@ -224,6 +229,15 @@ SIGNATURES = {
     "gnnrag_bert_encode_train": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
                                            C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
                                  [_VP, C.c_float, _VP, C.c_float, _VP, _VP, C.c_size_t, C.c_int32, _VP]),
+    # split-K linear for few rows and the inference encoder on it (additive to ABI 16)
+    "gnnrag_linear_splitk_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SplitkPlanStruct)]),
+    "gnnrag_linear_splitk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "gnnrag_linear_splitk": (C.c_int, [_VP, C.c_int64, C.c_int32, _VP, _VP, C.c_int32, _VP, _VP, _VP, C.c_float, _VP,
+                                       C.c_int32, C.c_int32, _VP, C.c_size_t, _VP]),
+    "gnnrag_bert_splitk_workspace_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "gnnrag_bert_encode_splitk": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
+                                            C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
+                                  [_VP, _VP, C.c_size_t, C.c_int32, _VP]),
     # relation-text features (additive to ABI 16)
     "gnnrag_rel_text_workspace_bytes": (C.c_size_t, [C.c_int64] + [C.c_int32] * 4),
     "gnnrag_rel_text_pool": (C.c_int, [_VP] * 6 + [C.c_int64] + [C.c_int32] * 3 + [_VP] * 5 + [C.c_size_t, _VP]),
@@ -257,6 +271,8 @@ PATH_ONLY_FWD, PATH_ONLY_INV = 0x10, 0x20        # OR-ed into the path: one-dire
 PATH_SEED_PRIOR = 0x40                           # OR-ed into the path: the (first layer's) prior is a seed distribution
 PATH_REUSE_PROJ = 0x80                           # gnnrag_reason_stack: the workspace still holds the relation projections
 E_TUPLE = -4
+SPLITK_EPI = {"bias": 0, "gelu": 1, "add_ln": 2}   # GNNRAG_SPLITK_EPI_* (include/gnnrag.h)
+SPLITK_MAX_SPLITS = 128                          # GNNRAG_SPLITK_MAX_SPLITS
 _lib = None
 
 

@@ -33,6 +33,7 @@
 // __shfl_xor tree, keys in ascending order), nothing allocated, nothing waits for the stream: safe under capture, a second
 // call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
 // attention: a workgroup per (question, head); the dense products: a row of C depends on its row of A only).
+#include "bert_device.h"
 #include "gnnrag_common.h"
 
 #ifndef GNNRAG_BERT_ATT_THREADS
@@ -44,45 +45,7 @@ namespace gnnrag {
 constexpr int kBertMaxT = 128;       // keys per question: two per lane
 constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
 
-// the multipliers of the 4 keep bytes in one 32-bit word (little endian: byte e belongs to element e)
-__device__ __forceinline__ f32x4 bert_keep4(uint32_t w, float scale) {
-  return (f32x4){(w & 0xffu) ? scale : 0.f, (w & 0xff00u) ? scale : 0.f, (w & 0xff0000u) ? scale : 0.f,
-                 (w & 0xff000000u) ? scale : 0.f};
-}
-
-// LayerNorm of one row by one wave: biased variance, two passes (mean, then sum (x - mean)^2); `load(i)` returns the
-// i-th float4 of the row (called three times per element: the row is L2 / L1 resident).  dst may be the row `load` reads:
-// a lane writes only the elements it has read itself, after both reductions.
-// DROP: the result is multiplied by scale where the row's keep byte is not 0, by 0 elsewhere (keep: the row's H bytes,
-// 4-byte aligned; a lane reads the 4 bytes of its float4 as one word).
-template <bool DROP = false, typename Load>
-__device__ __forceinline__ void bert_ln_row(Load load, const float* __restrict__ g, const float* __restrict__ bt,
-                                            float eps, int H4, int lane, float* dst,
-                                            const uint8_t* __restrict__ keep = nullptr, float scale = 0.f) {
-  const float inv_h = 1.f / (float)(H4 * 4);
-  float s = 0.f;
-  for (int i = lane; i < H4; i += 64) {
-    const f32x4 v = load(i);
-    s += (v[0] + v[1]) + (v[2] + v[3]);
-  }
-  const float mean = wave_sum(s) * inv_h;
-  float q = 0.f;
-  for (int i = lane; i < H4; i += 64) {
-    const f32x4 v = load(i);
-    const float d0 = v[0] - mean, d1 = v[1] - mean, d2 = v[2] - mean, d3 = v[3] - mean;
-    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-  }
-  const float rstd = 1.f / sqrtf(wave_sum(q) * inv_h + eps);
-  for (int i = lane; i < H4; i += 64) {
-    const f32x4 v = load(i);
-    const f32x4 gg = ((const f32x4*)g)[i], bb = ((const f32x4*)bt)[i];
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (v[e] - mean) * rstd * gg[e] + bb[e];
-    if (DROP) o = o * bert_keep4(((const uint32_t*)keep)[i], scale);
-    ((f32x4*)dst)[i] = o;
-  }
-}
+// bert_keep4, bert_ln_row (the LayerNorm of one row by one wave) and bert_gelu: bert_device.h
 
 // x[row] = LN(word_emb[id] + pos_emb[pos] + type_emb[0]); an id outside [0, vocab) reads nothing: its row is NaN.
 // IDPOS = false: pos = row % T.  IDPOS = true (pad_id >= 0): the wave counts the non-pad ids among ids[b, 0 .. t] itself
@@ -156,8 +119,6 @@ __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_drop_add_ln(const flo
   float* dst = out + (size_t)row * H4 * 4;
   bert_ln_row([&](int i) { return src[i] * bert_keep4(kr[i], scale) + ((const f32x4*)dst)[i]; }, g, bt, eps, H4, lane, dst);
 }
-
-__device__ __forceinline__ float bert_gelu(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752440f)); }
 
 // x = 0.5 x (1 + erf(x / sqrt 2)) in place over n floats (16-byte aligned); the last n % 4 by the first lanes
 __global__ __launch_bounds__(256) void k_bert_gelu(float* __restrict__ x, size_t n) {
@@ -331,6 +292,30 @@ static inline BertWs bert_ws(int64_t M, int64_t H, int64_t I) {
   return w;
 }
 
+// the workspace of the split-K form: qkv, ctx, ffn as above (no sum: the LayerNorm is the reduce's epilogue) and the
+// partial products of the largest of a layer's four products; total 0 for a shape gnnrag_linear_splitk refuses
+struct BertSplitkWs {
+  size_t qkv, ctx, ffn, part, part_bytes, total;
+};
+
+static inline BertSplitkWs bert_splitk_ws(int64_t M, int32_t H, int32_t I) {
+  BertSplitkWs w;
+  memset(&w, 0, sizeof(w));
+  const size_t p[4] = {gnnrag_linear_splitk_workspace_bytes(M, H, 3 * H, 0), gnnrag_linear_splitk_workspace_bytes(M, H, H, 0),
+                       gnnrag_linear_splitk_workspace_bytes(M, H, I, 0), gnnrag_linear_splitk_workspace_bytes(M, I, H, 0)};
+  for (int i = 0; i < 4; ++i) {
+    if (!p[i]) return w;
+    if (p[i] > w.part_bytes) w.part_bytes = p[i];
+  }
+  Carve cv;
+  w.qkv = cv.take((size_t)M * 3 * H * sizeof(float));
+  w.ctx = cv.take((size_t)M * H * sizeof(float));
+  w.ffn = cv.take((size_t)M * I * sizeof(float));
+  w.part = cv.take(w.part_bytes);
+  w.total = cv.off;
+  return w;
+}
+
 }  // namespace gnnrag
 
 using namespace gnnrag;
@@ -338,6 +323,11 @@ using namespace gnnrag;
 extern "C" size_t gnnrag_bert_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I) {
   if (B <= 0 || T <= 0 || H <= 0 || I <= 0) return 0;
   return bert_ws((int64_t)B * T, H, I).total;
+}
+
+extern "C" size_t gnnrag_bert_splitk_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I) {
+  if (B <= 0 || T <= 0 || H <= 0 || I <= 0 || (int64_t)3 * H > INT32_MAX) return 0;
+  return bert_splitk_ws((int64_t)B * T, H, I).total;
 }
 
 // the scale of a mask that is given: finite and > 0 (1 / (1 - p) of a p < 1)
@@ -376,12 +366,14 @@ extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int
 // all entry points; need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type term".
 // keep_hidden / keep_att NULL: that dropout site keeps the inference sequence (its scale is not read); both NULL is the
 // inference call, launch for launch.
+// splitk (inference only, both keeps NULL): the four products of a layer on gnnrag_linear_splitk, the GELU and the two
+// LayerNorms in its reduce; the embedding and attention launches are the same.
 static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
                            int32_t max_pos, const float* type_emb, bool need_type, int32_t pad_id, const float* rel_bias,
                            const float* ln_g, const float* ln_b, float ln_eps, int32_t L, const gnnrag_bert_layer* layers,
                            int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I, const uint8_t* keep_hidden,
                            float scale_hidden, const uint8_t* keep_att, float scale_att, float* out, void* ws,
-                           size_t ws_bytes, int32_t math, gnnrag_stream_t stream) {
+                           size_t ws_bytes, int32_t math, gnnrag_stream_t stream, bool splitk = false) {
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L < 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
   if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
   // the shape rules first: they are answered whatever the pointers are
@@ -392,7 +384,14 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   if (!bert_att_shape_ok(B, T, heads, dh) || (int64_t)B * T >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
   const int64_t M = (int64_t)B * T;
   const BertWs w = bert_ws(M, H, I);
-  if (L > 0 && ws_bytes < w.total) return GNNRAG_E_UNSUPPORTED;
+  BertSplitkWs sw{};
+  if (splitk) {
+    if (I % 4 != 0 || (int64_t)3 * H > INT32_MAX) return GNNRAG_E_UNSUPPORTED;
+    sw = bert_splitk_ws(M, H, I);
+    if (L > 0 && (!sw.total || ws_bytes < sw.total)) return GNNRAG_E_UNSUPPORTED;
+  } else if (L > 0 && ws_bytes < w.total) {
+    return GNNRAG_E_UNSUPPORTED;
+  }
   if (!ids || !word_emb || !pos_emb || (need_type && !type_emb) || !ln_g || !ln_b || !out || (L > 0 && (!layers || !ws)))
     return GNNRAG_E_BADARG;
   if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
@@ -434,6 +433,26 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
 #undef GNNRAG_EMBED_LN
   GNNRAG_LAUNCH_CHECK();
   if (L == 0) return 0;
+
+  if (splitk) {
+    float* qkv = (float*)((char*)ws + sw.qkv);
+    float* ctx = (float*)((char*)ws + sw.ctx);
+    float* ffn = (float*)((char*)ws + sw.ffn);
+    void* part = (char*)ws + sw.part;
+    for (int l = 0; l < L; ++l) {
+      const gnnrag_bert_layer& p = layers[l];
+      GNNRAG_RC(gnnrag_linear_splitk(out, M, H, p.W_qkv, p.b_qkv, GNNRAG_SPLITK_EPI_BIAS, nullptr, nullptr, nullptr, 0.f,
+                                     qkv, 3 * H, 0, part, sw.part_bytes, stream));
+      GNNRAG_RC(bert_attention_launch(qkv, rel_bias, nullptr, 0.f, B, T, heads, dh, ctx, st));
+      GNNRAG_RC(gnnrag_linear_splitk(ctx, M, H, p.W_o, p.b_o, GNNRAG_SPLITK_EPI_ADD_LN, out, p.ln1_g, p.ln1_b, ln_eps, out,
+                                     H, 0, part, sw.part_bytes, stream));
+      GNNRAG_RC(gnnrag_linear_splitk(out, M, H, p.W_i, p.b_i, GNNRAG_SPLITK_EPI_GELU, nullptr, nullptr, nullptr, 0.f, ffn,
+                                     I, 0, part, sw.part_bytes, stream));
+      GNNRAG_RC(gnnrag_linear_splitk(ffn, M, I, p.W_f, p.b_f, GNNRAG_SPLITK_EPI_ADD_LN, out, p.ln2_g, p.ln2_b, ln_eps, out,
+                                     H, 0, part, sw.part_bytes, stream));
+    }
+    return 0;
+  }
 
   float* qkv = (float*)((char*)ws + w.qkv);
   float* ctx = (float*)((char*)ws + w.ctx);
@@ -503,4 +522,14 @@ extern "C" int gnnrag_bert_encode_ex(const int64_t* ids, const float* word_emb, 
                                      gnnrag_stream_t stream) {
   return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
                          layers, B, T, H, heads, I, nullptr, 0.f, nullptr, 0.f, out, ws, ws_bytes, math, stream);
+}
+
+extern "C" int gnnrag_bert_encode_splitk(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                         int32_t max_pos, const float* type_emb, int32_t pad_id, const float* rel_bias,
+                                         const float* ln_g, const float* ln_b, float ln_eps, int32_t L,
+                                         const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H, int32_t heads,
+                                         int32_t I, float* out, void* ws, size_t ws_bytes, int32_t math,
+                                         gnnrag_stream_t stream) {
+  return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
+                         layers, B, T, H, heads, I, nullptr, 0.f, nullptr, 0.f, out, ws, ws_bytes, math, stream, true);
 }

@@ -39,6 +39,13 @@ dropout sites from torch's generator of the device and the kernels multiply them
 not ``F.dropout``'s draws: comparable loss curve, not equal draws.  Eval-mode calls and calls with both probabilities 0
 stay on the inference path, bit for bit.
 
+``GNNRAG_HIP_LM_SPLITK=1`` (read at every call; unset, empty or ``0`` is off, the default): an eligible INFERENCE call
+with ``B T <= SPLITK_MAX_ROWS`` rows runs on ``ops.bert_encode(..., splitk=True)`` - the four dense products of a layer on
+the split-K linear, which spreads a weight over the chip when a question brings 12 .. 20 rows, with the GELU and the
+LayerNorms in its reduce.  Exact fp32 in another summation order: the states are within the same bound, not the same bits,
+and a question's bits still do not depend on its batch.  Training-mode calls never take it.  Nothing else about
+eligibility changes; ``hip_splitk_calls`` counts these calls beside ``hip_calls``.
+
 An eligible call returns a ``BaseModelOutput`` whose ``[0]`` is ``last_hidden_state``; the pooler is not computed (the
 reference never reads it).  The packed query / key / value weight and bias of every layer are kept on the state object,
 keyed by ``(data_ptr, _version)`` of their six source tensors (as ``install.cache_rel_features`` keys its cache): an
@@ -60,6 +67,11 @@ DEFAULT = "1"        # GNNRAG_HIP_LM for BertModel when unset (DESIGN.md section
 # B = 64 (DESIGN.md section 8 f-6 keeps the numbers), so by the rule they stay off
 DEFAULT_ON = ("BertModel",)
 TRAIN_DEFAULT = "0"  # GNNRAG_HIP_LM_TRAIN when unset: off (DESIGN.md section 8 f-6 has the rule for a later flip)
+SPLITK_DEFAULT = "0"  # GNNRAG_HIP_LM_SPLITK when unset: off (DESIGN.md section 8 f-6 keeps the measurement)
+# the largest B T at which an inference call with GNNRAG_HIP_LM_SPLITK set takes the split-K encode: the largest measured
+# shape, (8, 20), at which its stream time is not worse than the encode without the switch; at (64, 20) it is
+# (tools/time_bert_encoder.py --splitk, profiles/bert_encoder_splitk_time.jsonl)
+SPLITK_MAX_ROWS = 160
 REL_BUCKETS = 32                # MPNetEncoder.compute_position_bias passes its default, whatever the configuration says
 
 # what differs between the classes: where positions come from, the token-type term, the attention bias, the names
@@ -83,6 +95,17 @@ def train_enabled() -> bool:
     """Whether a training-mode call with active dropout may use the library (``GNNRAG_HIP_LM_TRAIN``, read at every
     call)."""
     return os.environ.get("GNNRAG_HIP_LM_TRAIN", TRAIN_DEFAULT) not in ("0", "")
+
+
+def splitk_enabled() -> bool:
+    """Whether an eligible inference call may take the split-K encode (``GNNRAG_HIP_LM_SPLITK``, read at every call; unset,
+    empty or ``0`` is off)."""
+    return os.environ.get("GNNRAG_HIP_LM_SPLITK", SPLITK_DEFAULT) not in ("0", "")
+
+
+def splitk_rows_ok(B: int, T: int) -> bool:
+    """The split-K encode is for few rows: ``B T <= SPLITK_MAX_ROWS``."""
+    return 0 < int(B) * int(T) <= SPLITK_MAX_ROWS
 
 
 def draw_keep(L: int, B: int, T: int, H: int, heads: int, p_hidden: float, p_att: float, device):
@@ -134,6 +157,7 @@ class _LmPatch:
         self.bias_key, self.bias = None, {}     # MPNet: T -> the bias table, and the weight they were made from
         self.hip_calls = 0                      # eligible calls served by the library (tests, tools)
         self.hip_train_calls = 0                # those of them that ran the training-mode forward
+        self.hip_splitk_calls = 0               # those of them that ran the split-K inference encode
 
     # -- eligibility ----------------------------------------------------------------------------------------------
     def pad_id(self):
@@ -255,6 +279,9 @@ class _LmPatch:
                 hidden = ops.bert_encode_train(*top, keep_hidden=keep_h, scale_hidden=_scale(p_h), keep_att=keep_a,
                                                scale_att=_scale(p_a), **rest)
                 self.hip_train_calls += 1
+            elif splitk_enabled() and splitk_rows_ok(int(ids.shape[0]), int(ids.shape[1])):
+                hidden = ops.bert_encode(*top, splitk=True, **rest)
+                self.hip_splitk_calls += 1
             else:
                 hidden = ops.bert_encode(*top, **rest)
         self.hip_calls += 1

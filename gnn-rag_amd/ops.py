@@ -398,6 +398,62 @@ def linear(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None
     return out
 
 
+SplitkPlan = collections.namedtuple("SplitkPlan", "splits k_chunk launches")
+
+
+def linear_splitk_plan(M: int, K: int, Nout: int, splits: int = 0) -> SplitkPlan:
+    """``gnnrag_linear_splitk_plan`` (host only, no device): the effective ``(splits, k_chunk)`` and the launches of a
+    ``linear_splitk`` call.  ``splits=0`` is the library's rule - a function of ``(K, Nout)`` alone, never of ``M``; a
+    value >= 1 is forced.  A shape or a forced value the library refuses raises ``GnnragError`` with its code."""
+    plan = _lib.SplitkPlanStruct()
+    _lib.check(_lib.load().gnnrag_linear_splitk_plan(int(M), int(K), int(Nout), int(splits), C.byref(plan)),
+               "gnnrag_linear_splitk_plan")
+    return SplitkPlan(int(plan.splits), int(plan.k_chunk), int(plan.launches))
+
+
+def linear_splitk(A: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None, *, epi: str = "bias",
+                  add: Optional[torch.Tensor] = None, ln=None, splits: int = 0,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gnnrag_linear_splitk``: ``epilogue(A W^T + bias)`` with K cut into ``splits`` chunks across the chip and one
+    deterministic reduce (exact fp32 MFMA; made for few rows).  ``epi``: ``"bias"``, ``"gelu"`` (erf) or ``"add_ln"`` =
+    ``LayerNorm(x + add) g + b`` with ``ln = (g, b, eps)``.  ``out`` may be given, and for ``"add_ln"`` it may be ``add``
+    itself.  A row of the result depends on its row of ``A`` (and ``add``) only, never on ``M``."""
+    lib = _lib.load()
+    if epi not in _lib.SPLITK_EPI:
+        raise ValueError("epi must be one of %s" % (sorted(_lib.SPLITK_EPI),))
+    A = _chk(A, "A")
+    W = _chk(W, "W")
+    if A.dim() != 2 or W.dim() != 2 or W.shape[1] != A.shape[1]:
+        raise ValueError("W is %s, A is %s" % (tuple(W.shape), tuple(A.shape)))
+    M, K = A.shape
+    Nout = W.shape[0]
+    bias = None if bias is None else _chk(bias, "bias", shape=(Nout,))
+    g = b = None
+    eps = 0.0
+    if epi == "add_ln":
+        if add is None or ln is None:
+            raise ValueError("epi='add_ln' needs add and ln=(g, b, eps)")
+        if not add.is_contiguous():
+            raise ValueError("add must be contiguous")
+        add = _chk(add, "add", shape=(M, Nout))
+        g, b, eps = _chk(ln[0], "ln[0]", shape=(Nout,)), _chk(ln[1], "ln[1]", shape=(Nout,)), float(ln[2])
+    elif add is not None or ln is not None:
+        raise ValueError("add and ln belong to epi='add_ln'")
+    if out is None:
+        out = _buf((M, Nout), torch.float32, A.device, "linear_splitk: out")
+    else:
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
+        out = _chk(out, "out", shape=(M, Nout))
+    nws = int(lib.gnnrag_linear_splitk_workspace_bytes(M, K, Nout, int(splits)))
+    ws = _buf((max(nws, 16),), torch.uint8, A.device, "linear_splitk: workspace")
+    with torch.cuda.device(A.device):
+        _lib.check(lib.gnnrag_linear_splitk(A.data_ptr(), M, K, W.data_ptr(), _ptr(bias), _lib.SPLITK_EPI[epi], _ptr(add),
+                                            _ptr(g), _ptr(b), eps, out.data_ptr(), Nout, int(splits), ws.data_ptr(),
+                                            nws, _stream()), "gnnrag_linear_splitk")
+    return out
+
+
 def rel_transform(relfeat: torch.Tensor, relfeat_inv: torch.Tensor, layers, planes: bool = False, packed: bool = False):
     """Relation projections of all layers in one launch (reasongnn.py:75-79, :102-105):
     ``out[j, d] = rel_linear{j}(rel_features_d) (+ pos_emb{j}_d on its rows)``, d = 0 forward / 1 inverse.
@@ -1938,7 +1994,7 @@ def bert_attention_drop(qkv: torch.Tensor, B: int, T: int, heads: int, dh: int, 
 
 def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int, I: Optional[int] = None,
                 math: Optional[int] = None, *, pad_id: Optional[int] = None,
-                rel_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                rel_bias: Optional[torch.Tensor] = None, splitk: bool = False) -> torch.Tensor:
     """``gnnrag_bert_encode``: ids [B,T] int64 -> the last hidden state [B,T,H] of a BERT-class encoder (no mask, no
     pooler).  ``layers``: a list of dicts with the keys ``BERT_LAYER_FIELDS`` (W_qkv [3H,H] the query / key / value weights
     stacked, b_qkv [3H], W_o, b_o, ln1_g, ln1_b, W_i [I,H], b_i, W_f [H,I], b_f, ln2_g, ln2_b); an empty list returns the
@@ -1947,9 +2003,14 @@ def bert_encode(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers
 
     ``type_emb=None`` (no token-type term), ``pad_id`` (positions from the ids, as RoBERTa and MPNet count them) and
     ``rel_bias`` [heads, 2T-1] (MPNet's relative attention bias, every layer) go through ``gnnrag_bert_encode_ex``; with
-    the defaults the call is the one it has always been."""
+    the defaults the call is the one it has always been.
+
+    ``splitk=True`` is ``gnnrag_bert_encode_splitk``: the same encoder with the four dense products of a layer on the
+    split-K linear (``linear_splitk``, its own ``splits`` rule) and the GELU and LayerNorms in its reduce - made for the
+    12 .. 20 rows of one question; exact fp32 whatever ``math`` says.  Not the bits of the default call: another summation
+    order."""
     return _bert_encode("bert_encode", None, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math,
-                        pad_id, rel_bias)
+                        pad_id, rel_bias, splitk=bool(splitk))
 
 
 def bert_encode_train(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, layers, heads: int,
@@ -1965,7 +2026,8 @@ def bert_encode_train(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, 
                         type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias)
 
 
-def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias):
+def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias,
+                 splitk=False):
     """The shared body of ``bert_encode`` (``drop`` None) and ``bert_encode_train`` (``drop``: the two masks and scales)."""
     lib = _lib.load()
     ids = _chk(ids, "ids", dtype=torch.int64)
@@ -2009,7 +2071,7 @@ def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, 
             keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
             scale_att = _keep_scale(scale_att, "scale_att")
     out = _buf((B, T, H), torch.float32, dev, role + ": out")
-    nws = int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)) if L else 0
+    nws = int((lib.gnnrag_bert_splitk_workspace_bytes if splitk else lib.gnnrag_bert_workspace_bytes)(B, T, H, I)) if L else 0
     ws = _buf((max(nws, 1),), torch.uint8, dev, role + ": workspace")
     with torch.cuda.device(dev):
         if drop is not None:
@@ -2019,6 +2081,12 @@ def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, 
                                                     _ptr(keep_hidden), float(scale_hidden), _ptr(keep_att),
                                                     float(scale_att), out.data_ptr(), ws.data_ptr(), ws.numel(),
                                                     _math(math), _stream()), "gnnrag_bert_encode_train")
+        elif splitk:
+            _lib.check(lib.gnnrag_bert_encode_splitk(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
+                                                     pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
+                                                     ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I, out.data_ptr(),
+                                                     ws.data_ptr(), nws, _math(math), _stream()),
+                       "gnnrag_bert_encode_splitk")
         elif type_emb is not None and pad < 0 and rel_bias is None:
             _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
                                               pos_emb.shape[0], type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(),

@@ -985,6 +985,54 @@ int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t 
                              const uint8_t* keep_att /* or NULL */, float scale_att, float* out /* [B,T,H] */, void* ws,
                              size_t ws_bytes, int32_t math, gnnrag_stream_t stream);
 
+/* ---- Split-K linear for few rows, and the inference encoder on it (additive to ABI 16) ------------
+ * C = epilogue(A W^T + bias): A [M, K], W [Nout, K], bias [Nout] or NULL, C [M, Nout], all fp32.  K is cut into `splits`
+ * chunks of k_chunk (the last may be short); the first launch writes the chunks' partial products P[s] [M, Nout] into the
+ * workspace - exact fp32 MFMA, k ascending inside a chunk, a weight read once per group of up to 64 rows - and the second adds
+ * them in chunk order and applies the epilogue:  x = ((P[0] + P[1]) + ... + P[splits-1]) + bias, then
+ *   GNNRAG_SPLITK_EPI_BIAS     C = x
+ *   GNNRAG_SPLITK_EPI_GELU     C = 0.5 x (1 + erf(x / sqrt 2))     the encoder's own function: equal bits for equal x
+ *   GNNRAG_SPLITK_EPI_ADD_LN   C = LayerNorm(x + add) ln_g + ln_b   add [M, Nout]; biased variance, two passes, ln_eps inside
+ *                              the root, a wave per row as in the encoder; C may be the buffer add is.  Any Nout % 4 == 0.
+ * Two launches (at splits = 1 too), no atomics, no flags or counters between workgroups, no allocation, nothing waits for
+ * the stream, safe under capture.
+ * Value rule: C[r, c] depends on A[r, :], W[c, :] (all of W for a LayerNorm row), bias, add[r, :], ln_g, ln_b, K and the
+ * effective (splits, k_chunk) only - never on M, on where row r sits, or on the device.  splits = 0 takes the library's
+ * rule, a host-only function of (K, Nout) alone, so a question's bits do not depend on the batch it rides in; splits >= 1
+ * forces the value: k_chunk is then ceil(K / splits) rounded up to a multiple of 4.
+ * gnnrag_linear_splitk_plan reports the effective values and the launches (host only; M enters the argument checks only).
+ * gnnrag_linear_splitk_workspace_bytes: splits M Nout 4 bytes with the effective splits, rounded up to a multiple of 256;
+ * 0 for arguments the call refuses.
+ * Rules, answered in this order before anything is launched: a size <= 0, splits < 0 or an unknown epilogue is
+ * GNNRAG_E_BADARG; then the shape rules, whatever the pointers are: K % 4 != 0, Nout % 4 != 0, M >= 2^31, splits above
+ * GNNRAG_SPLITK_MAX_SPLITS, a forced value that would leave an empty chunk ((splits - 1) k_chunk >= K) or a workspace below
+ * the stated size are GNNRAG_E_UNSUPPORTED; then a NULL among A, W, C, ws (ADD_LN: add, ln_g, ln_b) or a NULL plan is
+ * GNNRAG_E_BADARG; then a pointer that is not 16-byte aligned is GNNRAG_E_UNSUPPORTED.
+ *
+ * gnnrag_bert_encode_splitk: gnnrag_bert_encode_ex (its arguments, its rules, its embedding and attention launches) with the
+ * four dense products of a layer on gnnrag_linear_splitk at splits = 0: QKV with BIAS, the attention output projection
+ * with ADD_LN (add = the residual, C = the residual's buffer), FFN-in with GELU, FFN-out with ADD_LN.  The separate GELU and
+ * LayerNorm launches are gone: 9 launches per layer.  Inference only.  The products are exact fp32 whatever `math` is (it is
+ * checked, not used).  The workspace is gnnrag_bert_splitk_workspace_bytes(B, T, H, I): qkv, ctx, ffn and the largest of
+ * the four products' partials (0 for a size <= 0 or H % 4 / I % 4 != 0, which the call refuses as UNSUPPORTED). */
+#define GNNRAG_SPLITK_EPI_BIAS   0
+#define GNNRAG_SPLITK_EPI_GELU   1
+#define GNNRAG_SPLITK_EPI_ADD_LN 2
+#define GNNRAG_SPLITK_MAX_SPLITS 128
+typedef struct gnnrag_splitk_plan_t { int32_t splits, k_chunk, launches, reserved[5]; } gnnrag_splitk_plan_t;
+int gnnrag_linear_splitk_plan(int64_t M, int32_t K, int32_t Nout, int32_t splits, gnnrag_splitk_plan_t* out);
+size_t gnnrag_linear_splitk_workspace_bytes(int64_t M, int32_t K, int32_t Nout, int32_t splits);
+int gnnrag_linear_splitk(const float* A, int64_t M, int32_t K, const float* W, const float* bias /* or NULL */,
+                         int32_t epi, const float* add, const float* ln_g, const float* ln_b, float ln_eps, float* C,
+                         int32_t Nout, int32_t splits, void* ws, size_t ws_bytes, gnnrag_stream_t stream);
+size_t gnnrag_bert_splitk_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t I);
+int gnnrag_bert_encode_splitk(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                              int32_t max_pos, const float* type_emb /* or NULL */, int32_t pad_id,
+                              const float* rel_bias /* [heads,2T-1] or NULL */, const float* ln_g, const float* ln_b,
+                              float ln_eps, int32_t L, const gnnrag_bert_layer* layers, int32_t B, int32_t T, int32_t H,
+                              int32_t heads, int32_t I, float* out /* [B,T,H] */, void* ws, size_t ws_bytes,
+                              int32_t math, gnnrag_stream_t stream);
+
 /* ---- Relation-text features (additive to ABI 16; SURVEY.md section 8 f-3, the relation-text branch) ----------------------
  * get_rel_feature with --relation_word_emb True (gnn/models/ReaRev/rearev.py:101-106, gnn/models/NSM/nsm.py:103-105):
  * question_emb over the frozen LM token states of the relation vocabulary, then AttnEncoder

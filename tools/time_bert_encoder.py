@@ -6,6 +6,8 @@
                                       [--out profiles/bert_encoder_time.jsonl]
     python tools/time_bert_encoder.py --kernel [--libs 256=,64=gnn-rag_amd/lib/exp_bertatt64.so,...]
     python tools/time_bert_encoder.py --train [--arch bert|roberta|mpnet]
+    python tools/time_bert_encoder.py --splitk [--arch bert|roberta] [--kernel]
+                                      [--out profiles/bert_encoder_splitk_time.jsonl]
 
 * the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
   tests/bert_oracle.py - the real all-MiniLM-L6-v2 weights are not needed for a timing) in eval mode, ``enc(ids)[0]`` on a
@@ -26,6 +28,14 @@
 ``GNNRAG_HIP_LM=1`` in both legs, ``GNNRAG_HIP_LM_TRAIN`` off (transformers' own forward) and on (``draw_keep`` and
 ``gnnrag_bert_encode_train``), each in a process of its own; the same shapes, host enqueue and stream time; no per-kernel
 split.  The draws differ between the legs (and between iterations), so there is no checksum to compare.
+
+``--splitk``: the inference encode with ``GNNRAG_HIP_LM=1`` in both legs and ``GNNRAG_HIP_LM_SPLITK`` off (the encode as it
+has always been) and on (``gnnrag_bert_encode_splitk``), each in a process of its own; the same shapes, host enqueue and
+stream time.  The on leg lifts ``SPLITK_MAX_ROWS`` so that every shape is measured on the new path: that bound is what the
+numbers decide.  ``--splitk --kernel``: device time of the four dense products of a layer at the
+MiniLM and the 768-wide shape, 20 calls per graph - ``ops.linear`` (the product alone; its GELU or LayerNorm is one more
+launch in the encode) against ``ops.linear_splitk`` (the product, the reduce and the epilogue) at the library's ``splits``,
+and at (1, 12) a sweep over forced ``splits`` with the bytes of W over the time beside it.
 
 ``--kernel``: ``gnnrag_bert_attention`` alone, 20 calls per graph, per library given in ``--libs`` as ``label=path``
 (``GNNRAG_LIB``; empty path = the built library): how the workgroup size (``-DGNNRAG_BERT_ATT_THREADS``,
@@ -112,6 +122,10 @@ def child_encode(a):
     from gnnrag_amd import ops
     from gnnrag_amd.modules.question_encoding.lm_encoder import enabled, patch_lm_encoder, train_enabled
     on = train_enabled() if a.train else enabled(ARCHS[a.arch])
+    if a.splitk:
+        from gnnrag_amd.modules.question_encoding import lm_encoder
+        on = lm_encoder.splitk_enabled()
+        lm_encoder.SPLITK_MAX_ROWS = 1 << 30    # measure every shape on the new path: the bound is read off these numbers
     if a.arch == "bert":
         shape, n_layers, vocab = bo.MINILM, L, VOCAB
         m32 = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)[0]
@@ -142,18 +156,20 @@ def child_encode(a):
             with torch.no_grad():
                 out[:] = [enc(x)[0]]
 
-        before, before_train = patch.hip_calls, patch.hip_train_calls
+        before, before_train, before_splitk = patch.hip_calls, patch.hip_train_calls, patch.hip_splitk_calls
         host, ev, host_min, ev_min = _measure(torch, encode, ids, a.warm)
-        rec = {"what": "encode_train" if a.train else "encode", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
+        rec = {"what": "encode_train" if a.train else "encode_splitk" if a.splitk else "encode", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
                "H": shape["H"], "I": shape["I"],
                "host_ms": host, "event_ms": ev, "host_ms_min": host_min, "event_ms_min": ev_min, "iters": a.iters,
                "warm": a.warm, "hip_calls_per_encode": (patch.hip_calls - before) / len(ids),
                "checksum": float(out[0].double().square().sum()), "device": torch.cuda.get_device_name(0)}
+        if a.splitk:
+            rec["hip_splitk_calls_per_encode"] = (patch.hip_splitk_calls - before_splitk) / len(ids)
         if a.train:
             rec["dropout"] = float(enc.config.hidden_dropout_prob)
             rec["hip_train_calls_per_encode"] = (patch.hip_train_calls - before_train) / len(ids)
         print(TAG + json.dumps(rec), flush=True)
-        if not on or a.arch != "bert" or a.train:
+        if not on or a.arch != "bert" or a.train or a.splitk:
             continue
         # the split of the HIP leg
         P = bo.layer_params(enc)
@@ -193,6 +209,54 @@ def child_kernel(a):
             print(TAG + json.dumps(rec), flush=True)
 
 
+SWEEP = (1, 2, 4, 8, 16, 32, 64, 128)
+
+
+def child_splitk_kernel(a):
+    """The four products of a layer: the old form (``ops.linear``) against the split-K form, and the sweep at (1, 12)."""
+    torch, bo, dev = _setup()
+    from gnnrag_amd import _lib, ops
+    name = torch.cuda.get_device_name(0)
+    for shape_name, shp in (("minilm", bo.MINILM), ("base", BASE)):
+        H, I = shp["H"], shp["I"]
+        W = {"qkv": torch.randn(3 * H, H, device=dev) * 0.05, "out_proj": torch.randn(H, H, device=dev) * 0.05,
+             "ffn_in": torch.randn(I, H, device=dev) * 0.05, "ffn_out": torch.randn(H, I, device=dev) * 0.05}
+        epi = {"qkv": "bias", "out_proj": "add_ln", "ffn_in": "gelu", "ffn_out": "add_ln"}
+        g, b = torch.ones(H, device=dev), torch.zeros(H, device=dev)
+        for B, T in SHAPES:
+            M = B * T
+            res = torch.randn(M, H, device=dev)
+            for prod, w in W.items():
+                Nout, K = w.shape
+                x = torch.randn(M, K, device=dev)
+                bias = torch.randn(Nout, device=dev) * 0.1
+                ln = epi[prod] == "add_ln"
+                kw = dict(epi=epi[prod], add=res, ln=(g, b, 1e-12)) if ln else dict(epi=epi[prod])
+                old = _graph_us(torch, lambda: ops.linear(x, w, bias, add=res if ln else None), a)
+                plan = ops.linear_splitk_plan(M, K, Nout)
+                new = _graph_us(torch, lambda: ops.linear_splitk(x, w, bias, **kw), a)
+                rec = {"what": "splitk_product", "shape": shape_name, "product": prod, "B": B, "T": T, "K": K, "Nout": Nout,
+                       "epilogue": epi[prod], "linear_us": old, "splitk_us": new, "splits": plan.splits,
+                       "k_chunk": plan.k_chunk, "calls_per_graph": CALLS, "iters": a.iters, "device": name}
+                if M <= 16:
+                    rec["w_bytes"] = 4 * K * Nout
+                    rec["linear_w_tb_s"], rec["splitk_w_tb_s"] = 4e-6 * K * Nout / old, 4e-6 * K * Nout / new
+                print(TAG + json.dumps(rec), flush=True)
+                if (B, T) != SHAPES[0]:
+                    continue
+                sweep = {}
+                for s in SWEEP:
+                    try:
+                        ops.linear_splitk_plan(M, K, Nout, s)
+                    except _lib.GnnragError:
+                        continue                # above K / 4, or a value that would leave an empty chunk
+                    sweep[str(s)] = _graph_us(torch, lambda: ops.linear_splitk(x, w, bias, splits=s, **kw), a)
+                print(TAG + json.dumps({"what": "splitk_sweep", "shape": shape_name, "product": prod, "B": B, "T": T, "K": K,
+                                        "Nout": Nout, "us_by_splits": sweep, "rule_splits": plan.splits, "rule_us": new,
+                                        "w_bytes": 4 * K * Nout, "calls_per_graph": CALLS, "iters": a.iters,
+                                        "device": name}), flush=True)
+
+
 def _spawn(argv, env_extra, lines, limit):
     """A fresh child process under its own time limit (nothing replaces the program of a process that holds the GPU)."""
     env = dict(os.environ)
@@ -215,17 +279,31 @@ def main():
     ap.add_argument("--arch", choices=sorted(ARCHS), default="bert")
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--train", action="store_true", help="training mode at dropout 0.1: GNNRAG_HIP_LM_TRAIN off / on")
+    ap.add_argument("--splitk", action="store_true", help="inference: GNNRAG_HIP_LM_SPLITK off / on; with --kernel the products")
     ap.add_argument("--libs", default="256=")
     ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "bert_encoder_time.jsonl"))
-    ap.add_argument("--child", choices=["encode", "kernel"])
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", choices=["encode", "kernel", "splitk_kernel"])
     ap.add_argument("--label", default="")
     a = ap.parse_args()
     if a.child:
-        return {"encode": child_encode, "kernel": child_kernel}[a.child](a)
-    common = ["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch] + (["--train"] if a.train else [])
+        return {"encode": child_encode, "kernel": child_kernel, "splitk_kernel": child_splitk_kernel}[a.child](a)
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "bert_encoder_splitk_time.jsonl" if a.splitk else "bert_encoder_time.jsonl")
+    common = (["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch] + (["--train"] if a.train else []) +
+              (["--splitk"] if a.splitk else []))
     lines = []
-    if a.kernel:
+    if a.splitk and a.kernel:
+        _spawn(["--child", "splitk_kernel"] + common, {}, lines, a.limit)
+    elif a.splitk:
+        for rnd in range(a.rounds):
+            for switch in ("0", "1"):
+                before = len(lines)
+                _spawn(["--child", "encode"] + common, {"GNNRAG_HIP_LM": "1", "GNNRAG_HIP_LM_SPLITK": switch}, lines, a.limit)
+                for rec in lines[before:]:
+                    rec["round"] = rnd
+                    rec["splitk"] = "on" if switch == "1" else "off"
+    elif a.kernel:
         for spec in a.libs.split(","):
             label, _, path = spec.partition("=")
             env = {"GNNRAG_LIB": os.path.abspath(os.path.join(REPO, path))} if path else {}
