@@ -66,6 +66,12 @@ class BertLayer(C.Structure):
                                           "ln2_g", "ln2_b")]
 
 
+class BertLayerGrads(C.Structure):
+    """Mirror of ``struct gnnrag_bert_layer_grads`` (include/gnnrag.h); a NULL field is a gradient that is not wanted."""
+    _fields_ = [(n, C.c_void_p) for n in ("dW_qkv", "db_qkv", "dW_o", "db_o", "dln1_g", "dln1_b", "dW_i", "db_i", "dW_f",
+                                          "db_f", "dln2_g", "dln2_b")]
+
+
 class SplitkPlanStruct(C.Structure):
     """Mirror of ``struct gnnrag_splitk_plan_t`` (include/gnnrag.h)."""
     _fields_ = [("splits", C.c_int32), ("k_chunk", C.c_int32), ("launches", C.c_int32), ("reserved", C.c_int32 * 5)]
@@ -229,6 +235,19 @@ SIGNATURES = {
     "gnnrag_bert_encode_train": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, C.c_float,
                                            C.c_int32, C.POINTER(BertLayer)] + [C.c_int32] * 5 +
                                  [_VP, C.c_float, _VP, C.c_float, _VP, _VP, C.c_size_t, C.c_int32, _VP]),
+    # fine-tuning the encoder: the layers' saving forward and their backward (additive to ABI 16)
+    "gnnrag_bert_reserve_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "gnnrag_bert_layers_forward_save": (C.c_int, [_VP, C.c_int32, C.POINTER(BertLayer), C.c_float] + [C.c_int32] * 5 +
+                                        [_VP, C.c_float, _VP, C.c_float, _VP, _VP, C.c_size_t, _VP, C.c_size_t, C.c_int32,
+                                         _VP]),
+    "gnnrag_bert_layers_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "gnnrag_bert_layers_backward": (C.c_int, [_VP, C.c_int32, C.POINTER(BertLayer), C.c_float] + [C.c_int32] * 5 +
+                                    [_VP, C.c_float, _VP, C.c_float, _VP, C.c_size_t, _VP, C.POINTER(BertLayerGrads), _VP,
+                                     C.c_size_t, _VP]),
+    "gnnrag_bert_attention_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_bert_attention_backward": (C.c_int, [_VP, _VP] + [C.c_int32] * 4 + [_VP, C.c_float, _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_bert_ln_backward": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, _VP, C.c_float, C.c_int64, C.c_int32] + [_VP] * 6),
+    "gnnrag_bert_gelu_backward": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, _VP]),
     # split-K linear for few rows and the inference encoder on it (additive to ABI 16)
     "gnnrag_linear_splitk_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SplitkPlanStruct)]),
     "gnnrag_linear_splitk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),

@@ -13,7 +13,9 @@ two iterations on :class:`QueryReformFn` (``gnnrag_query_reform_train`` / ``gnnr
 reasoning layer on :class:`LayerTailFn` (``gnnrag_layer_tail_train`` / ``gnnrag_layer_tail_backward``), the concatenated update under
 dropout on :class:`UpdateDropFn` (``gnnrag_update_drop_train`` / ``gnnrag_update_drop_backward``), the KL loss behind
 the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``), the relation tables of
-the fused training form on :class:`RelationTablesFn` (``gnnrag_relation_tables`` / ``gnnrag_relation_tables_backward``)."""
+the fused training form on :class:`RelationTablesFn` (``gnnrag_relation_tables`` / ``gnnrag_relation_tables_backward``), the
+layers of an unfrozen BERT-class question encoder on :class:`BertLayersFn` (``gnnrag_bert_layers_forward_save`` /
+``gnnrag_bert_layers_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -384,3 +386,59 @@ class KLLossFn(torch.autograd.Function):
             return None, None, None
         pred, teacher, label_valid, reserve = ctx.saved_tensors
         return ops.kl_loss_backward(g_loss.float().reshape(1), pred, teacher, label_valid, reserve), None, None
+
+
+BERT_LAYER_PARAMS = 16      # per layer: query / key / value weights, their biases, then W_o, b_o, ln1_g, ln1_b, W_i .. ln2_b
+
+
+class BertLayersFn(torch.autograd.Function):
+    """``out [B,T,H]`` = the encoder layers of a BERT-class LM on ``x0 [B,T,H]`` (the output of the embedding stage, which
+    stays transformers' module) on ``gnnrag_bert_layers_forward_save`` / ``gnnrag_bert_layers_backward``.  ``params``: per
+    layer the ``BERT_LAYER_PARAMS`` tensors - the separate query / key / value weights, their biases, then W_o, b_o, ln1_g,
+    ln1_b, W_i, b_i, W_f, b_f, ln2_g, ln2_b.  The packed ``W_qkv`` / ``b_qkv`` are built here and their gradients go back
+    as their three row blocks (the key bias block is exactly zero, see the header).  ``keep_hidden`` / ``keep_att``: the
+    keep bytes of ``ops.bert_keep_shapes`` or None; they never receive a gradient.  The reserve, the masks and the packed
+    weights are saved in the context of THIS call: two encodes followed by one backward each read their own."""
+
+    @staticmethod
+    def forward(ctx, x0, keep_hidden, scale_hidden, keep_att, scale_att, heads, eps, *params):
+        L = len(params) // BERT_LAYER_PARAMS
+        if L < 1 or L * BERT_LAYER_PARAMS != len(params):
+            raise ValueError("BertLayersFn: %d tensors per layer" % BERT_LAYER_PARAMS)
+        B, T, H = x0.shape
+        layers = []
+        for l in range(L):
+            p = [t.detach() for t in params[BERT_LAYER_PARAMS * l: BERT_LAYER_PARAMS * (l + 1)]]
+            layers.append(dict(zip(ops.BERT_LAYER_FIELDS, [torch.cat(p[0:3], 0).contiguous(),
+                                                           torch.cat(p[3:6], 0).contiguous()] + p[6:])))
+        out, reserve = ops.bert_layers_forward_save(x0.detach(), layers, int(heads), float(eps), B, T,
+                                                    keep_hidden=keep_hidden, scale_hidden=scale_hidden,
+                                                    keep_att=keep_att, scale_att=scale_att)
+        ctx.meta = (B, T, H, L, int(heads), float(eps), float(scale_hidden), float(scale_att))
+        ctx.save_for_backward(reserve, keep_hidden, keep_att, *[layer[n] for layer in layers for n in ops.BERT_LAYER_FIELDS])
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        B, T, H, L, heads, eps, scale_hidden, scale_att = ctx.meta
+        reserve, keep_hidden, keep_att = ctx.saved_tensors[:3]
+        flat, nf = ctx.saved_tensors[3:], len(ops.BERT_LAYER_FIELDS)
+        layers = [dict(zip(ops.BERT_LAYER_FIELDS, flat[nf * l: nf * (l + 1)])) for l in range(L)]
+        nig, first = ctx.needs_input_grad, 7
+        need = []
+        for l in range(L):
+            n = nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
+            d = {"dW_qkv": any(n[0:3]), "db_qkv": any(n[3:6])}
+            d.update({"d" + name: n[4 + i] for i, name in enumerate(ops.BERT_LAYER_FIELDS) if i >= 2})
+            need.append(d)
+        g_x0, grads = ops.bert_layers_backward(g_out.float(), layers, heads, eps, B, T, reserve, keep_hidden=keep_hidden,
+                                               scale_hidden=scale_hidden, keep_att=keep_att, scale_att=scale_att,
+                                               need_x0=nig[0], need=need)
+        ret = [g_x0, None, None, None, None, None, None]
+        for l in range(L):
+            g, n = grads[l], nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
+            for packed, lo in ((g["dW_qkv"], 0), (g["db_qkv"], 3)):
+                ret += [packed[H * k: H * (k + 1)] if packed is not None and n[lo + k] else None for k in range(3)]
+            ret += [g["d" + name] for name in ops.BERT_LAYER_FIELDS[2:]]
+        return tuple(ret)

@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libgnnrag_hip.so")
 ARCH = "gfx950"
-SOURCES = ["csr_plan.hip", "aggregate.hip", "aggregate_bwd.hip", "gemm_f32.hip", "tables_b3.hip", "softmax_layer.hip", "rel_transform.hip", "gemm_tn.hip", "rel_tables_bwd.hip", "dense_aux.hip", "eval_tail.hip", "query_update.hip", "query_update_bwd.hip", "layer_tail.hip", "train_tail.hip", "frontier.hip", "lstm.hip", "lstm_bwd.hip", "paths.hip", "instruction.hip", "instruction_bwd.hip", "rel_text.hip", "bert_encoder.hip", "linear_splitk.hip", "optim.hip"]
+SOURCES = ["csr_plan.hip", "aggregate.hip", "aggregate_bwd.hip", "gemm_f32.hip", "tables_b3.hip", "softmax_layer.hip", "rel_transform.hip", "gemm_tn.hip", "rel_tables_bwd.hip", "dense_aux.hip", "eval_tail.hip", "query_update.hip", "query_update_bwd.hip", "layer_tail.hip", "train_tail.hip", "frontier.hip", "lstm.hip", "lstm_bwd.hip", "paths.hip", "instruction.hip", "instruction_bwd.hip", "rel_text.hip", "bert_encoder.hip", "bert_encoder_bwd.hip", "linear_splitk.hip", "optim.hip"]
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(REPO, "include"),
          "-I" + CSRC, "-Wno-unused-result"]
 

@@ -34,6 +34,7 @@
 // call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
 // attention: a workgroup per (question, head); the dense products: a row of C depends on its row of A only).
 #include "bert_device.h"
+#include "bert_reserve.h"
 #include "gnnrag_common.h"
 
 #ifndef GNNRAG_BERT_ATT_THREADS
@@ -532,4 +533,86 @@ extern "C" int gnnrag_bert_encode_splitk(const int64_t* ids, const float* word_e
                                          gnnrag_stream_t stream) {
   return bert_encode_run(ids, word_emb, vocab, pos_emb, max_pos, type_emb, false, pad_id, rel_bias, ln_g, ln_b, ln_eps, L,
                          layers, B, T, H, heads, I, nullptr, 0.f, nullptr, 0.f, out, ws, ws_bytes, math, stream, true);
+}
+
+extern "C" size_t gnnrag_bert_reserve_bytes(int32_t L, int32_t B, int32_t T, int32_t H, int32_t I) {
+  if (L <= 0 || B <= 0 || T <= 0 || H <= 0 || I <= 0 || (H & 3) || (I & 3)) return 0;
+  return (size_t)L * bert_reserve((int64_t)B * T, H, I).layer;
+}
+
+// The L layers of bert_encode_run on a caller-given x0, launch for launch (the same kernels on the same values in the same
+// order: equal bits), with the values the backward needs left in the reserve (bert_reserve.h) instead of the workspace:
+// the products write their blocks of the reserve directly; the layer input, LayerNorm 1's output and the FFN
+// pre-activation are kept by a device copy in front of the launch that overwrites the running buffer.
+extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
+                                               int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
+                                               const uint8_t* keep_hidden, float scale_hidden, const uint8_t* keep_att,
+                                               float scale_att, float* out, void* reserve, size_t reserve_bytes, void* ws,
+                                               size_t ws_bytes, int32_t math, gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L <= 0) return GNNRAG_E_BADARG;
+  if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
+  if (H % heads != 0 || H % 4 != 0 || I % 4 != 0 || T > kBertMaxT) return GNNRAG_E_UNSUPPORTED;
+  const int32_t dh = H / heads;
+  if (!bert_att_shape_ok(B, T, heads, dh) || (int64_t)B * T >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
+  const int64_t M = (int64_t)B * T;
+  const BertWs w = bert_ws(M, H, I);
+  const BertReserve r = bert_reserve(M, H, I);
+  if (!x0 || !layers || !out || !reserve || !ws) return GNNRAG_E_BADARG;
+  if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
+  if (!aligned16(x0, out, reserve, ws) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
+  for (int l = 0; l < L; ++l) {
+    const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
+                                layers[l].ln1_g, layers[l].ln1_b, layers[l].W_i,   layers[l].b_i,
+                                layers[l].W_f,   layers[l].b_f,   layers[l].ln2_g, layers[l].ln2_b};
+    for (int i = 0; i < 12; ++i)
+      if (!p[i]) return GNNRAG_E_BADARG;
+    for (int i = 0; i < 12; ++i)
+      if (!aligned16(p[i])) return GNNRAG_E_UNSUPPORTED;
+  }
+  if (reserve_bytes < (size_t)L * r.layer || ws_bytes < w.total) return GNNRAG_E_WORKSPACE;
+
+  hipStream_t st = (hipStream_t)stream;
+  const int H4 = H / 4;
+  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
+  float* ffn = (float*)((char*)ws + w.ffn);
+  const size_t n_ffn = (size_t)M * I;
+  const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
+  const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
+  const size_t plane = (size_t)M * H, att_plane = (size_t)B * heads * T * T;
+  const size_t mh = plane * sizeof(float);
+  auto residual_block = [&](const float* a, int32_t K, const float* W, const float* b, const float* g, const float* bt,
+                            const uint8_t* keep, float* sum) -> int {
+    if (keep) {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, nullptr, 0, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_drop_add_ln, ln_grid, ln_block, 0, st, sum, keep, scale_hidden, g, bt, ln_eps, (int)M, H4,
+                         out);
+    } else {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, out, M, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, g, bt, ln_eps, (int)M, H4, out);
+    }
+    GNNRAG_LAUNCH_CHECK();
+    return 0;
+  };
+  if (out != x0) GNNRAG_HIP(hipMemcpyAsync(out, x0, mh, hipMemcpyDeviceToDevice, st));
+  for (int l = 0; l < L; ++l) {
+    const gnnrag_bert_layer& p = layers[l];
+    char* rl = (char*)reserve + (size_t)l * r.layer;
+    float* qkv = (float*)(rl + r.qkv);
+    float* ctx = (float*)(rl + r.ctx);
+    float* pre = (float*)(rl + r.pre);
+    GNNRAG_HIP(hipMemcpyAsync(rl + r.xin, out, mh, hipMemcpyDeviceToDevice, st));
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
+    GNNRAG_RC(bert_attention_launch(qkv, nullptr, keep_att ? keep_att + (size_t)l * att_plane : nullptr, scale_att, B, T,
+                                    heads, dh, ctx, st));
+    GNNRAG_RC(residual_block(ctx, H, p.W_o, p.b_o, p.ln1_g, p.ln1_b,
+                             keep_hidden ? keep_hidden + (size_t)(1 + 2 * l) * plane : nullptr, (float*)(rl + r.sum1)));
+    GNNRAG_HIP(hipMemcpyAsync(rl + r.x1, out, mh, hipMemcpyDeviceToDevice, st));
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, pre, I, math, stream));
+    GNNRAG_HIP(hipMemcpyAsync(ffn, pre, n_ffn * sizeof(float), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, ffn, n_ffn);
+    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(residual_block(ffn, I, p.W_f, p.b_f, p.ln2_g, p.ln2_b,
+                             keep_hidden ? keep_hidden + (size_t)(2 + 2 * l) * plane : nullptr, (float*)(rl + r.sum2)));
+  }
+  return 0;
 }

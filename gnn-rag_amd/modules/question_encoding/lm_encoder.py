@@ -27,7 +27,7 @@ unchanged:
 * the only argument is a 2-D int64 CUDA ``input_ids`` (an ``attention_mask``, ``token_type_ids``, ... fall through);
 * all parameters are contiguous fp32 CUDA tensors and the kernels take the shape (``ops.bert_encode_supported``; with
   positions from the ids also ``T + pad_id <= max_position_embeddings - 1``, where transformers itself would raise);
-* nothing needs a gradient: grad mode is off, or no LM parameter requires grad;
+* nothing needs a gradient: grad mode is off, or no LM parameter requires grad - or fine-tuning is switched on (below);
 * dropout is inert: the module is in eval mode, or both dropout probabilities are 0 - or the training-mode forward is
   switched on (next paragraph).
 
@@ -45,6 +45,19 @@ the split-K linear, which spreads a weight over the chip when a question brings 
 LayerNorms in its reduce.  Exact fp32 in another summation order: the states are within the same bound, not the same bits,
 and a question's bits still do not depend on its batch.  Training-mode calls never take it.  Nothing else about
 eligibility changes; ``hip_splitk_calls`` counts these calls beside ``hip_calls``.
+
+``GNNRAG_HIP_LM_FINETUNE=1`` (read at every call; unset, empty or ``0`` is off, the default): the reference's
+``--lm_frozen 0``.  A call that needs a gradient - grad mode on and an LM parameter requiring grad - otherwise ends in "a
+gradient is needed".  With the switch on it runs on the library when the class's ``GNNRAG_HIP_LM`` rule is met, the class is
+``BertModel`` or ``RobertaModel`` (``MPNetModel`` keeps transformers' forward, with a refusal text of its own: its
+relative-bias table would need a gradient), ``ops.bert_layers_backward_supported`` takes the shape and every other rule
+above holds.  ``x0 = enc.embeddings(input_ids)`` is then transformers' own module under torch autograd - its LayerNorm, its
+dropout, its position rule, its lookup backward - and the layers run on ``autograd.BertLayersFn``
+(``gnnrag_bert_layers_forward_save`` / ``gnnrag_bert_layers_backward``).  Active dropout does not need
+``GNNRAG_HIP_LM_TRAIN`` on this path: the keep bytes of planes ``1 .. 2L`` and of the attention planes come from
+:func:`draw_keep` (comparable loss curve, not equal draws).  The reserve belongs to the autograd context of the call: two
+encodes followed by one backward each read their own.  ``hip_finetune_calls`` counts these calls beside ``hip_calls``.  With
+the switch off or unset every call behaves as without it.
 
 An eligible call returns a ``BaseModelOutput`` whose ``[0]`` is ``last_hidden_state``; the pooler is not computed (the
 reference never reads it).  The packed query / key / value weight and bias of every layer are kept on the state object,
@@ -67,6 +80,7 @@ DEFAULT = "1"        # GNNRAG_HIP_LM for BertModel when unset (DESIGN.md section
 # B = 64 (DESIGN.md section 8 f-6 keeps the numbers), so by the rule they stay off
 DEFAULT_ON = ("BertModel",)
 TRAIN_DEFAULT = "0"  # GNNRAG_HIP_LM_TRAIN when unset: off (DESIGN.md section 8 f-6 has the rule for a later flip)
+FINETUNE_DEFAULT = "0"  # GNNRAG_HIP_LM_FINETUNE when unset: off (Fine-tuning: the rule for a flip)
 SPLITK_DEFAULT = "0"  # GNNRAG_HIP_LM_SPLITK when unset: off (DESIGN.md section 8 f-6 keeps the measurement)
 # the largest B T at which an inference call with GNNRAG_HIP_LM_SPLITK set takes the split-K encode: the largest measured
 # shape, (8, 20), at which its stream time is not worse than the encode without the switch; at (64, 20) it is
@@ -95,6 +109,12 @@ def train_enabled() -> bool:
     """Whether a training-mode call with active dropout may use the library (``GNNRAG_HIP_LM_TRAIN``, read at every
     call)."""
     return os.environ.get("GNNRAG_HIP_LM_TRAIN", TRAIN_DEFAULT) not in ("0", "")
+
+
+def finetune_enabled() -> bool:
+    """Whether a call that needs a gradient may run its layers on the library (``GNNRAG_HIP_LM_FINETUNE``, read at every
+    call; unset, empty or ``0`` is off)."""
+    return os.environ.get("GNNRAG_HIP_LM_FINETUNE", FINETUNE_DEFAULT) not in ("0", "")
 
 
 def splitk_enabled() -> bool:
@@ -158,6 +178,7 @@ class _LmPatch:
         self.hip_calls = 0                      # eligible calls served by the library (tests, tools)
         self.hip_train_calls = 0                # those of them that ran the training-mode forward
         self.hip_splitk_calls = 0               # those of them that ran the split-K inference encode
+        self.hip_finetune_calls = 0             # those of them that ran the layers under autograd (fine-tuning)
 
     # -- eligibility ----------------------------------------------------------------------------------------------
     def pad_id(self):
@@ -171,6 +192,10 @@ class _LmPatch:
         cfg = self.enc.config
         return bool(self.enc.training and (float(cfg.hidden_dropout_prob) != 0.0 or
                                            float(cfg.attention_probs_dropout_prob) != 0.0))
+
+    def needs_grad(self) -> bool:
+        """Whether a call now would have to be differentiated: grad mode is on and an LM parameter requires grad."""
+        return bool(torch.is_grad_enabled() and any(p.requires_grad for p in self.enc.parameters()))
 
     def refusal(self, args, kwargs):
         """None when the call runs on the library, else the first rule (of the module docstring) it does not meet."""
@@ -193,10 +218,17 @@ class _LmPatch:
         if ids.dtype != torch.int64 or ids.dim() != 2 or ids.numel() == 0:
             return "input_ids is not a 2-D int64 tensor"
         params = list(enc.parameters())
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return "a gradient is needed"
+        finetune = self.needs_grad()
+        if finetune:
+            if not finetune_enabled():
+                return "a gradient is needed"
+            if arch["rel_bias"]:
+                return "a gradient is needed and the relative attention bias has no backward on the library"
+            if len(enc.encoder.layer) < 1 or not ops.bert_layers_backward_supported(
+                    int(ids.shape[1]), int(cfg.hidden_size), int(cfg.num_attention_heads), int(cfg.intermediate_size)):
+                return "a shape the backward kernels do not take"
         if self.dropout_active():
-            if not train_enabled():
+            if not finetune and not train_enabled():
                 return "dropout is active"
             if not (float(cfg.hidden_dropout_prob) < 1.0 and float(cfg.attention_probs_dropout_prob) < 1.0):
                 return "a dropout probability of 1"
@@ -259,6 +291,27 @@ class _LmPatch:
                 self.bias[T] = rel_bias_table(self.enc.encoder, T)
         return self.bias[T]
 
+    def _finetune(self, ids):
+        """The unfrozen encoder: transformers' embedding stage under torch autograd (its LayerNorm, its dropout, its
+        position rule), then the layers on ``autograd.BertLayersFn``."""
+        from ... import autograd
+        enc, cfg = self.enc, self.enc.config
+        B, T = int(ids.shape[0]), int(ids.shape[1])
+        L, H, heads = len(enc.encoder.layer), int(cfg.hidden_size), int(cfg.num_attention_heads)
+        x0 = enc.embeddings(input_ids=ids)
+        keep_h, keep_a, p_h, p_a = None, None, 0.0, 0.0
+        if self.dropout_active():
+            p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
+            keep_h, keep_a = draw_keep(L, B, T, H, heads, p_h, p_a, ids.device)     # plane 0 (the embedding's) is not read
+        params = []
+        for layer in enc.encoder.layer:
+            q, k, v, o, ln1 = self._projections(layer)
+            it, fo = layer.intermediate.dense, layer.output
+            params += [q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, o.weight, o.bias, ln1.weight, ln1.bias,
+                       it.weight, it.bias, fo.dense.weight, fo.dense.bias, fo.LayerNorm.weight, fo.LayerNorm.bias]
+        return autograd.BertLayersFn.apply(x0, keep_h, _scale(p_h), keep_a, _scale(p_a), heads, float(cfg.layer_norm_eps),
+                                           *params)
+
     # -- the wrapper ----------------------------------------------------------------------------------------------
     def forward(self, *args, **kwargs):
         if self.refusal(args, kwargs) is not None:
@@ -267,6 +320,11 @@ class _LmPatch:
         enc = self.enc
         ids = args[0] if args else kwargs["input_ids"]
         emb, cfg = enc.embeddings, enc.config
+        if self.needs_grad():
+            hidden = self._finetune(ids)
+            self.hip_calls += 1
+            self.hip_finetune_calls += 1
+            return BaseModelOutput(last_hidden_state=hidden)
         type_emb = emb.token_type_embeddings.weight if _ARCH[self.arch]["token_type"] else None
         top = (ids, emb.word_embeddings.weight, emb.position_embeddings.weight, type_emb, emb.LayerNorm.weight,
                emb.LayerNorm.bias, float(cfg.layer_norm_eps), self.layers(), int(cfg.num_attention_heads))

@@ -2101,6 +2101,180 @@ def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, 
     return out
 
 
+BERT_GRAD_FIELDS = tuple(n for n, _ in _lib.BertLayerGrads._fields_)
+
+
+def bert_layers_backward_supported(T: int, H: int, heads: int, I: int) -> bool:
+    """Whether ``gnnrag_bert_layers_forward_save`` / ``gnnrag_bert_layers_backward`` take the shape (the header's rules:
+    those of the attention kernels, and ``H % 4 == 0``, ``I % 4 == 0`` for the weight-gradient products)."""
+    return (0 < T <= BERT_MAX_T and H > 0 and I > 0 and heads > 0 and H % heads == 0 and H % 4 == 0 and I % 4 == 0 and
+            H // heads in (32, 64))
+
+
+def _bert_layer_shapes(H: int, I: int):
+    return {"W_qkv": (3 * H, H), "b_qkv": (3 * H,), "W_o": (H, H), "b_o": (H,), "ln1_g": (H,), "ln1_b": (H,),
+            "W_i": (I, H), "b_i": (I,), "W_f": (H, I), "b_f": (H,), "ln2_g": (H,), "ln2_b": (H,)}
+
+
+def _bert_layer_array(layers, H: int, I: int):
+    """The host array of ``gnnrag_bert_layer`` structs and the tensors it points to (kept alive by the caller)."""
+    shapes, keep, arr = _bert_layer_shapes(H, I), [], (_lib.BertLayer * max(len(layers), 1))()
+    for l, layer in enumerate(layers):
+        for name in BERT_LAYER_FIELDS:
+            t = _chk(layer[name].detach(), "layers[%d].%s" % (l, name), shape=shapes[name])
+            keep.append(t)
+            setattr(arr[l], name, t.data_ptr())
+    return arr, keep
+
+
+def _bert_layers_args(x, layers, heads, keep_hidden, scale_hidden, keep_att, scale_att, B, T, who):
+    if x.dim() not in (2, 3):
+        raise ValueError("%s must be [B*T,H] or [B,T,H]" % who)
+    x = _chk(x, who, shape=(B * T, x.shape[-1]) if x.dim() == 2 else (B, T, x.shape[-1]))
+    H, L = int(x.shape[-1]), len(layers)
+    if L < 1:
+        raise ValueError("bert layers: at least one layer")
+    I = int(layers[0]["W_i"].shape[0])
+    shape_hidden, shape_att = bert_keep_shapes(L, B, T, H, heads)
+    if keep_hidden is not None:
+        keep_hidden = _chk(keep_hidden, "keep_hidden", dtype=torch.uint8, shape=shape_hidden)
+        scale_hidden = _keep_scale(scale_hidden, "scale_hidden")
+    if keep_att is not None:
+        keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
+        scale_att = _keep_scale(scale_att, "scale_att")
+    return x, H, I, L, keep_hidden, float(scale_hidden), keep_att, float(scale_att)
+
+
+def bert_layers_forward_save(x0, layers, heads: int, eps: float, B: int, T: int, math: Optional[int] = None, *,
+                             keep_hidden: Optional[torch.Tensor] = None, scale_hidden: float = 1.0,
+                             keep_att: Optional[torch.Tensor] = None, scale_att: float = 1.0):
+    """``gnnrag_bert_layers_forward_save``: the layers of ``bert_encode_train`` on ``x0`` [B*T, H] (or [B,T,H]) - the
+    output of the embedding stage - with the same launches, so the bits of ``bert_encode_train`` for the same ``x0`` and
+    masks.  ``keep_hidden`` has the (1 + 2L) planes of ``bert_keep_shapes`` (plane 0, the embedding's, is not read).
+    Returns ``(out, reserve)``: out of x0's shape and the reserve (uint8, ``gnnrag_bert_reserve_bytes``) that
+    :func:`bert_layers_backward` reads; it is allocated per call and belongs to this forward."""
+    lib = _lib.load()
+    x0, H, I, L, keep_hidden, scale_hidden, keep_att, scale_att = _bert_layers_args(
+        x0, layers, heads, keep_hidden, scale_hidden, keep_att, scale_att, B, T, "x0")
+    arr, keep = _bert_layer_array(layers, H, I)
+    dev = x0.device
+    role = "bert_layers_forward_save: "
+    out = _buf(tuple(x0.shape), torch.float32, dev, role + "out")
+    reserve = _buf((max(int(lib.gnnrag_bert_reserve_bytes(L, B, T, H, I)), 1),), torch.uint8, dev, role + "reserve")
+    ws = _buf((max(int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)), 1),), torch.uint8, dev, role + "workspace")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_layers_forward_save(x0.data_ptr(), L, arr, float(eps), B, T, H, heads, I,
+                                                       _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att,
+                                                       out.data_ptr(), reserve.data_ptr(), reserve.numel(), ws.data_ptr(),
+                                                       ws.numel(), _math(math), _stream()),
+                   "gnnrag_bert_layers_forward_save")
+    return out, reserve
+
+
+def bert_layers_backward(g_out, layers, heads: int, eps: float, B: int, T: int, reserve, *,
+                         keep_hidden: Optional[torch.Tensor] = None, scale_hidden: float = 1.0,
+                         keep_att: Optional[torch.Tensor] = None, scale_att: float = 1.0, need_x0: bool = True,
+                         need=None):
+    """Backward of :func:`bert_layers_forward_save` (``gnnrag_bert_layers_backward``): ``g_out`` the gradient of its output,
+    the layers, masks and scales as given to it, ``reserve`` as it returned it.  ``need``: per layer a dict over
+    ``BERT_GRAD_FIELDS`` of what is wanted (None: everything); an unwanted gradient is None and its product is not launched.
+    Returns ``(g_x0, grads)``: g_x0 of g_out's shape (None without ``need_x0``) and a list of dicts over ``BERT_GRAD_FIELDS``
+    (dW_qkv [3H,H], db_qkv [3H] with the key third exactly 0, ...).  One fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    g_out, H, I, L, keep_hidden, scale_hidden, keep_att, scale_att = _bert_layers_args(
+        g_out, layers, heads, keep_hidden, scale_hidden, keep_att, scale_att, B, T, "g_out")
+    arr, keep = _bert_layer_array(layers, H, I)
+    reserve = _chk(reserve, "reserve", dtype=torch.uint8)
+    dev = g_out.device
+    role = "bert_layers_backward: "
+    shapes = _bert_layer_shapes(H, I)
+    garr, grads = (_lib.BertLayerGrads * L)(), []
+    for l in range(L):
+        want = need[l] if need is not None else {}
+        g = {}
+        for name in BERT_GRAD_FIELDS:
+            wanted = bool(want.get(name, False)) if need is not None else True
+            g[name] = _buf(shapes[name[1:]], torch.float32, dev, role + name) if wanted else None   # dW_o: W_o's shape
+            setattr(garr[l], name, _ptr(g[name]))
+        grads.append(g)
+    g_x0 = _buf(tuple(g_out.shape), torch.float32, dev, role + "g_x0") if need_x0 else None
+    with torch.cuda.device(dev):
+        # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn inside): query it on g_out's device
+        ws = _buf((max(int(lib.gnnrag_bert_layers_backward_workspace_bytes(B, T, H, heads, I)), 16),), torch.uint8, dev,
+                  role + "workspace")
+        _lib.check(lib.gnnrag_bert_layers_backward(g_out.data_ptr(), L, arr, float(eps), B, T, H, heads, I,
+                                                   _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att,
+                                                   reserve.data_ptr(), reserve.numel(), _ptr(g_x0), garr, ws.data_ptr(),
+                                                   ws.numel(), _stream()), "gnnrag_bert_layers_backward")
+    return g_x0, grads
+
+
+def bert_attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, T: int, heads: int, dh: int,
+                            keep: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
+    """``gnnrag_bert_attention_backward``: d_qkv [B*T, 3*heads*dh] from qkv, d_ctx [B*T, heads*dh] and the keep bytes
+    [B, heads, T, T] of :func:`bert_attention_drop` (None: :func:`bert_attention`).  The probabilities are recomputed."""
+    lib = _lib.load()
+    H = heads * dh
+    qkv = _chk(qkv, "qkv", shape=(B * T, 3 * H))
+    d_ctx = _chk(d_ctx, "d_ctx", shape=(B * T, H))
+    if keep is not None:
+        keep = _chk(keep, "keep", dtype=torch.uint8, shape=(B, heads, T, T))
+        scale = _keep_scale(scale, "scale")
+    role = "bert_attention_backward: "
+    d_qkv = _buf((B * T, 3 * H), torch.float32, qkv.device, role + "d_qkv")
+    ws = _buf((max(int(lib.gnnrag_bert_attention_backward_workspace_bytes(B, T, heads)), 16),), torch.uint8, qkv.device,
+              role + "workspace")
+    with torch.cuda.device(qkv.device):
+        _lib.check(lib.gnnrag_bert_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), B, T, heads, dh, _ptr(keep),
+                                                      float(scale), d_qkv.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                      _stream()), "gnnrag_bert_attention_backward")
+    return d_qkv
+
+
+def bert_ln_backward(dy: torch.Tensor, d: torch.Tensor, g: torch.Tensor, eps: float,
+                     keep: Optional[torch.Tensor] = None, scale: float = 1.0, res: Optional[torch.Tensor] = None):
+    """``gnnrag_bert_ln_backward``: the backward of ``LN(z) g + b`` for the rows z = d * (keep ? scale : 0) + res (``keep``
+    uint8 [M,H] and ``res`` [M,H] together) or z = d (both None).  Returns ``(dz, dY, dgamma, dbeta)``: dz [M,H] the
+    gradient of z (and of res), dY = dz * (keep ? scale : 0) the gradient of d (dz itself without a mask), and the two
+    parameter gradients [H]."""
+    lib = _lib.load()
+    dy = _chk(dy, "dy")
+    M, H = dy.shape
+    d = _chk(d, "d", shape=(M, H))
+    g = _chk(g.detach(), "g", shape=(H,))
+    if (keep is None) != (res is None):
+        raise ValueError("bert_ln_backward: keep and res go together")
+    if keep is not None:
+        keep = _chk(keep, "keep", dtype=torch.uint8, shape=(M, H))
+        res = _chk(res, "res", shape=(M, H))
+        scale = _keep_scale(scale, "scale")
+    dev, role = dy.device, "bert_ln_backward: "
+    dz = _buf((M, H), torch.float32, dev, role + "dz")
+    dY = _buf((M, H), torch.float32, dev, role + "dY") if keep is not None else None
+    summ = _buf((M, H), torch.float32, dev, role + "summ")
+    dgamma, dbeta = _buf((H,), torch.float32, dev, role + "dgamma"), _buf((H,), torch.float32, dev, role + "dbeta")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_ln_backward(dy.data_ptr(), d.data_ptr(), _ptr(keep), float(scale), _ptr(res), g.data_ptr(),
+                                               float(eps), M, H, dz.data_ptr(), _ptr(dY), summ.data_ptr(), dgamma.data_ptr(),
+                                               dbeta.data_ptr(), _stream()), "gnnrag_bert_ln_backward")
+    return dz, (dz if dY is None else dY), dgamma, dbeta
+
+
+def bert_gelu_backward(pre: torch.Tensor, d_act: torch.Tensor, want_act: bool = False):
+    """``gnnrag_bert_gelu_backward``: ``d_pre = d_act * gelu'(pre)`` (the erf form) over any shape; with ``want_act`` also
+    ``gelu(pre)``.  Returns ``(d_pre, act or None)``."""
+    lib = _lib.load()
+    pre = _chk(pre, "pre")
+    d_act = _chk(d_act, "d_act", shape=tuple(pre.shape))
+    dev, role = pre.device, "bert_gelu_backward: "
+    d_pre = _buf(tuple(pre.shape), torch.float32, dev, role + "d_pre")
+    act = _buf(tuple(pre.shape), torch.float32, dev, role + "act") if want_act else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_gelu_backward(pre.data_ptr(), d_act.data_ptr(), pre.numel(), d_pre.data_ptr(), _ptr(act),
+                                                 _stream()), "gnnrag_bert_gelu_backward")
+    return d_pre, act
+
+
 REL_TEXT_MAX_T, REL_TEXT_MAX_K, REL_TEXT_MAX_D = 256, 4096, 4096     # GNNRAG_REL_TEXT_MAX_* (include/gnnrag.h)
 
 

@@ -985,6 +985,76 @@ int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t 
                              const uint8_t* keep_att /* or NULL */, float scale_att, float* out /* [B,T,H] */, void* ws,
                              size_t ws_bytes, int32_t math, gnnrag_stream_t stream);
 
+/* ---- Fine-tuning the encoder: the layers under autograd (additive to ABI 16; DESIGN.md section 8 f-6, Fine-tuning) --------
+ * The reference's --lm_frozen 0 trains the LM with the GNN.  The embedding stage stays with the caller (its output x0
+ * [B T, H] comes in, its gradient g_x0 goes out); BertModel / RobertaModel layers only (no rel_bias: MPNet's table would
+ * need a gradient of its own).
+ *
+ * gnnrag_bert_layers_forward_save: the L layers of gnnrag_bert_encode_train on x0 - the same launches on the same values in
+ * the same order, so `out` [B T, H] has the bits gnnrag_bert_encode_train gives for the same x0 and masks (keep_hidden: the
+ * (1 + 2L)-plane buffer of that call, planes 1 .. 2L are read; keep_att as there; NULL: the inference sequence of the site).
+ * out may be x0.  ws: gnnrag_bert_workspace_bytes(B, T, H, I).  It additionally leaves in `reserve`
+ * (gnnrag_bert_reserve_bytes(L, B, T, H, I) = L M (8 H + I) 4 bytes, M = B T; 0 for a size <= 0 or H % 4 / I % 4 != 0) per
+ * layer, in this order, without padding:
+ *   xin [M,H] the layer input | qkv [M,3H] | ctx [M,H] | sum1 [M,H] | x1 [M,H] LayerNorm 1's output | pre [M,I] the FFN
+ *   pre-activation (the value in front of the GELU) | sum2 [M,H]
+ * sum1 / sum2: the dense output in front of the LayerNorm - dense + bias under hidden dropout (the residual is added
+ * behind the dropout), dense + bias + residual without it.  The blocks the products write are written in place; xin, x1
+ * and pre are kept by a device copy.
+ *
+ * gnnrag_bert_layers_backward: from g_out [M,H] (the gradient of `out`), the reserve and the masks and scales of the
+ * forward: g_x0 [M,H] and per layer (grads: HOST array of L structs of device pointers, or NULL) dW_qkv [3H,H], db_qkv [3H],
+ * dW_o, db_o, dW_i, db_i, dW_f, db_f and the four LayerNorm vectors.  A NULL output pointer: that gradient is not wanted
+ * and its product is not launched.  Layers L-1 .. 0; per layer LayerNorm 2, FFN-out, GELU, FFN-in, LayerNorm 1, attention
+ * output, attention, QKV.  Every dense product is exact fp32 on existing entry points: gnnrag_linear on a transposed copy
+ * of the weight (the residual's gradient in its add epilogue), gnnrag_gemm_tn for the weights, 8-slice column sums for the
+ * biases and LayerNorm vectors.  The key third of db_qkv is written as exactly +0: every row of dS sums to zero, so that
+ * gradient is mathematically zero and autograd leaves rounding residue there; dW_qkv and g_x0 keep their key terms.
+ * The attention step recomputes the probabilities from qkv (nothing [T,T] is stored by the forward); one workgroup per
+ * (question, head), no atomics: a wave owns a query row for dQ, the owner of key j sums dK_j and dV_j over the query rows
+ * in ascending order; a query row whose keys are all dropped gives a zero dQ row and adds nothing to dK, dV.
+ * Workspace: gnnrag_bert_layers_backward_workspace_bytes(B, T, H, heads, I) (0 for a shape outside the rules; like
+ * gnnrag_gemm_tn_workspace_bytes it depends on the current device).  fp32 throughout, nothing allocated, nothing waits for
+ * the stream, a second call gives the same bits, the rows of g_x0 of a question do not depend on the batch around it.
+ * Rules of both calls, answered in this order before anything is launched: a size <= 0 (L <= 0 included) or an unknown
+ * math is GNNRAG_E_BADARG; then the shape rules whatever the pointers are: H % heads != 0, H / heads not in {32, 64}, T > 128,
+ * H % 4 != 0, I % 4 != 0 are GNNRAG_E_UNSUPPORTED; then a NULL among x0 / g_out, layers, out, reserve, ws or a needed layer
+ * pointer, or a scale of a given mask that is not finite and > 0, is GNNRAG_E_BADARG; then a pointer that is not 16-byte
+ * aligned (keep_hidden: 4) is GNNRAG_E_UNSUPPORTED; then a reserve or workspace below the stated size is GNNRAG_E_WORKSPACE.
+ *
+ * The three kernels alone (tests): gnnrag_bert_attention_backward (d_qkv [M,3H] fully written; ws of
+ * gnnrag_bert_attention_backward_workspace_bytes(B, T, heads) = B heads 2 T T 4 bytes), gnnrag_bert_ln_backward (the row is
+ * rebuilt as d m + res with keep given - res and dY are then required, dY = dz m - and as d without; summ [M,H] receives
+ * dy xhat; dgamma / dbeta [H] or NULL are its and dy's column sums) and gnnrag_bert_gelu_backward (d_pre = d_act gelu'(pre),
+ * gelu' = Phi(x) + x phi(x) with Phi by erf; d_pre may be d_act; act [n] or NULL receives gelu(pre)). */
+typedef struct gnnrag_bert_layer_grads { float *dW_qkv, *db_qkv, *dW_o, *db_o, *dln1_g, *dln1_b,
+                                               *dW_i, *db_i, *dW_f, *db_f, *dln2_g, *dln2_b; } gnnrag_bert_layer_grads;
+size_t gnnrag_bert_reserve_bytes(int32_t L, int32_t B, int32_t T, int32_t H, int32_t I);
+int gnnrag_bert_layers_forward_save(const float* x0 /* [B T,H] */, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
+                                    int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
+                                    const uint8_t* keep_hidden /* or NULL */, float scale_hidden,
+                                    const uint8_t* keep_att /* or NULL */, float scale_att, float* out /* [B T,H] */,
+                                    void* reserve, size_t reserve_bytes, void* ws, size_t ws_bytes, int32_t math,
+                                    gnnrag_stream_t stream);
+size_t gnnrag_bert_layers_backward_workspace_bytes(int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I);
+int gnnrag_bert_layers_backward(const float* g_out /* [B T,H] */, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
+                                int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
+                                const uint8_t* keep_hidden /* or NULL */, float scale_hidden,
+                                const uint8_t* keep_att /* or NULL */, float scale_att, const void* reserve,
+                                size_t reserve_bytes, float* g_x0 /* [B T,H] or NULL */,
+                                const gnnrag_bert_layer_grads* grads /* or NULL */, void* ws, size_t ws_bytes,
+                                gnnrag_stream_t stream);
+size_t gnnrag_bert_attention_backward_workspace_bytes(int32_t B, int32_t T, int32_t heads);
+int gnnrag_bert_attention_backward(const float* qkv, const float* d_ctx, int32_t B, int32_t T, int32_t heads, int32_t dh,
+                                   const uint8_t* keep /* [B,heads,T,T] or NULL */, float scale, float* d_qkv, void* ws,
+                                   size_t ws_bytes, gnnrag_stream_t stream);
+int gnnrag_bert_ln_backward(const float* dy, const float* d, const uint8_t* keep /* or NULL */, float scale,
+                            const float* res /* or NULL */, const float* g, float eps, int64_t M, int32_t H, float* dz,
+                            float* dY /* or NULL */, float* summ, float* dgamma /* or NULL */, float* dbeta /* or NULL */,
+                            gnnrag_stream_t stream);
+int gnnrag_bert_gelu_backward(const float* pre, const float* d_act, int64_t n, float* d_pre, float* act /* or NULL */,
+                              gnnrag_stream_t stream);
+
 /* ---- Split-K linear for few rows, and the inference encoder on it (additive to ABI 16) ------------
  * C = epilogue(A W^T + bias): A [M, K], W [Nout, K], bias [Nout] or NULL, C [M, Nout], all fp32.  K is cut into `splits`
  * chunks of k_chunk (the last may be short); the first launch writes the chunks' partial products P[s] [M, Nout] into the

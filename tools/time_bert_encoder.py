@@ -8,6 +8,8 @@
     python tools/time_bert_encoder.py --train [--arch bert|roberta|mpnet]
     python tools/time_bert_encoder.py --splitk [--arch bert|roberta] [--kernel]
                                       [--out profiles/bert_encoder_splitk_time.jsonl]
+    python tools/time_bert_encoder.py --finetune [--arch bert|roberta]
+                                      [--out profiles/bert_encoder_finetune_time.jsonl]
 
 * the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
   tests/bert_oracle.py - the real all-MiniLM-L6-v2 weights are not needed for a timing) in eval mode, ``enc(ids)[0]`` on a
@@ -36,6 +38,12 @@ numbers decide.  ``--splitk --kernel``: device time of
 MiniLM and the 768-wide shape, 20 calls per graph - ``ops.linear`` (the product alone; its GELU or LayerNorm is one more
 launch in the encode) against ``ops.linear_splitk`` (the product, the reduce and the epilogue) at the library's ``splits``,
 and at (1, 12) a sweep over forced ``splits`` with the bytes of W over the time beside it.
+
+``--finetune``: forward + backward of the UNFROZEN encoder alone (the reference's ``--lm_frozen 0``) in training mode at
+transformers' dropout 0.1: ``out = enc(ids)[0]; out.backward(g)`` with every parameter requiring grad and the gradients
+cleared before each iteration, ``GNNRAG_HIP_LM=1`` in both legs and ``GNNRAG_HIP_LM_FINETUNE`` off (transformers and torch
+autograd) and on (transformers' embedding stage, the layers on ``gnnrag_bert_layers_forward_save`` /
+``gnnrag_bert_layers_backward``), each in a process of its own; the same shapes, host enqueue and stream time of the pair.
 
 ``--kernel``: ``gnnrag_bert_attention`` alone, 20 calls per graph, per library given in ``--libs`` as ``label=path``
 (``GNNRAG_LIB``; empty path = the built library): how the workgroup size (``-DGNNRAG_BERT_ATT_THREADS``,
@@ -195,6 +203,51 @@ def child_encode(a):
                             "in the reference's data loader; it cannot be built offline"}), flush=True)
 
 
+def child_finetune(a):
+    torch, bo, dev = _setup()
+    import numpy as np
+    from gnnrag_amd.modules.question_encoding.lm_encoder import finetune_enabled, patch_lm_encoder
+    on = finetune_enabled()
+    if a.arch == "bert":
+        shape, n_layers, vocab = bo.MINILM, L, VOCAB
+        enc = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)[0]
+    else:
+        import lm_variants_oracle as lo
+        shape, n_layers, vocab = BASE, BASE_L, BASE_VOCAB[a.arch]
+        enc = lo.model_class(a.arch)(lo.config(a.arch, L=BASE_L, vocab=vocab, max_pos=BASE_MAX_POS, **BASE))
+    enc = enc.to(dev).train()
+    patch_lm_encoder(_Holder(enc))
+    patch = enc._gnnrag_lm_patch
+    for B, T in SHAPES:
+        ids0 = np.random.RandomState(B).randint(0 if a.arch == "bert" else 2, vocab, (B, T))
+        if a.arch != "bert":
+            ids0[1::2, T // 2:] = 1             # every second question padded from the middle (pad id 1)
+        ids0 = torch.from_numpy(ids0).long().to(dev)
+        g = torch.randn(B, T, shape["H"], device=dev)
+        before = patch.hip_finetune_calls
+        host, ev = [], []
+        for it in range(a.warm + a.iters):
+            x = ids0.clone()
+            enc.zero_grad(set_to_none=True)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            t0 = time.perf_counter()
+            enc(x)[0].backward(g)
+            t1 = time.perf_counter()
+            e1.record()
+            e1.synchronize()
+            if it >= a.warm:
+                host.append((t1 - t0) * 1e3)
+                ev.append(e0.elapsed_time(e1))
+        rec = {"what": "finetune_fwd_bwd", "arch": a.arch, "switch": "on" if on else "off", "B": B, "T": T, "L": n_layers,
+               "H": shape["H"], "I": shape["I"], "host_ms": _median(host), "event_ms": _median(ev), "host_ms_min": min(host),
+               "event_ms_min": min(ev), "iters": a.iters, "warm": a.warm, "dropout": float(enc.config.hidden_dropout_prob),
+               "hip_finetune_calls_per_encode": (patch.hip_finetune_calls - before) / (a.warm + a.iters),
+               "device": torch.cuda.get_device_name(0)}
+        print(TAG + json.dumps(rec), flush=True)
+
+
 def child_kernel(a):
     torch, bo, dev = _setup()
     from gnnrag_amd import ops
@@ -280,20 +333,34 @@ def main():
     ap.add_argument("--kernel", action="store_true")
     ap.add_argument("--train", action="store_true", help="training mode at dropout 0.1: GNNRAG_HIP_LM_TRAIN off / on")
     ap.add_argument("--splitk", action="store_true", help="inference: GNNRAG_HIP_LM_SPLITK off / on; with --kernel the products")
+    ap.add_argument("--finetune", action="store_true",
+                    help="unfrozen, training mode, forward + backward: GNNRAG_HIP_LM_FINETUNE off / on")
     ap.add_argument("--libs", default="256=")
     ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--child", choices=["encode", "kernel", "splitk_kernel"])
+    ap.add_argument("--child", choices=["encode", "kernel", "splitk_kernel", "finetune"])
     ap.add_argument("--label", default="")
     a = ap.parse_args()
     if a.child:
-        return {"encode": child_encode, "kernel": child_kernel, "splitk_kernel": child_splitk_kernel}[a.child](a)
+        return {"encode": child_encode, "kernel": child_kernel, "splitk_kernel": child_splitk_kernel,
+                "finetune": child_finetune}[a.child](a)
+    if a.finetune and a.arch == "mpnet":
+        raise SystemExit("--finetune: MPNetModel keeps transformers' forward in both legs, there is nothing to compare")
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "bert_encoder_splitk_time.jsonl" if a.splitk else "bert_encoder_time.jsonl")
+        a.out = os.path.join(REPO, "profiles", "bert_encoder_finetune_time.jsonl" if a.finetune else
+                             "bert_encoder_splitk_time.jsonl" if a.splitk else "bert_encoder_time.jsonl")
     common = (["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch] + (["--train"] if a.train else []) +
               (["--splitk"] if a.splitk else []))
     lines = []
-    if a.splitk and a.kernel:
+    if a.finetune:
+        for rnd in range(a.rounds):
+            for switch in ("0", "1"):
+                before = len(lines)
+                _spawn(["--child", "finetune"] + common, {"GNNRAG_HIP_LM": "1", "GNNRAG_HIP_LM_FINETUNE": switch}, lines,
+                       a.limit)
+                for rec in lines[before:]:
+                    rec["round"] = rnd
+    elif a.splitk and a.kernel:
         _spawn(["--child", "splitk_kernel"] + common, {}, lines, a.limit)
     elif a.splitk:
         for rnd in range(a.rounds):
