@@ -34,8 +34,7 @@
 // call returns the same bits, and a question's rows never depend on the batch around it (LayerNorm: a wave per row;
 // attention: a workgroup per (question, head); the dense products: a row of C depends on its row of A only).
 #include "bert_device.h"
-#include "bert_reserve.h"
-#include "gnnrag_common.h"
+#include "bert_host.h"
 
 #ifndef GNNRAG_BERT_ATT_THREADS
 #define GNNRAG_BERT_ATT_THREADS 512  // 64 .. 1024, a multiple of 64; never changes a result
@@ -43,9 +42,7 @@
 
 namespace gnnrag {
 
-constexpr int kBertMaxT = 128;       // keys per question: two per lane
-constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
-
+// kBertMaxT, kBertLnRows and the entry points' shape, scale and pointer rules: bert_host.h
 // bert_keep4, bert_ln_row (the LayerNorm of one row by one wave) and bert_gelu: bert_device.h
 
 // x[row] = LN(word_emb[id] + pos_emb[pos] + type_emb[0]); an id outside [0, vocab) reads nothing: its row is NaN.
@@ -272,10 +269,6 @@ static int bert_attention_launch(const float* qkv, const float* rel_bias, const 
                   : bert_attention_launch_dh<64>(qkv, rel_bias, keep, keep_scale, B, T, heads, ctx, stream);
 }
 
-static inline bool bert_att_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {
-  return (dh == 32 || dh == 64) && T >= 1 && T <= kBertMaxT && heads >= 1 && B >= 1 && B * heads < ((int64_t)1 << 31);
-}
-
 // the workspace: qkv [M, 3H], ctx [M, H], sum [M, H] (dense + residual, the LayerNorm's input), ffn [M, I]; each block
 // starts on a 256-byte boundary
 struct BertWs {
@@ -317,6 +310,62 @@ static inline BertSplitkWs bert_splitk_ws(int64_t M, int32_t H, int32_t I) {
   return w;
 }
 
+// where one layer's values go.  pre == ffn: the GELU runs in place on the product's output (no copy); xin / x1 NULL: the
+// layer's input and LayerNorm 1's output are not kept.
+struct BertLayerDst {
+  float *qkv, *ctx, *sum1, *sum2, *pre, *ffn, *xin, *x1;
+};
+
+// The L layers on the running buffer `out` [M, H]: the one layer sequence of every entry point but the split-K one.
+// dst_of(l) names layer l's destinations.  With workspace blocks, pre == ffn and no save slots these are the eight
+// launches per layer of the inference and training forward; the saving forward points the products into its reserve and
+// gets three device copies on top, each in front of the launch that overwrites what it keeps: xin before the QKV product,
+// x1 behind LayerNorm 1, pre -> ffn before the GELU.  The same kernels on the same values in the same order either way:
+// equal bits in `out`.
+template <typename DstOf>
+static int bert_layers_run(int32_t L, const gnnrag_bert_layer* layers, const float* rel_bias, float ln_eps, int32_t B,
+                           int32_t T, int32_t H, int32_t heads, int32_t I, const BertKeep& keep, float scale_hidden,
+                           float scale_att, float* out, DstOf dst_of, int32_t math, gnnrag_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t M = (int64_t)B * T;
+  const int32_t dh = H / heads;
+  const int H4 = H / 4;
+  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
+  const size_t n_ffn = (size_t)M * I, mh = (size_t)M * H * sizeof(float);
+  const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
+  const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
+  // x = LN(dense(a) + b + x).  Inference: the residual rides in the product's epilogue.  With hidden dropout the product
+  // goes without it and the LayerNorm launch drops, adds the residual and normalises (kp: the site's keep bytes).
+  auto residual_block = [&](const float* a, int32_t K, const float* W, const float* b, const float* g, const float* bt,
+                            const uint8_t* kp, float* sum) -> int {
+    if (kp) {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, nullptr, 0, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_drop_add_ln, ln_grid, ln_block, 0, st, sum, kp, scale_hidden, g, bt, ln_eps, (int)M, H4,
+                         out);
+    } else {
+      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, out, M, 0, sum, H, math, stream));
+      hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, g, bt, ln_eps, (int)M, H4, out);
+    }
+    GNNRAG_LAUNCH_CHECK();
+    return 0;
+  };
+  for (int l = 0; l < L; ++l) {
+    const gnnrag_bert_layer& p = layers[l];
+    const BertLayerDst d = dst_of(l);
+    if (d.xin) GNNRAG_HIP(hipMemcpyAsync(d.xin, out, mh, hipMemcpyDeviceToDevice, st));
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, d.qkv, 3 * H, math, stream));
+    GNNRAG_RC(bert_attention_launch(d.qkv, rel_bias, keep.probs(l), scale_att, B, T, heads, dh, d.ctx, st));
+    GNNRAG_RC(residual_block(d.ctx, H, p.W_o, p.b_o, p.ln1_g, p.ln1_b, keep.att_out(l), d.sum1));
+    if (d.x1) GNNRAG_HIP(hipMemcpyAsync(d.x1, out, mh, hipMemcpyDeviceToDevice, st));
+    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, d.pre, I, math, stream));
+    if (d.pre != d.ffn) GNNRAG_HIP(hipMemcpyAsync(d.ffn, d.pre, n_ffn * sizeof(float), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, d.ffn, n_ffn);
+    GNNRAG_LAUNCH_CHECK();
+    GNNRAG_RC(residual_block(d.ffn, I, p.W_f, p.b_f, p.ln2_g, p.ln2_b, keep.ffn_out(l), d.sum2));
+  }
+  return 0;
+}
+
 }  // namespace gnnrag
 
 using namespace gnnrag;
@@ -330,9 +379,6 @@ extern "C" size_t gnnrag_bert_splitk_workspace_bytes(int32_t B, int32_t T, int32
   if (B <= 0 || T <= 0 || H <= 0 || I <= 0 || (int64_t)3 * H > INT32_MAX) return 0;
   return bert_splitk_ws((int64_t)B * T, H, I).total;
 }
-
-// the scale of a mask that is given: finite and > 0 (1 / (1 - p) of a p < 1)
-static inline bool bert_scale_ok(const uint8_t* keep, float scale) { return !keep || (std::isfinite(scale) && scale > 0.f); }
 
 extern "C" size_t gnnrag_bert_keep_hidden_bytes(int32_t L, int32_t B, int32_t T, int32_t H) {
   if (L < 0 || B <= 0 || T <= 0 || H <= 0) return 0;      // L = 0 is legal: plane 0 alone
@@ -364,9 +410,10 @@ extern "C" int gnnrag_bert_attention(const float* qkv, int32_t B, int32_t T, int
   return gnnrag_bert_attention_bias(qkv, B, T, heads, dh, nullptr, ctx, stream);
 }
 
-// all entry points; need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type term".
-// keep_hidden / keep_att NULL: that dropout site keeps the inference sequence (its scale is not read); both NULL is the
-// inference call, launch for launch.
+// all encode entry points: the argument rules, the embedding launch, then the layers on bert_layers_run with every
+// destination in the workspace.  need_type: a NULL type_emb is an argument error (gnnrag_bert_encode), not "no token-type
+// term".  keep_hidden / keep_att NULL: that dropout site keeps the inference sequence (its scale is not read); both NULL
+// is the inference call, launch for launch.
 // splitk (inference only, both keeps NULL): the four products of a layer on gnnrag_linear_splitk, the GELU and the two
 // LayerNorms in its reduce; the embedding and attention launches are the same.
 static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
@@ -400,15 +447,7 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   if (!aligned16(word_emb, pos_emb, type_emb, rel_bias, ln_g, ln_b, out) || ((uintptr_t)ids & 7) ||
       (L > 0 && !aligned16(ws)) || ((uintptr_t)keep_hidden & 3))
     return GNNRAG_E_UNSUPPORTED;
-  for (int l = 0; l < L; ++l) {
-    const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
-                                layers[l].ln1_g, layers[l].ln1_b, layers[l].W_i,   layers[l].b_i,
-                                layers[l].W_f,   layers[l].b_f,   layers[l].ln2_g, layers[l].ln2_b};
-    for (int i = 0; i < 12; ++i)
-      if (!p[i]) return GNNRAG_E_BADARG;
-    for (int i = 0; i < 12; ++i)
-      if (!aligned16(p[i])) return GNNRAG_E_UNSUPPORTED;
-  }
+  for (int l = 0; l < L; ++l) GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsAll));
 
   hipStream_t st = (hipStream_t)stream;
   const int H4 = H / 4;
@@ -455,43 +494,13 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
     return 0;
   }
 
-  float* qkv = (float*)((char*)ws + w.qkv);
-  float* ctx = (float*)((char*)ws + w.ctx);
-  float* sum = (float*)((char*)ws + w.sum);
-  float* ffn = (float*)((char*)ws + w.ffn);
-  const size_t n_ffn = (size_t)M * I;
-  const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
-  const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
-  const size_t plane = (size_t)M * H, att_plane = (size_t)B * heads * T * T;
-  // x = LN(dense(a) + b + x).  Inference: the residual rides in the product's epilogue.  With hidden dropout the product
-  // goes without it and the LayerNorm launch drops, adds the residual and normalises (plane: the site's keep bytes).
-  auto residual_block = [&](const float* a, int32_t K, const float* W, const float* b, const float* g, const float* bt,
-                            const uint8_t* keep) -> int {
-    if (keep) {
-      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, nullptr, 0, 0, sum, H, math, stream));
-      hipLaunchKernelGGL(k_bert_drop_add_ln, ln_grid, ln_block, 0, st, sum, keep, scale_hidden, g, bt, ln_eps, (int)M, H4,
-                         out);
-    } else {
-      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, out, M, 0, sum, H, math, stream));
-      hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, g, bt, ln_eps, (int)M, H4, out);
-    }
-    GNNRAG_LAUNCH_CHECK();
-    return 0;
-  };
-  for (int l = 0; l < L; ++l) {
-    const gnnrag_bert_layer& p = layers[l];
-    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
-    GNNRAG_RC(bert_attention_launch(qkv, rel_bias, keep_att ? keep_att + (size_t)l * att_plane : nullptr, scale_att, B, T,
-                                    heads, dh, ctx, st));
-    GNNRAG_RC(residual_block(ctx, H, p.W_o, p.b_o, p.ln1_g, p.ln1_b,
-                             keep_hidden ? keep_hidden + (size_t)(1 + 2 * l) * plane : nullptr));
-    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, ffn, I, math, stream));
-    hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, ffn, n_ffn);
-    GNNRAG_LAUNCH_CHECK();
-    GNNRAG_RC(residual_block(ffn, I, p.W_f, p.b_f, p.ln2_g, p.ln2_b,
-                             keep_hidden ? keep_hidden + (size_t)(2 + 2 * l) * plane : nullptr));
-  }
-  return 0;
+  // one set of workspace blocks for every layer, the GELU in place, nothing saved
+  char* wsb = (char*)ws;
+  float* sum = (float*)(wsb + w.sum);
+  float* ffn = (float*)(wsb + w.ffn);
+  const BertLayerDst d{(float*)(wsb + w.qkv), (float*)(wsb + w.ctx), sum, sum, ffn, ffn, nullptr, nullptr};
+  return bert_layers_run(L, layers, rel_bias, ln_eps, B, T, H, heads, I, BertKeep(keep_hidden, keep_att, B, T, H, heads),
+                         scale_hidden, scale_att, out, [&](int) { return d; }, math, stream);
 }
 
 extern "C" int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
@@ -540,10 +549,10 @@ extern "C" size_t gnnrag_bert_reserve_bytes(int32_t L, int32_t B, int32_t T, int
   return (size_t)L * bert_reserve((int64_t)B * T, H, I).layer;
 }
 
-// The L layers of bert_encode_run on a caller-given x0, launch for launch (the same kernels on the same values in the same
-// order: equal bits), with the values the backward needs left in the reserve (bert_reserve.h) instead of the workspace:
-// the products write their blocks of the reserve directly; the layer input, LayerNorm 1's output and the FFN
-// pre-activation are kept by a device copy in front of the launch that overwrites the running buffer.
+// bert_layers_run - the layer loop bert_encode_run calls - on a caller-given x0, with the values the backward needs left in
+// the reserve (bert_reserve.h) instead of the workspace: the products write their blocks of the reserve directly; the
+// layer input, LayerNorm 1's output and the FFN pre-activation go to its save slots.  No relative attention bias.  Its own
+// argument rules: a short reserve or workspace is GNNRAG_E_WORKSPACE, behind every pointer rule.
 extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
                                                int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
                                                const uint8_t* keep_hidden, float scale_hidden, const uint8_t* keep_att,
@@ -560,59 +569,17 @@ extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const
   if (!x0 || !layers || !out || !reserve || !ws) return GNNRAG_E_BADARG;
   if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
   if (!aligned16(x0, out, reserve, ws) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
-  for (int l = 0; l < L; ++l) {
-    const float* const p[12] = {layers[l].W_qkv, layers[l].b_qkv, layers[l].W_o,   layers[l].b_o,
-                                layers[l].ln1_g, layers[l].ln1_b, layers[l].W_i,   layers[l].b_i,
-                                layers[l].W_f,   layers[l].b_f,   layers[l].ln2_g, layers[l].ln2_b};
-    for (int i = 0; i < 12; ++i)
-      if (!p[i]) return GNNRAG_E_BADARG;
-    for (int i = 0; i < 12; ++i)
-      if (!aligned16(p[i])) return GNNRAG_E_UNSUPPORTED;
-  }
+  for (int l = 0; l < L; ++l) GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsAll));
   if (reserve_bytes < (size_t)L * r.layer || ws_bytes < w.total) return GNNRAG_E_WORKSPACE;
 
-  hipStream_t st = (hipStream_t)stream;
-  const int H4 = H / 4;
-  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
+  if (out != x0)
+    GNNRAG_HIP(hipMemcpyAsync(out, x0, (size_t)M * H * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   float* ffn = (float*)((char*)ws + w.ffn);
-  const size_t n_ffn = (size_t)M * I;
-  const size_t gelu_blocks = (n_ffn / 4 + 255) / 256;
-  const dim3 gelu_grid((unsigned)(gelu_blocks < 1 ? 1 : gelu_blocks > 65536 ? 65536 : gelu_blocks));
-  const size_t plane = (size_t)M * H, att_plane = (size_t)B * heads * T * T;
-  const size_t mh = plane * sizeof(float);
-  auto residual_block = [&](const float* a, int32_t K, const float* W, const float* b, const float* g, const float* bt,
-                            const uint8_t* keep, float* sum) -> int {
-    if (keep) {
-      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, nullptr, 0, 0, sum, H, math, stream));
-      hipLaunchKernelGGL(k_bert_drop_add_ln, ln_grid, ln_block, 0, st, sum, keep, scale_hidden, g, bt, ln_eps, (int)M, H4,
-                         out);
-    } else {
-      GNNRAG_RC(gnnrag_linear(a, M, K, W, b, out, M, 0, sum, H, math, stream));
-      hipLaunchKernelGGL(k_bert_add_ln, ln_grid, ln_block, 0, st, sum, g, bt, ln_eps, (int)M, H4, out);
-    }
-    GNNRAG_LAUNCH_CHECK();
-    return 0;
-  };
-  if (out != x0) GNNRAG_HIP(hipMemcpyAsync(out, x0, mh, hipMemcpyDeviceToDevice, st));
-  for (int l = 0; l < L; ++l) {
-    const gnnrag_bert_layer& p = layers[l];
+  auto dst_of = [&](int l) {
     char* rl = (char*)reserve + (size_t)l * r.layer;
-    float* qkv = (float*)(rl + r.qkv);
-    float* ctx = (float*)(rl + r.ctx);
-    float* pre = (float*)(rl + r.pre);
-    GNNRAG_HIP(hipMemcpyAsync(rl + r.xin, out, mh, hipMemcpyDeviceToDevice, st));
-    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_qkv, p.b_qkv, nullptr, 0, 0, qkv, 3 * H, math, stream));
-    GNNRAG_RC(bert_attention_launch(qkv, nullptr, keep_att ? keep_att + (size_t)l * att_plane : nullptr, scale_att, B, T,
-                                    heads, dh, ctx, st));
-    GNNRAG_RC(residual_block(ctx, H, p.W_o, p.b_o, p.ln1_g, p.ln1_b,
-                             keep_hidden ? keep_hidden + (size_t)(1 + 2 * l) * plane : nullptr, (float*)(rl + r.sum1)));
-    GNNRAG_HIP(hipMemcpyAsync(rl + r.x1, out, mh, hipMemcpyDeviceToDevice, st));
-    GNNRAG_RC(gnnrag_linear(out, M, H, p.W_i, p.b_i, nullptr, 0, 0, pre, I, math, stream));
-    GNNRAG_HIP(hipMemcpyAsync(ffn, pre, n_ffn * sizeof(float), hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(k_bert_gelu, gelu_grid, dim3(256), 0, st, ffn, n_ffn);
-    GNNRAG_LAUNCH_CHECK();
-    GNNRAG_RC(residual_block(ffn, I, p.W_f, p.b_f, p.ln2_g, p.ln2_b,
-                             keep_hidden ? keep_hidden + (size_t)(2 + 2 * l) * plane : nullptr, (float*)(rl + r.sum2)));
-  }
-  return 0;
+    return BertLayerDst{(float*)(rl + r.qkv), (float*)(rl + r.ctx), (float*)(rl + r.sum1), (float*)(rl + r.sum2),
+                        (float*)(rl + r.pre), ffn,                  (float*)(rl + r.xin),  (float*)(rl + r.x1)};
+  };
+  return bert_layers_run(L, layers, nullptr, ln_eps, B, T, H, heads, I, BertKeep(keep_hidden, keep_att, B, T, H, heads),
+                         scale_hidden, scale_att, out, dst_of, math, stream);
 }

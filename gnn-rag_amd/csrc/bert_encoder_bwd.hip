@@ -19,8 +19,7 @@
 // the rows of g_x0 of a question depend on that question's rows only (LayerNorm: a wave per row; attention: a workgroup
 // per (question, head); the products: a row of C depends on its row of A only).
 #include "bert_device.h"
-#include "bert_reserve.h"
-#include "gnnrag_common.h"
+#include "bert_host.h"
 
 #ifndef GNNRAG_BERT_ATT_BWD_THREADS
 #define GNNRAG_BERT_ATT_BWD_THREADS 512  // 64 .. 1024, a multiple of 64; decides who owns a row, never a summation order
@@ -28,8 +27,7 @@
 
 namespace gnnrag {
 
-constexpr int kBertMaxT = 128;       // keys per question: two per lane (bert_encoder.hip)
-constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels (bert_encoder.hip)
+// kBertMaxT, kBertLnRows and the entry points' shape, scale and pointer rules: bert_host.h
 
 // LayerNorm backward of one row by one wave.  The row is rebuilt as the forward formed it: DROP: z = d m + res (d the
 // dense output without the residual, m from the keep bytes); else z = d (dense + residual).  Statistics as bert_ln_row
@@ -268,11 +266,6 @@ static inline size_t bert_att_bwd_scratch_bytes(int64_t B, int32_t T, int32_t he
   return (size_t)B * heads * 2 * T * T * sizeof(float);
 }
 
-// the shape rules of bert_att_shape_ok (bert_encoder.hip)
-static inline bool bert_att_bwd_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {
-  return (dh == 32 || dh == 64) && T >= 1 && T <= kBertMaxT && heads >= 1 && B >= 1 && B * heads < ((int64_t)1 << 31);
-}
-
 template <int DH, bool DROP>
 static int bert_attention_bwd_launch_as(const float* qkv, const float* dctx, const uint8_t* keep, float keep_scale,
                                         int32_t B, int32_t T, int32_t heads, float* dqkv, float* sq, hipStream_t stream) {
@@ -376,11 +369,7 @@ static inline BertBwdWs bert_bwd_ws(int64_t B, int32_t T, int32_t H, int32_t hea
 
 static inline bool bert_bwd_shape_ok(int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I) {
   if (H % heads != 0 || (H & 3) || (I & 3) || (int64_t)3 * H > INT32_MAX) return false;
-  return bert_att_bwd_shape_ok(B, T, heads, H / heads) && (int64_t)B * T < ((int64_t)1 << 31);
-}
-
-static inline bool bert_bwd_scale_ok(const uint8_t* keep, float scale) {
-  return !keep || (std::isfinite(scale) && scale > 0.f);
+  return bert_att_shape_ok(B, T, heads, H / heads) && (int64_t)B * T < ((int64_t)1 << 31);
 }
 
 }  // namespace gnnrag
@@ -396,8 +385,8 @@ extern "C" int gnnrag_bert_attention_backward(const float* qkv, const float* d_c
                                               int32_t dh, const uint8_t* keep, float scale, float* d_qkv, void* ws,
                                               size_t ws_bytes, gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
-  if (!bert_att_bwd_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
-  if (!qkv || !d_ctx || !d_qkv || !ws || !bert_bwd_scale_ok(keep, scale)) return GNNRAG_E_BADARG;
+  if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
+  if (!qkv || !d_ctx || !d_qkv || !ws || !bert_scale_ok(keep, scale)) return GNNRAG_E_BADARG;
   if (!aligned16(qkv, d_ctx, d_qkv, ws)) return GNNRAG_E_UNSUPPORTED;
   if (ws_bytes < bert_att_bwd_scratch_bytes(B, T, heads)) return GNNRAG_E_WORKSPACE;
   return bert_attention_bwd_launch(qkv, d_ctx, keep, scale, B, T, heads, dh, d_qkv, (float*)ws, (hipStream_t)stream);
@@ -408,7 +397,7 @@ extern "C" int gnnrag_bert_ln_backward(const float* dy, const float* d, const ui
                                        float* dgamma, float* dbeta, gnnrag_stream_t stream) {
   if (M <= 0 || H <= 0) return GNNRAG_E_BADARG;
   if ((H & 3) || M >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
-  if (!dy || !d || !g || !dz || !summ || (keep && (!res || !dY)) || !bert_bwd_scale_ok(keep, scale))
+  if (!dy || !d || !g || !dz || !summ || (keep && (!res || !dY)) || !bert_scale_ok(keep, scale))
     return GNNRAG_E_BADARG;
   if (!aligned16(dy, d, res, g, dz, dY, summ) || ((uintptr_t)keep & 3)) return GNNRAG_E_UNSUPPORTED;
   GNNRAG_RC(bert_ln_bwd_launch(dy, d, keep, scale, res, g, eps, M, H, dz, dY, summ, (hipStream_t)stream));
@@ -436,15 +425,10 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L <= 0) return GNNRAG_E_BADARG;
   if (!bert_bwd_shape_ok(B, T, H, heads, I)) return GNNRAG_E_UNSUPPORTED;
   if (!g_out || !layers || !reserve || !ws) return GNNRAG_E_BADARG;
-  if (!bert_bwd_scale_ok(keep_hidden, scale_hidden) || !bert_bwd_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
+  if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
   if (!aligned16(g_out, reserve, g_x0, ws) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) {
-    const float* const p[6] = {layers[l].W_qkv, layers[l].W_o, layers[l].ln1_g, layers[l].W_i, layers[l].W_f,
-                               layers[l].ln2_g};
-    for (int i = 0; i < 6; ++i)
-      if (!p[i]) return GNNRAG_E_BADARG;
-    for (int i = 0; i < 6; ++i)
-      if (!aligned16(p[i])) return GNNRAG_E_UNSUPPORTED;
+    GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsBwd));      // the biases are not read: NULL is legal
     if (grads) {
       const gnnrag_bert_layer_grads& o = grads[l];
       if (!aligned16(o.dW_qkv, o.db_qkv, o.dW_o, o.db_o, o.dW_i, o.db_i, o.dW_f, o.db_f)) return GNNRAG_E_UNSUPPORTED;
@@ -470,7 +454,7 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
   float* att = (float*)(wsb + w.att);
   void* tn = wsb + w.tn;
   const int32_t dh = H / heads;
-  const size_t plane = (size_t)M * H, att_plane = (size_t)B * heads * T * T;
+  const BertKeep keep(keep_hidden, keep_att, B, T, H, heads);
   const gnnrag_bert_layer_grads none{};
   const float* g = g_out;
   for (int l = L - 1; l >= 0; --l) {
@@ -484,8 +468,7 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
     const float* x1 = (const float*)(rl + r.x1);
     const float* pre = (const float*)(rl + r.pre);
     const float* sum2 = (const float*)(rl + r.sum2);
-    const uint8_t* k1 = keep_hidden ? keep_hidden + (size_t)(1 + 2 * l) * plane : nullptr;
-    const uint8_t* k2 = keep_hidden ? keep_hidden + (size_t)(2 + 2 * l) * plane : nullptr;
+    const uint8_t *k1 = keep.att_out(l), *k2 = keep.ffn_out(l);
     const float* dY = keep_hidden ? dYb : dz;     // the gradient of a dense output in front of a LayerNorm
 
     // LayerNorm 2 and the FFN
@@ -508,8 +491,7 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
     GNNRAG_RC(bert_colsum2(dY, o.db_o, nullptr, nullptr, M, H, H, st));
     GNNRAG_RC(transpose_launch(p.W_o, wt, H, H, st));
     GNNRAG_RC(gnnrag_linear(dY, M, H, wt, nullptr, nullptr, 0, 0, dctx, H, GNNRAG_MATH_FP32, stream_));
-    GNNRAG_RC(bert_attention_bwd_launch(qkv, dctx, keep_att ? keep_att + (size_t)l * att_plane : nullptr, scale_att, B, T,
-                                        heads, dh, dqkv, att, st));
+    GNNRAG_RC(bert_attention_bwd_launch(qkv, dctx, keep.probs(l), scale_att, B, T, heads, dh, dqkv, att, st));
     if (o.dW_qkv) GNNRAG_RC(gnnrag_gemm_tn(dqkv, xin, M, 3 * H, H, o.dW_qkv, tn, w.tn_bytes, stream_));
     if (o.db_qkv) {
       // the query and value thirds; the key third is exactly +0

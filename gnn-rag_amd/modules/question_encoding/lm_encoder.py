@@ -242,17 +242,18 @@ class _LmPatch:
         return None
 
     # -- parameters -----------------------------------------------------------------------------------------------
-    def _projections(self, layer):
-        """(query, key, value, output projection, the LayerNorm behind it) of one layer."""
+    def _modules(self, layer):
+        """One layer's modules: (query, key, value, output projection, the LayerNorm behind it, intermediate dense, output
+        dense, the LayerNorm behind it) - the only place that knows a transformers layer's attribute names."""
         a = layer.attention
-        if self.arch == "MPNetModel":
-            return a.attn.q, a.attn.k, a.attn.v, a.attn.o, a.LayerNorm
-        return a.self.query, a.self.key, a.self.value, a.output.dense, a.output.LayerNorm
+        att = ((a.attn.q, a.attn.k, a.attn.v, a.attn.o, a.LayerNorm) if self.arch == "MPNetModel" else
+               (a.self.query, a.self.key, a.self.value, a.output.dense, a.output.LayerNorm))
+        return att + (layer.intermediate.dense, layer.output.dense, layer.output.LayerNorm)
 
     def _qkv_sources(self):
         out = []
         for layer in self.enc.encoder.layer:
-            q, k, v, _, _ = self._projections(layer)
+            q, k, v = self._modules(layer)[:3]
             out += [q.weight, k.weight, v.weight, q.bias, k.bias, v.bias]
         return out
 
@@ -270,13 +271,20 @@ class _LmPatch:
     def layers(self):
         out = []
         for layer, (W_qkv, b_qkv) in zip(self.enc.encoder.layer, self.packed_qkv()):
-            _, _, _, o, ln1 = self._projections(layer)
-            it, fo = layer.intermediate.dense, layer.output
+            o, ln1, it, fo, ln2 = self._modules(layer)[3:]
             out.append({"W_qkv": W_qkv, "b_qkv": b_qkv, "W_o": o.weight, "b_o": o.bias,
                         "ln1_g": ln1.weight, "ln1_b": ln1.bias, "W_i": it.weight, "b_i": it.bias,
-                        "W_f": fo.dense.weight, "b_f": fo.dense.bias, "ln2_g": fo.LayerNorm.weight,
-                        "ln2_b": fo.LayerNorm.bias})
+                        "W_f": fo.weight, "b_f": fo.bias, "ln2_g": ln2.weight, "ln2_b": ln2.bias})
         return out
+
+    def _draw(self, L, ids):
+        """``(p_hidden, p_att, keep_hidden, keep_att)`` of one call with active dropout: the configuration's two
+        probabilities and one :func:`draw_keep` for ``L`` layers on the device of ``ids``."""
+        cfg = self.enc.config
+        p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
+        keep_h, keep_a = draw_keep(L, int(ids.shape[0]), int(ids.shape[1]), int(cfg.hidden_size),
+                                   int(cfg.num_attention_heads), p_h, p_a, ids.device)
+        return p_h, p_a, keep_h, keep_a
 
     def rel_bias(self, T):
         """MPNet's bias table for ``T`` tokens (None for the other classes), kept until the weight changes."""
@@ -296,21 +304,17 @@ class _LmPatch:
         position rule), then the layers on ``autograd.BertLayersFn``."""
         from ... import autograd
         enc, cfg = self.enc, self.enc.config
-        B, T = int(ids.shape[0]), int(ids.shape[1])
-        L, H, heads = len(enc.encoder.layer), int(cfg.hidden_size), int(cfg.num_attention_heads)
         x0 = enc.embeddings(input_ids=ids)
-        keep_h, keep_a, p_h, p_a = None, None, 0.0, 0.0
+        p_h, p_a, keep_h, keep_a = 0.0, 0.0, None, None
         if self.dropout_active():
-            p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
-            keep_h, keep_a = draw_keep(L, B, T, H, heads, p_h, p_a, ids.device)     # plane 0 (the embedding's) is not read
+            p_h, p_a, keep_h, keep_a = self._draw(len(enc.encoder.layer), ids)      # plane 0 (the embedding's) is not read
         params = []
         for layer in enc.encoder.layer:
-            q, k, v, o, ln1 = self._projections(layer)
-            it, fo = layer.intermediate.dense, layer.output
+            q, k, v, o, ln1, it, fo, ln2 = self._modules(layer)
             params += [q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, o.weight, o.bias, ln1.weight, ln1.bias,
-                       it.weight, it.bias, fo.dense.weight, fo.dense.bias, fo.LayerNorm.weight, fo.LayerNorm.bias]
-        return autograd.BertLayersFn.apply(x0, keep_h, _scale(p_h), keep_a, _scale(p_a), heads, float(cfg.layer_norm_eps),
-                                           *params)
+                       it.weight, it.bias, fo.weight, fo.bias, ln2.weight, ln2.bias]
+        return autograd.BertLayersFn.apply(x0, keep_h, _scale(p_h), keep_a, _scale(p_a), int(cfg.num_attention_heads),
+                                           float(cfg.layer_norm_eps), *params)
 
     # -- the wrapper ----------------------------------------------------------------------------------------------
     def forward(self, *args, **kwargs):
@@ -331,9 +335,7 @@ class _LmPatch:
         rest = dict(I=int(cfg.intermediate_size), pad_id=self.pad_id(), rel_bias=self.rel_bias(int(ids.shape[1])))
         with torch.no_grad():
             if self.dropout_active():
-                p_h, p_a = float(cfg.hidden_dropout_prob), float(cfg.attention_probs_dropout_prob)
-                B, T = int(ids.shape[0]), int(ids.shape[1])
-                keep_h, keep_a = draw_keep(len(top[7]), B, T, int(cfg.hidden_size), top[8], p_h, p_a, ids.device)
+                p_h, p_a, keep_h, keep_a = self._draw(len(top[7]), ids)
                 hidden = ops.bert_encode_train(*top, keep_hidden=keep_h, scale_hidden=_scale(p_h), keep_att=keep_a,
                                                scale_att=_scale(p_a), **rest)
                 self.hip_train_calls += 1

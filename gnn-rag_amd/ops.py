@@ -2026,9 +2026,39 @@ def bert_encode_train(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, 
                         type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias)
 
 
+def _bert_layer_shapes(H: int, I: int):
+    return {"W_qkv": (3 * H, H), "b_qkv": (3 * H,), "W_o": (H, H), "b_o": (H,), "ln1_g": (H,), "ln1_b": (H,),
+            "W_i": (I, H), "b_i": (I,), "W_f": (H, I), "b_f": (H,), "ln2_g": (H,), "ln2_b": (H,)}
+
+
+def _bert_layer_array(layers, H: int, I: int):
+    """The host array of ``gnnrag_bert_layer`` structs and the tensors it points to (kept alive by the caller)."""
+    shapes, keep, arr = _bert_layer_shapes(H, I), [], (_lib.BertLayer * max(len(layers), 1))()
+    for l, layer in enumerate(layers):
+        for name in BERT_LAYER_FIELDS:
+            t = _chk(layer[name].detach(), "layers[%d].%s" % (l, name), shape=shapes[name])
+            keep.append(t)
+            setattr(arr[l], name, t.data_ptr())
+    return arr, keep
+
+
+def _bert_keep_args(L, B, T, H, heads, keep_hidden, scale_hidden, keep_att, scale_att):
+    """The two keep buffers against the shapes of ``bert_keep_shapes``, and the scales of those that are given (the scale
+    of a mask that is None goes on unchecked: the library does not read it)."""
+    shape_hidden, shape_att = bert_keep_shapes(L, B, T, H, heads)
+    if keep_hidden is not None:
+        keep_hidden = _chk(keep_hidden, "keep_hidden", dtype=torch.uint8, shape=shape_hidden)
+        scale_hidden = _keep_scale(scale_hidden, "scale_hidden")
+    if keep_att is not None:
+        keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
+        scale_att = _keep_scale(scale_att, "scale_att")
+    return keep_hidden, float(scale_hidden), keep_att, float(scale_att)
+
+
 def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, layers, heads, I, math, pad_id, rel_bias,
                  splitk=False):
-    """The shared body of ``bert_encode`` (``drop`` None) and ``bert_encode_train`` (``drop``: the two masks and scales)."""
+    """The shared body of ``bert_encode`` (``drop`` None) and ``bert_encode_train`` (``drop``: the two masks and scales):
+    one argument list, the entry point chosen by name."""
     lib = _lib.load()
     ids = _chk(ids, "ids", dtype=torch.int64)
     if ids.dim() != 2:
@@ -2052,52 +2082,29 @@ def _bert_encode(role, drop, ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps, 
         I = int(layers[0]["W_i"].shape[0])
     elif I is None:
         I = 4 * H
-    shapes = {"W_qkv": (3 * H, H), "b_qkv": (3 * H,), "W_o": (H, H), "b_o": (H,), "ln1_g": (H,), "ln1_b": (H,),
-              "W_i": (I, H), "b_i": (I,), "W_f": (H, I), "b_f": (H,), "ln2_g": (H,), "ln2_b": (H,)}
-    keep, arr = [], (_lib.BertLayer * max(L, 1))()
-    for l, layer in enumerate(layers):
-        for name in BERT_LAYER_FIELDS:
-            t = _chk(layer[name].detach(), "layers[%d].%s" % (l, name), shape=shapes[name])
-            keep.append(t)
-            setattr(arr[l], name, t.data_ptr())
+    arr, keep = _bert_layer_array(layers, H, I)
     dev = ids.device
     if drop is not None:
-        keep_hidden, scale_hidden, keep_att, scale_att = drop
-        shape_hidden, shape_att = bert_keep_shapes(L, B, T, H, heads)
-        if keep_hidden is not None:
-            keep_hidden = _chk(keep_hidden, "keep_hidden", dtype=torch.uint8, shape=shape_hidden)
-            scale_hidden = _keep_scale(scale_hidden, "scale_hidden")
-        if keep_att is not None:
-            keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
-            scale_att = _keep_scale(scale_att, "scale_att")
+        entry, drop = "gnnrag_bert_encode_train", _bert_keep_args(L, B, T, H, heads, *drop)
+    elif splitk:
+        entry = "gnnrag_bert_encode_splitk"
+    elif type_emb is not None and pad < 0 and rel_bias is None:
+        entry = "gnnrag_bert_encode"            # the call it has always been: it has no pad_id and no rel_bias argument
+    else:
+        entry = "gnnrag_bert_encode_ex"
     out = _buf((B, T, H), torch.float32, dev, role + ": out")
     nws = int((lib.gnnrag_bert_splitk_workspace_bytes if splitk else lib.gnnrag_bert_workspace_bytes)(B, T, H, I)) if L else 0
     ws = _buf((max(nws, 1),), torch.uint8, dev, role + ": workspace")
     with torch.cuda.device(dev):
+        args = [ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(), pos_emb.shape[0], _ptr(type_emb)]
+        if entry != "gnnrag_bert_encode":
+            args += [pad, _ptr(rel_bias)]
+        args += [ln_g.data_ptr(), ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I]
         if drop is not None:
-            _lib.check(lib.gnnrag_bert_encode_train(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
-                                                    pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
-                                                    ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I,
-                                                    _ptr(keep_hidden), float(scale_hidden), _ptr(keep_att),
-                                                    float(scale_att), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    _math(math), _stream()), "gnnrag_bert_encode_train")
-        elif splitk:
-            _lib.check(lib.gnnrag_bert_encode_splitk(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
-                                                     pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
-                                                     ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I, out.data_ptr(),
-                                                     ws.data_ptr(), nws, _math(math), _stream()),
-                       "gnnrag_bert_encode_splitk")
-        elif type_emb is not None and pad < 0 and rel_bias is None:
-            _lib.check(lib.gnnrag_bert_encode(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
-                                              pos_emb.shape[0], type_emb.data_ptr(), ln_g.data_ptr(), ln_b.data_ptr(),
-                                              float(eps), L, arr, B, T, H, heads, I, out.data_ptr(), ws.data_ptr(),
-                                              ws.numel(), _math(math), _stream()), "gnnrag_bert_encode")
-        else:
-            _lib.check(lib.gnnrag_bert_encode_ex(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
-                                                 pos_emb.shape[0], _ptr(type_emb), pad, _ptr(rel_bias), ln_g.data_ptr(),
-                                                 ln_b.data_ptr(), float(eps), L, arr, B, T, H, heads, I, out.data_ptr(),
-                                                 ws.data_ptr(), ws.numel(), _math(math), _stream()),
-                       "gnnrag_bert_encode_ex")
+            keep_hidden, scale_hidden, keep_att, scale_att = drop
+            args += [_ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att]
+        args += [out.data_ptr(), ws.data_ptr(), nws if splitk else ws.numel(), _math(math), _stream()]
+        _lib.check(getattr(lib, entry)(*args), entry)
     return out
 
 
@@ -2111,22 +2118,6 @@ def bert_layers_backward_supported(T: int, H: int, heads: int, I: int) -> bool:
             H // heads in (32, 64))
 
 
-def _bert_layer_shapes(H: int, I: int):
-    return {"W_qkv": (3 * H, H), "b_qkv": (3 * H,), "W_o": (H, H), "b_o": (H,), "ln1_g": (H,), "ln1_b": (H,),
-            "W_i": (I, H), "b_i": (I,), "W_f": (H, I), "b_f": (H,), "ln2_g": (H,), "ln2_b": (H,)}
-
-
-def _bert_layer_array(layers, H: int, I: int):
-    """The host array of ``gnnrag_bert_layer`` structs and the tensors it points to (kept alive by the caller)."""
-    shapes, keep, arr = _bert_layer_shapes(H, I), [], (_lib.BertLayer * max(len(layers), 1))()
-    for l, layer in enumerate(layers):
-        for name in BERT_LAYER_FIELDS:
-            t = _chk(layer[name].detach(), "layers[%d].%s" % (l, name), shape=shapes[name])
-            keep.append(t)
-            setattr(arr[l], name, t.data_ptr())
-    return arr, keep
-
-
 def _bert_layers_args(x, layers, heads, keep_hidden, scale_hidden, keep_att, scale_att, B, T, who):
     if x.dim() not in (2, 3):
         raise ValueError("%s must be [B*T,H] or [B,T,H]" % who)
@@ -2135,14 +2126,7 @@ def _bert_layers_args(x, layers, heads, keep_hidden, scale_hidden, keep_att, sca
     if L < 1:
         raise ValueError("bert layers: at least one layer")
     I = int(layers[0]["W_i"].shape[0])
-    shape_hidden, shape_att = bert_keep_shapes(L, B, T, H, heads)
-    if keep_hidden is not None:
-        keep_hidden = _chk(keep_hidden, "keep_hidden", dtype=torch.uint8, shape=shape_hidden)
-        scale_hidden = _keep_scale(scale_hidden, "scale_hidden")
-    if keep_att is not None:
-        keep_att = _chk(keep_att, "keep_att", dtype=torch.uint8, shape=shape_att)
-        scale_att = _keep_scale(scale_att, "scale_att")
-    return x, H, I, L, keep_hidden, float(scale_hidden), keep_att, float(scale_att)
+    return (x, H, I, L) + _bert_keep_args(L, B, T, H, heads, keep_hidden, scale_hidden, keep_att, scale_att)
 
 
 def bert_layers_forward_save(x0, layers, heads: int, eps: float, B: int, T: int, math: Optional[int] = None, *,
