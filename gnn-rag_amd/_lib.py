@@ -248,6 +248,23 @@ SIGNATURES = {
     "gnnrag_bert_attention_backward": (C.c_int, [_VP, _VP] + [C.c_int32] * 4 + [_VP, C.c_float, _VP, _VP, C.c_size_t, _VP]),
     "gnnrag_bert_ln_backward": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, _VP, C.c_float, C.c_int64, C.c_int32] + [_VP] * 6),
     "gnnrag_bert_gelu_backward": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, _VP]),
+    # fine-tuning the whole encoder: the embedding stage and MPNet's relative bias (additive to ABI 16)
+    "gnnrag_bert_embed_reserve_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_bert_embed_forward_save": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, _VP, C.c_int32, _VP, _VP, C.c_float] +
+                                       [C.c_int32] * 3 + [_VP, C.c_float, _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_bert_embed_backward_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "gnnrag_bert_embed_backward": (C.c_int, [_VP, _VP, _VP, C.c_size_t] + [C.c_int32] * 8 +
+                                   [_VP, C.c_float, _VP, C.c_float] + [_VP] * 6 + [C.c_size_t, _VP]),
+    "gnnrag_bert_layers_forward_save_ex": (C.c_int, [_VP, C.c_int32, C.POINTER(BertLayer), _VP, C.c_float] +
+                                           [C.c_int32] * 5 + [_VP, C.c_float, _VP, C.c_float, _VP, _VP, C.c_size_t, _VP,
+                                                              C.c_size_t, C.c_int32, _VP]),
+    "gnnrag_bert_layers_backward_ex": (C.c_int, [_VP, C.c_int32, C.POINTER(BertLayer), _VP, C.c_float] + [C.c_int32] * 5 +
+                                       [_VP, C.c_float, _VP, C.c_float, _VP, C.c_size_t, _VP, C.POINTER(BertLayerGrads),
+                                        _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_bert_attention_backward_bias": (C.c_int, [_VP, _VP] + [C.c_int32] * 4 +
+                                            [_VP, _VP, C.c_float, _VP, _VP, C.c_size_t, _VP]),
+    "gnnrag_bert_rel_bias_reduce": (C.c_int, [_VP] + [C.c_int32] * 3 + [_VP, _VP]),
+    "gnnrag_bert_embed_scatter": (C.c_int, [_VP, _VP, _VP, C.c_int64] + [C.c_int32] * 5 + [_VP, _VP, _VP]),
     # split-K linear for few rows and the inference encoder on it (additive to ABI 16)
     "gnnrag_linear_splitk_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SplitkPlanStruct)]),
     "gnnrag_linear_splitk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),

@@ -15,7 +15,8 @@ dropout on :class:`UpdateDropFn` (``gnnrag_update_drop_train`` / ``gnnrag_update
 the last distribution on :class:`KLLossFn` (``gnnrag_kl_loss_train`` / ``gnnrag_kl_loss_backward``), the relation tables of
 the fused training form on :class:`RelationTablesFn` (``gnnrag_relation_tables`` / ``gnnrag_relation_tables_backward``), the
 layers of an unfrozen BERT-class question encoder on :class:`BertLayersFn` (``gnnrag_bert_layers_forward_save`` /
-``gnnrag_bert_layers_backward``)."""
+``gnnrag_bert_layers_backward``), with MPNet's relative bias on :class:`BertLayersBiasFn`, and the embedding stage in front
+of them on :class:`BertEmbedFn` (``gnnrag_bert_embed_forward_save`` / ``gnnrag_bert_embed_backward``)."""
 from __future__ import annotations
 
 import torch
@@ -402,43 +403,103 @@ class BertLayersFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, keep_hidden, scale_hidden, keep_att, scale_att, heads, eps, *params):
-        L = len(params) // BERT_LAYER_PARAMS
-        if L < 1 or L * BERT_LAYER_PARAMS != len(params):
-            raise ValueError("BertLayersFn: %d tensors per layer" % BERT_LAYER_PARAMS)
-        B, T, H = x0.shape
-        layers = []
-        for l in range(L):
-            p = [t.detach() for t in params[BERT_LAYER_PARAMS * l: BERT_LAYER_PARAMS * (l + 1)]]
-            layers.append(dict(zip(ops.BERT_LAYER_FIELDS, [torch.cat(p[0:3], 0).contiguous(),
-                                                           torch.cat(p[3:6], 0).contiguous()] + p[6:])))
-        out, reserve = ops.bert_layers_forward_save(x0.detach(), layers, int(heads), float(eps), B, T,
-                                                    keep_hidden=keep_hidden, scale_hidden=scale_hidden,
-                                                    keep_att=keep_att, scale_att=scale_att)
-        ctx.meta = (B, T, H, L, int(heads), float(eps), float(scale_hidden), float(scale_att))
-        ctx.save_for_backward(reserve, keep_hidden, keep_att, *[layer[n] for layer in layers for n in ops.BERT_LAYER_FIELDS])
-        return out
+        return _bert_layers_forward(ctx, x0, None, keep_hidden, scale_hidden, keep_att, scale_att, heads, eps, params)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_out):
-        B, T, H, L, heads, eps, scale_hidden, scale_att = ctx.meta
-        reserve, keep_hidden, keep_att = ctx.saved_tensors[:3]
-        flat, nf = ctx.saved_tensors[3:], len(ops.BERT_LAYER_FIELDS)
-        layers = [dict(zip(ops.BERT_LAYER_FIELDS, flat[nf * l: nf * (l + 1)])) for l in range(L)]
-        nig, first = ctx.needs_input_grad, 7
-        need = []
-        for l in range(L):
-            n = nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
-            d = {"dW_qkv": any(n[0:3]), "db_qkv": any(n[3:6])}
-            d.update({"d" + name: n[4 + i] for i, name in enumerate(ops.BERT_LAYER_FIELDS) if i >= 2})
-            need.append(d)
-        g_x0, grads = ops.bert_layers_backward(g_out.float(), layers, heads, eps, B, T, reserve, keep_hidden=keep_hidden,
-                                               scale_hidden=scale_hidden, keep_att=keep_att, scale_att=scale_att,
-                                               need_x0=nig[0], need=need)
-        ret = [g_x0, None, None, None, None, None, None]
-        for l in range(L):
-            g, n = grads[l], nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
-            for packed, lo in ((g["dW_qkv"], 0), (g["db_qkv"], 3)):
-                ret += [packed[H * k: H * (k + 1)] if packed is not None and n[lo + k] else None for k in range(3)]
-            ret += [g["d" + name] for name in ops.BERT_LAYER_FIELDS[2:]]
-        return tuple(ret)
+        g_x0, _, per_param = _bert_layers_backward(ctx, g_out, first=7, want_bias=False)
+        return (g_x0, None, None, None, None, None, None) + per_param
+
+
+class BertLayersBiasFn(torch.autograd.Function):
+    """:class:`BertLayersFn` with MPNet's relative attention bias: ``rel_bias [heads, 2T-1]`` (entry ``[h, j - i + T - 1]``
+    is added to the scaled score of query i and key j in every layer) is the second, differentiable input, on
+    ``gnnrag_bert_layers_forward_save_ex`` / ``gnnrag_bert_layers_backward_ex``.  Its gradient is one table summed over the
+    layers; it is computed only when the input needs it."""
+
+    @staticmethod
+    def forward(ctx, x0, rel_bias, keep_hidden, scale_hidden, keep_att, scale_att, heads, eps, *params):
+        return _bert_layers_forward(ctx, x0, rel_bias.detach().contiguous(), keep_hidden, scale_hidden, keep_att,
+                                    scale_att, heads, eps, params)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        g_x0, d_bias, per_param = _bert_layers_backward(ctx, g_out, first=8, want_bias=ctx.needs_input_grad[1])
+        return (g_x0, d_bias, None, None, None, None, None, None) + per_param
+
+
+def _bert_layers_forward(ctx, x0, rel_bias, keep_hidden, scale_hidden, keep_att, scale_att, heads, eps, params):
+    """The forward of :class:`BertLayersFn` (``rel_bias`` None) and :class:`BertLayersBiasFn`."""
+    L = len(params) // BERT_LAYER_PARAMS
+    if L < 1 or L * BERT_LAYER_PARAMS != len(params):
+        raise ValueError("BertLayersFn: %d tensors per layer" % BERT_LAYER_PARAMS)
+    B, T, H = x0.shape
+    layers = []
+    for l in range(L):
+        p = [t.detach() for t in params[BERT_LAYER_PARAMS * l: BERT_LAYER_PARAMS * (l + 1)]]
+        layers.append(dict(zip(ops.BERT_LAYER_FIELDS, [torch.cat(p[0:3], 0).contiguous(),
+                                                       torch.cat(p[3:6], 0).contiguous()] + p[6:])))
+    out, reserve = ops.bert_layers_forward_save(x0.detach(), layers, int(heads), float(eps), B, T,
+                                                keep_hidden=keep_hidden, scale_hidden=scale_hidden,
+                                                keep_att=keep_att, scale_att=scale_att, rel_bias=rel_bias)
+    ctx.meta = (B, T, H, L, int(heads), float(eps), float(scale_hidden), float(scale_att))
+    ctx.save_for_backward(reserve, keep_hidden, keep_att, rel_bias,
+                          *[layer[n] for layer in layers for n in ops.BERT_LAYER_FIELDS])
+    return out
+
+
+def _bert_layers_backward(ctx, g_out, first, want_bias):
+    """``(g_x0, d_rel_bias, the per-parameter gradients)`` of the two Functions; ``first``: the index of the first layer
+    parameter among the Function's inputs."""
+    B, T, H, L, heads, eps, scale_hidden, scale_att = ctx.meta
+    reserve, keep_hidden, keep_att, rel_bias = ctx.saved_tensors[:4]
+    flat, nf = ctx.saved_tensors[4:], len(ops.BERT_LAYER_FIELDS)
+    layers = [dict(zip(ops.BERT_LAYER_FIELDS, flat[nf * l: nf * (l + 1)])) for l in range(L)]
+    nig = ctx.needs_input_grad
+    need = []
+    for l in range(L):
+        n = nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
+        d = {"dW_qkv": any(n[0:3]), "db_qkv": any(n[3:6])}
+        d.update({"d" + name: n[4 + i] for i, name in enumerate(ops.BERT_LAYER_FIELDS) if i >= 2})
+        need.append(d)
+    res = ops.bert_layers_backward(g_out.float(), layers, heads, eps, B, T, reserve, keep_hidden=keep_hidden,
+                                   scale_hidden=scale_hidden, keep_att=keep_att, scale_att=scale_att,
+                                   need_x0=nig[0], need=need, rel_bias=rel_bias, want_rel_bias_grad=bool(want_bias))
+    g_x0, grads, d_bias = res if want_bias else res + (None,)
+    ret = []
+    for l in range(L):
+        g, n = grads[l], nig[first + BERT_LAYER_PARAMS * l: first + BERT_LAYER_PARAMS * (l + 1)]
+        for packed, lo in ((g["dW_qkv"], 0), (g["db_qkv"], 3)):
+            ret += [packed[H * k: H * (k + 1)] if packed is not None and n[lo + k] else None for k in range(3)]
+        ret += [g["d" + name] for name in ops.BERT_LAYER_FIELDS[2:]]
+    return g_x0, d_bias, tuple(ret)
+
+
+class BertEmbedFn(torch.autograd.Function):
+    """``x0 [B,T,H]`` = the embedding stage of a BERT-class LM - the lookups, the positions (``pad_id`` None: 0 .. T-1, else
+    counted from the ids), the LayerNorm and the dropout of keep plane 0 (``keep`` uint8 [B*T,H] or None) - on
+    ``gnnrag_bert_embed_forward_save`` / ``gnnrag_bert_embed_backward``.  Differentiable inputs: ``word_emb``, ``pos_emb``,
+    ``type_emb`` (None for an encoder without a token-type term), ``ln_g``, ``ln_b``; a table's gradient is dense, with the
+    rows ``word_pad`` / ``pos_pad`` (transformers' ``padding_idx``, or None) exactly zero.  The reserve belongs to the
+    context of THIS call."""
+
+    @staticmethod
+    def forward(ctx, ids, keep, scale, pad_id, word_pad, pos_pad, eps, word_emb, pos_emb, type_emb, ln_g, ln_b):
+        x0, reserve = ops.bert_embed_forward_save(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, float(eps), pad_id=pad_id,
+                                                  keep=keep, scale=scale)
+        ctx.meta = (float(scale), word_pad, pos_pad, float(eps), int(word_emb.shape[0]), int(pos_emb.shape[0]),
+                    0 if type_emb is None else int(type_emb.shape[0]))
+        ctx.save_for_backward(ids, reserve, keep, ln_g.detach())
+        return x0
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x0):
+        scale, word_pad, pos_pad, eps, vocab, max_pos, n_type = ctx.meta
+        ids, reserve, keep, ln_g = ctx.saved_tensors
+        need = dict(zip(ops.BERT_EMBED_GRADS, ctx.needs_input_grad[7:12]))
+        g = ops.bert_embed_backward(g_x0.float().contiguous(), ids, reserve, ln_g, eps, vocab, max_pos, n_type,
+                                    word_pad=word_pad, pos_pad=pos_pad, keep=keep, scale=scale, need=need)
+        return (None,) * 7 + tuple(g[n] for n in ops.BERT_EMBED_GRADS)

@@ -90,6 +90,42 @@ __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_ln(const int64_
   }
 }
 
+// What the embedding backward needs of k_bert_embed_ln's row: sum0[row] = word_emb[id] + type_emb[0] + pos_emb[pos] - the
+// same additions in the same order, so the value that kernel normalises - and pos_out[row] = pos.  A row that kernel makes
+// NaN (an id or a position outside its table) gets a NaN sum0 row and pos_out = -1.  IDPOS / TYPE as there.
+template <bool IDPOS, bool TYPE>
+__global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_save(const int64_t* __restrict__ ids,
+                                                                      const float* __restrict__ word_emb, int vocab,
+                                                                      const float* __restrict__ pos_emb, int max_pos,
+                                                                      const float* __restrict__ type_emb, int pad_id, int M,
+                                                                      int T, int H4, float* __restrict__ sum0,
+                                                                      int32_t* __restrict__ pos_out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
+  if (row >= M) return;
+  f32x4* dst = (f32x4*)(sum0 + (size_t)row * H4 * 4);
+  const int64_t id = ids[row];
+  int pos = row % T;
+  if (IDPOS) {
+    const int64_t* q = ids + (size_t)(row - pos);
+    const bool n0 = lane <= pos && q[lane] != (int64_t)pad_id;
+    const bool n1 = lane + 64 <= pos && q[lane + 64] != (int64_t)pad_id;
+    const int count = __popcll(__ballot(n0)) + __popcll(__ballot(n1));
+    pos = id != (int64_t)pad_id ? pad_id + count : pad_id;
+  }
+  if (id < 0 || id >= (int64_t)vocab || pos < 0 || pos >= max_pos) {
+    const float nan = __uint_as_float(0x7fc00000u);
+    for (int i = lane; i < H4; i += 64) dst[i] = (f32x4){nan, nan, nan, nan};
+    if (lane == 0) pos_out[row] = -1;
+    return;
+  }
+  const f32x4* w = (const f32x4*)(word_emb + (size_t)id * H4 * 4);
+  const f32x4* p = (const f32x4*)(pos_emb + (size_t)pos * H4 * 4);
+  const f32x4* ty = (const f32x4*)type_emb;
+  for (int i = lane; i < H4; i += 64) dst[i] = TYPE ? (w[i] + ty[i]) + p[i] : w[i] + p[i];
+  if (lane == 0) pos_out[row] = pos;
+}
+
 // out[row] = LN(in[row]); in already holds dense(x) + bias + residual.  out == in is allowed (no __restrict__ on the two).
 __global__ __launch_bounds__(64 * kBertLnRows) void k_bert_add_ln(const float* in, const float* __restrict__ g,
                                                                   const float* __restrict__ bt, float eps, int M, int H4,
@@ -366,6 +402,59 @@ static int bert_layers_run(int32_t L, const gnnrag_bert_layer* layers, const flo
   return 0;
 }
 
+// The embedding launch of every entry point: pad_id >= 0 takes the positions from the ids, type_emb NULL leaves the
+// token-type term out, keep NULL (plane 0 of keep_hidden otherwise) is the inference kernel.
+static int bert_embed_ln_launch(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                int32_t max_pos, const float* type_emb, int32_t pad_id, const float* ln_g,
+                                const float* ln_b, float ln_eps, int64_t M, int32_t T, int32_t H, float* out,
+                                const uint8_t* keep_hidden, float scale_hidden, hipStream_t st) {
+  const int H4 = H / 4;
+  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
+#define GNNRAG_EMBED_LN(IDPOS, TYPE)                                                                                    \
+  if (keep_hidden)                                                                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, true>), ln_grid, ln_block, 0, st, ids, word_emb,    \
+                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out, keep_hidden,  \
+                       scale_hidden);                                                                                   \
+  else                                                                                                                  \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, false>), ln_grid, ln_block, 0, st, ids, word_emb,   \
+                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out,               \
+                       (const uint8_t*)nullptr, 0.f)
+  if (pad_id >= 0 && type_emb) {
+    GNNRAG_EMBED_LN(true, true);
+  } else if (pad_id >= 0) {
+    GNNRAG_EMBED_LN(true, false);
+  } else if (type_emb) {
+    GNNRAG_EMBED_LN(false, true);
+  } else {
+    GNNRAG_EMBED_LN(false, false);
+  }
+#undef GNNRAG_EMBED_LN
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// k_bert_embed_save on the same arguments
+static int bert_embed_save_launch(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                  int32_t max_pos, const float* type_emb, int32_t pad_id, int64_t M, int32_t T, int32_t H,
+                                  float* sum0, int32_t* pos, hipStream_t st) {
+  const dim3 grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), block(64 * kBertLnRows);
+#define GNNRAG_EMBED_SAVE(IDPOS, TYPE)                                                                                  \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_save<IDPOS, TYPE>), grid, block, 0, st, ids, word_emb, vocab, pos_emb, \
+                     max_pos, type_emb, pad_id, (int)M, T, H / 4, sum0, pos)
+  if (pad_id >= 0 && type_emb) {
+    GNNRAG_EMBED_SAVE(true, true);
+  } else if (pad_id >= 0) {
+    GNNRAG_EMBED_SAVE(true, false);
+  } else if (type_emb) {
+    GNNRAG_EMBED_SAVE(false, true);
+  } else {
+    GNNRAG_EMBED_SAVE(false, false);
+  }
+#undef GNNRAG_EMBED_SAVE
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace gnnrag
 
 using namespace gnnrag;
@@ -450,28 +539,8 @@ static int bert_encode_run(const int64_t* ids, const float* word_emb, int32_t vo
   for (int l = 0; l < L; ++l) GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsAll));
 
   hipStream_t st = (hipStream_t)stream;
-  const int H4 = H / 4;
-  const dim3 ln_grid((unsigned)((M + kBertLnRows - 1) / kBertLnRows)), ln_block(64 * kBertLnRows);
-#define GNNRAG_EMBED_LN(IDPOS, TYPE)                                                                                    \
-  if (keep_hidden)                                                                                                      \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, true>), ln_grid, ln_block, 0, st, ids, word_emb,    \
-                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out, keep_hidden,  \
-                       scale_hidden);                                                                                   \
-  else                                                                                                                  \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_embed_ln<IDPOS, TYPE, false>), ln_grid, ln_block, 0, st, ids, word_emb,   \
-                       vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, (int)M, T, H4, out,               \
-                       (const uint8_t*)nullptr, 0.f)
-  if (pad_id >= 0 && type_emb) {
-    GNNRAG_EMBED_LN(true, true);
-  } else if (pad_id >= 0) {
-    GNNRAG_EMBED_LN(true, false);
-  } else if (type_emb) {
-    GNNRAG_EMBED_LN(false, true);
-  } else {
-    GNNRAG_EMBED_LN(false, false);
-  }
-#undef GNNRAG_EMBED_LN
-  GNNRAG_LAUNCH_CHECK();
+  GNNRAG_RC(bert_embed_ln_launch(ids, word_emb, vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, M, T, H, out,
+                                 keep_hidden, scale_hidden, st));
   if (L == 0) return 0;
 
   if (splitk) {
@@ -551,13 +620,15 @@ extern "C" size_t gnnrag_bert_reserve_bytes(int32_t L, int32_t B, int32_t T, int
 
 // bert_layers_run - the layer loop bert_encode_run calls - on a caller-given x0, with the values the backward needs left in
 // the reserve (bert_reserve.h) instead of the workspace: the products write their blocks of the reserve directly; the
-// layer input, LayerNorm 1's output and the FFN pre-activation go to its save slots.  No relative attention bias.  Its own
-// argument rules: a short reserve or workspace is GNNRAG_E_WORKSPACE, behind every pointer rule.
-extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
-                                               int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
-                                               const uint8_t* keep_hidden, float scale_hidden, const uint8_t* keep_att,
-                                               float scale_att, float* out, void* reserve, size_t reserve_bytes, void* ws,
-                                               size_t ws_bytes, int32_t math, gnnrag_stream_t stream) {
+// layer input, LayerNorm 1's output and the FFN pre-activation go to its save slots.  rel_bias NULL: no relative attention
+// bias (gnnrag_bert_layers_forward_save).  Its own argument rules: a short reserve or workspace is GNNRAG_E_WORKSPACE,
+// behind every pointer rule.
+extern "C" int gnnrag_bert_layers_forward_save_ex(const float* x0, int32_t L, const gnnrag_bert_layer* layers,
+                                                  const float* rel_bias, float ln_eps, int32_t B, int32_t T, int32_t H,
+                                                  int32_t heads, int32_t I, const uint8_t* keep_hidden, float scale_hidden,
+                                                  const uint8_t* keep_att, float scale_att, float* out, void* reserve,
+                                                  size_t reserve_bytes, void* ws, size_t ws_bytes, int32_t math,
+                                                  gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L <= 0) return GNNRAG_E_BADARG;
   if (math != GNNRAG_MATH_FP32 && math != GNNRAG_MATH_BF16X3 && math != GNNRAG_MATH_MIXED) return GNNRAG_E_BADARG;
   if (H % heads != 0 || H % 4 != 0 || I % 4 != 0 || T > kBertMaxT) return GNNRAG_E_UNSUPPORTED;
@@ -568,7 +639,7 @@ extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const
   const BertReserve r = bert_reserve(M, H, I);
   if (!x0 || !layers || !out || !reserve || !ws) return GNNRAG_E_BADARG;
   if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
-  if (!aligned16(x0, out, reserve, ws) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(x0, out, reserve, ws, rel_bias) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsAll));
   if (reserve_bytes < (size_t)L * r.layer || ws_bytes < w.total) return GNNRAG_E_WORKSPACE;
 
@@ -580,6 +651,45 @@ extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const
     return BertLayerDst{(float*)(rl + r.qkv), (float*)(rl + r.ctx), (float*)(rl + r.sum1), (float*)(rl + r.sum2),
                         (float*)(rl + r.pre), ffn,                  (float*)(rl + r.xin),  (float*)(rl + r.x1)};
   };
-  return bert_layers_run(L, layers, nullptr, ln_eps, B, T, H, heads, I, BertKeep(keep_hidden, keep_att, B, T, H, heads),
+  return bert_layers_run(L, layers, rel_bias, ln_eps, B, T, H, heads, I, BertKeep(keep_hidden, keep_att, B, T, H, heads),
                          scale_hidden, scale_att, out, dst_of, math, stream);
+}
+
+extern "C" int gnnrag_bert_layers_forward_save(const float* x0, int32_t L, const gnnrag_bert_layer* layers, float ln_eps,
+                                               int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I,
+                                               const uint8_t* keep_hidden, float scale_hidden, const uint8_t* keep_att,
+                                               float scale_att, float* out, void* reserve, size_t reserve_bytes, void* ws,
+                                               size_t ws_bytes, int32_t math, gnnrag_stream_t stream) {
+  return gnnrag_bert_layers_forward_save_ex(x0, L, layers, nullptr, ln_eps, B, T, H, heads, I, keep_hidden, scale_hidden,
+                                            keep_att, scale_att, out, reserve, reserve_bytes, ws, ws_bytes, math, stream);
+}
+
+extern "C" size_t gnnrag_bert_embed_reserve_bytes(int32_t B, int32_t T, int32_t H) {
+  if (B <= 0 || T <= 0 || H <= 0 || (H & 3)) return 0;
+  return bert_embed_reserve((int64_t)B * T, H).total;
+}
+
+// The embedding stage of gnnrag_bert_encode_train - its k_bert_embed_ln launch on the same arguments, so its bits in
+// `out` - and k_bert_embed_save for the reserve of gnnrag_bert_embed_backward.
+extern "C" int gnnrag_bert_embed_forward_save(const int64_t* ids, const float* word_emb, int32_t vocab,
+                                              const float* pos_emb, int32_t max_pos, const float* type_emb, int32_t pad_id,
+                                              const float* ln_g, const float* ln_b, float ln_eps, int32_t B, int32_t T,
+                                              int32_t H, const uint8_t* keep, float scale, float* out, void* reserve,
+                                              size_t reserve_bytes, gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
+  if (H % 4 != 0 || T > kBertMaxT || T > max_pos) return GNNRAG_E_UNSUPPORTED;
+  if (pad_id >= 0 && (int64_t)T + pad_id > (int64_t)max_pos - 1) return GNNRAG_E_UNSUPPORTED;
+  if ((int64_t)B * T >= ((int64_t)1 << 31)) return GNNRAG_E_UNSUPPORTED;
+  if (!ids || !word_emb || !pos_emb || !ln_g || !ln_b || !out || !reserve || !bert_scale_ok(keep, scale))
+    return GNNRAG_E_BADARG;
+  if (!aligned16(word_emb, pos_emb, type_emb, ln_g, ln_b, out, reserve) || ((uintptr_t)ids & 7) || ((uintptr_t)keep & 3))
+    return GNNRAG_E_UNSUPPORTED;
+  const int64_t M = (int64_t)B * T;
+  const BertEmbedReserve r = bert_embed_reserve(M, H);
+  if (reserve_bytes < r.total) return GNNRAG_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  GNNRAG_RC(bert_embed_ln_launch(ids, word_emb, vocab, pos_emb, max_pos, type_emb, pad_id, ln_g, ln_b, ln_eps, M, T, H, out,
+                                 keep, scale, st));
+  return bert_embed_save_launch(ids, word_emb, vocab, pos_emb, max_pos, type_emb, pad_id, M, T, H,
+                                (float*)((char*)reserve + r.sum0), (int32_t*)((char*)reserve + r.pos), st);
 }

@@ -1,6 +1,6 @@
 // Backward of the encoder layers of a BERT-class question encoder (bert_encoder.hip, gnnrag_bert_layers_forward_save):
 // what fine-tuning the LM (the reference's --lm_frozen 0, gnn/modules/question_encoding/bert_encoder.py:80-87) derives
-// for transformers' BertModel / RobertaModel layers.  The embedding stage stays outside (its gradient is g_x0).
+// for transformers' BertModel / RobertaModel / MPNetModel layers, and of the embedding stage in front of them.
 //
 // Layers run L-1 .. 0; g is the gradient of the layer's output.  With m = keep ? scale : 0 of the site (1 without a mask):
 //   LayerNorm 2   dz2 = LN'(g) on the rebuilt row z = sum2 m + x1; dY = dz2 m             k_bert_ln_bwd
@@ -14,6 +14,13 @@
 //   attention     d_qkv from qkv, d_ctx, keep_att                                          k_bert_attention_bwd
 //   QKV           dW_qkv = d_qkv^T xin; db_qkv = colsum(d_qkv) with the key third written as +0 (every row of dS sums to
 //                 zero: the gradient is mathematically zero, autograd leaves rounding residue); g = dz1 + d_qkv W_qkv
+// MPNet (rel_bias given): the attention step recomputes the probabilities with the bias (k_bert_attention_bwd_bias) and the
+// table's gradient is the sum of the dS squares along their diagonals, the layers added in the order L-1 .. 0
+// (k_bert_rel_bias_reduce).
+// The embedding stage (gnnrag_bert_embed_backward; x0 = LN(word[id] + type[0] + pos[p]) m, the dropout BEHIND the LayerNorm):
+//   dy = g_x0 m                                                                            k_bert_mask_mul
+//   dz = LN'(dy) on the saved row sum0; d_ln_g = colsum(dy xhat), d_ln_b = colsum(dy)      k_bert_ln_bwd<false>, colsum_launch
+//   d_type[0] = colsum(dz); d_word[k], d_pos[k] = the dz rows that name k, ascending       k_bert_embed_scatter
 // Every backward product is exact fp32 (gnnrag_gemm_tn has no other form).  fp32 throughout, no atomics, every reduction in
 // an order the shape alone fixes, nothing allocated, nothing waits for the stream: a second call gives the same bits, and
 // the rows of g_x0 of a question depend on that question's rows only (LayerNorm: a wave per row; attention: a workgroup
@@ -143,123 +150,106 @@ __device__ __forceinline__ float bert_att_opaque(float v) {
 // No atomics.  A query row whose keys are all dropped has pt = 0, r = 0 and dS = 0: a zero dQ row, nothing added to dK, dV.
 // The dot products are explicit fmaf chains: the two instantiations of a DH compute the same bits where the masks are all
 // ones at scale 1.
+// BIAS (k_bert_attention_bwd_bias, MPNet): the head's row of rel_bias [heads, 2T-1] sits in LDS behind dO (2T floats
+// reserved) and the score of (t, j) is (q . k) scale + bias[j - t + T - 1], added in blocks of their own behind
+// bert_att_opaque as k_bert_attention<DH, true> adds it: an all-zero table gives the bits of the kernel without a bias,
+// and without BIAS rel_bias is not read and the LDS layout is the one above.  The bias's own gradient is the sum of the
+// dS squares along their diagonals: k_bert_rel_bias_reduce.
 template <int DH, bool DROP>
 __global__ __launch_bounds__(GNNRAG_BERT_ATT_BWD_THREADS) void k_bert_attention_bwd(
     const float* __restrict__ qkv, const float* __restrict__ dctx, int T, int heads, const uint8_t* __restrict__ keep,
     float keep_scale, float* __restrict__ dqkv, float* sq) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int LD = DH + 1;
-  const int b = blockIdx.x / heads, h = blockIdx.x % heads;
-  const int H = heads * DH;
-  const int tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nthr >> 6;
-  float* ks = smem;                                   // [T, LD]
-  float* vs = ks + T * LD;                            // [T, LD]
-  float* qs = vs + T * LD;                            // [T, LD]
-  float* gs = qs + T * LD;                            // [T, LD]  dO
-  float* ds = gs + T * LD + wave * kBertMaxT;         // [kBertMaxT]  this wave's row of dS
-  float* dsg = sq + (size_t)blockIdx.x * 2 * T * T;   // [T, T]  dS, query row i, key column j
-  float* ptg = dsg + (size_t)T * T;                   // [T, T]  pt
+  constexpr bool BIAS = false;
+  const float* rel_bias = nullptr;
+#include "bert_attention_bwd_body.h"
+}
 
-  const float* base = qkv + (size_t)b * T * 3 * H + h * DH;
-  const float* gbase = dctx + (size_t)b * T * H + h * DH;
-  float* obase = dqkv + (size_t)b * T * 3 * H + h * DH;
-  for (int i = tid; i < T * (DH / 4); i += nthr) {
-    const int j = i / (DH / 4), c = (i % (DH / 4)) * 4;
-    const float* row = base + (size_t)j * 3 * H;
-    const f32x4 qv = *(const f32x4*)(row + c);
-    const f32x4 kv = *(const f32x4*)(row + H + c);
-    const f32x4 vv = *(const f32x4*)(row + 2 * H + c);
-    const f32x4 gv = *(const f32x4*)(gbase + (size_t)j * H + c);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      qs[j * LD + c + e] = qv[e];
-      ks[j * LD + c + e] = kv[e];
-      vs[j * LD + c + e] = vv[e];
-      gs[j * LD + c + e] = gv[e];
-    }
+template <int DH, bool DROP>
+__global__ __launch_bounds__(GNNRAG_BERT_ATT_BWD_THREADS) void k_bert_attention_bwd_bias(
+    const float* __restrict__ qkv, const float* __restrict__ rel_bias, const float* __restrict__ dctx, int T, int heads,
+    const uint8_t* __restrict__ keep, float keep_scale, float* __restrict__ dqkv, float* sq) {
+  constexpr bool BIAS = true;
+#include "bert_attention_bwd_body.h"
+}
+
+// d_bias[h][d + T - 1] (+)= sum_b sum_{i, j = i + d} dS[b, h, i, j] from the squares k_bert_attention_bwd left in `sq`
+// ([B heads, 2, T, T]: the dS square of every pair first).  One thread owns an entry and adds b ascending, then i
+// ascending; add != 0: the entry's present value comes first (the layers share one table: their sums are added in the
+// order the backward visits them).
+__global__ __launch_bounds__(256) void k_bert_rel_bias_reduce(const float* __restrict__ sq, int B, int T, int heads,
+                                                              int add, float* d_bias) {
+  const int W = 2 * T - 1;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= heads * W) return;
+  const int h = idx / W, d = idx % W - (T - 1);
+  const int i0 = d < 0 ? -d : 0, i1 = d < 0 ? T : T - d;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const float* s = sq + ((size_t)b * heads + h) * 2 * T * T + d;
+    for (int i = i0; i < i1; ++i) acc += s[i * (T + 1)];
   }
-  __syncthreads();
+  d_bias[idx] = add ? d_bias[idx] + acc : acc;
+}
 
-  const float scale = 1.f / sqrtf((float)DH);
-  const int j0 = lane, j1 = lane + 64;
-  for (int t = wave; t < T; t += nw) {
-    const float* q = qs + t * LD;
-    const float* go = gs + t * LD;
-    float s0 = -INFINITY, s1 = -INFINITY, dp0 = 0.f, dp1 = 0.f;
-    if (j0 < T) {
-      const float *k = ks + j0 * LD, *v = vs + j0 * LD;
-      float a = 0.f, c = 0.f;
-#pragma unroll
-      for (int d = 0; d < DH; ++d) {
-        a = fmaf(q[d], k[d], a);
-        c = fmaf(go[d], v[d], c);
-      }
-      s0 = a * scale;
-      dp0 = c;
-    }
-    if (j1 < T) {
-      const float *k = ks + j1 * LD, *v = vs + j1 * LD;
-      float a = 0.f, c = 0.f;
-#pragma unroll
-      for (int d = 0; d < DH; ++d) {
-        a = fmaf(q[d], k[d], a);
-        c = fmaf(go[d], v[d], c);
-      }
-      s1 = a * scale;
-      dp1 = c;
-    }
-    const float m = wave_max(fmaxf(s0, s1));
-    const float e0 = j0 < T ? expf(s0 - m) : 0.f, e1 = j1 < T ? expf(s1 - m) : 0.f;
-    const float sum = wave_sum(e0 + e1);
-    const float p0 = e0 / sum, p1 = e1 / sum;
-    float m0 = 1.f, m1 = 1.f;
-    if (DROP) {
-      const uint8_t* kr = keep + ((size_t)blockIdx.x * T + t) * T;     // blockIdx.x = b heads + h
-      m0 = j0 < T && kr[j0] ? keep_scale : 0.f;
-      m1 = j1 < T && kr[j1] ? keep_scale : 0.f;
-    }
-    const float pt0 = DROP ? p0 * m0 : p0, pt1 = DROP ? p1 * m1 : p1;
-    const float r = wave_sum(fmaf(pt0, dp0, pt1 * dp1));
-    // the masked product is rounded on its own (behind bert_att_opaque it cannot be fused into the subtraction): with
-    // one key p = 1, r is that same rounded product and dS is exactly 0, as it is in exact arithmetic
-    const float dS0 = p0 * ((DROP ? bert_att_opaque(dp0 * m0) : dp0) - r);
-    const float dS1 = p1 * ((DROP ? bert_att_opaque(dp1 * m1) : dp1) - r);
-    if (j0 < T) {
-      ds[j0] = dS0;
-      dsg[t * T + j0] = dS0;
-      ptg[t * T + j0] = pt0;
-    }
-    if (j1 < T) {
-      ds[j1] = dS1;
-      dsg[t * T + j1] = dS1;
-      ptg[t * T + j1] = pt1;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (lane < DH) {
-      float acc = 0.f;
-      for (int j = 0; j < T; ++j) acc = fmaf(ds[j], ks[j * LD + lane], acc);
-      obase[(size_t)t * 3 * H + lane] = acc * scale;
-    }
-    // the next row's writes to ds follow this row's reads in program order (one wave, LDS in order)
-    __builtin_amdgcn_wave_barrier();
+// dy = g m over n4 float4s (m from the keep bytes): the embedding's dropout sits behind its LayerNorm
+__global__ __launch_bounds__(256) void k_bert_mask_mul(const float* __restrict__ g, const uint8_t* __restrict__ keep,
+                                                       float scale, size_t n4, float* __restrict__ dy) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
+    ((f32x4*)dy)[i] = ((const f32x4*)g)[i] * bert_keep4(((const uint32_t*)keep)[i], scale);
+}
+
+// Gradient of an embedding table from dz [M, H]: out[k] = the sum of the rows dz[q] with key(q) == k in ascending q, where
+// key(q) is the table row token q names - ids[q] (blockIdx.y == 0, d_word) or pos[q] (blockIdx.y == 1, d_pos) - and no row
+// at all for a token whose id lies outside [0, vocab), whose pos lies outside [0, max_pos) (the forward's -1 included) or
+// whose key is the table's padding row (word_pad / pos_pad; -1: none).  A wave per (token r, table): 64 rows per ballot,
+// it leaves when a row below r has r's key, else it owns table row key(r) and adds the matching rows of r .. M - 1, lanes
+// over the float4s of a row.  No atomics; the rows nobody owns keep the zeros the host's fill gave them.
+__global__ __launch_bounds__(64 * kBertLnRows) void k_bert_embed_scatter(const int64_t* __restrict__ ids,
+                                                                         const int32_t* __restrict__ pos,
+                                                                         const float* __restrict__ dz, int M, int H4,
+                                                                         int vocab, int max_pos, int word_pad, int pos_pad,
+                                                                         float* __restrict__ d_word,
+                                                                         float* __restrict__ d_pos) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * kBertLnRows + (threadIdx.x >> 6);
+  if (r >= M) return;
+  const bool word = blockIdx.y == 0;
+  float* out = word ? d_word : d_pos;
+  if (!out) return;
+  const int pad = word ? word_pad : pos_pad;
+  auto key = [&](int q) -> int {
+    const int64_t id = ids[q];
+    const int p = pos[q];
+    if (id < 0 || id >= (int64_t)vocab || p < 0 || p >= max_pos) return -1;
+    const int k = word ? (int)id : p;
+    return k == pad ? -1 : k;
+  };
+  const int mine = key(r);
+  if (mine < 0) return;
+  for (int base = 0; base < r; base += 64) {
+    const int q = base + lane;
+    if (__ballot(q < r && key(q) == mine)) return;
   }
-  __syncthreads();          // the squares are written by this workgroup and read by it: visible behind the barrier
-
-  for (int idx = tid; idx < T * DH; idx += nthr) {
-    const int j = idx / DH, d = idx % DH;
-    float ak = 0.f, av = 0.f;
-    for (int i = 0; i < T; ++i) {
-      ak = fmaf(dsg[i * T + j], qs[i * LD + d], ak);
-      av = fmaf(ptg[i * T + j], gs[i * LD + d], av);
+  f32x4* dst = (f32x4*)(out + (size_t)mine * H4 * 4);
+  for (int c0 = 0; c0 < H4; c0 += 64) {
+    const int c = c0 + lane;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int base = r & ~63; base < M; base += 64) {
+      const int q = base + lane;
+      unsigned long long hits = __ballot(q >= r && q < M && key(q) == mine);
+      while (hits) {
+        const int q1 = base + __builtin_ctzll(hits);
+        hits &= hits - 1;
+        if (c < H4) acc = acc + ((const f32x4*)(dz + (size_t)q1 * H4 * 4))[c];
+      }
     }
-    obase[(size_t)j * 3 * H + H + d] = ak * scale;
-    obase[(size_t)j * 3 * H + 2 * H + d] = av;
+    if (c < H4) dst[c] = acc;
   }
 }
 
-static inline size_t bert_att_bwd_lds_bytes(int T, int dh, int threads) {
-  return ((size_t)4 * T * (dh + 1) + (size_t)(threads / 64) * kBertMaxT) * sizeof(float);
+static inline size_t bert_att_bwd_lds_bytes(int T, int dh, int threads, bool bias = false) {
+  return ((size_t)4 * T * (dh + 1) + (bias ? (size_t)2 * T : 0) + (size_t)(threads / 64) * kBertMaxT) * sizeof(float);
 }
 
 static inline size_t bert_att_bwd_scratch_bytes(int64_t B, int32_t T, int32_t heads) {
@@ -281,9 +271,37 @@ static int bert_attention_bwd_launch_as(const float* qkv, const float* dctx, con
   return 0;
 }
 
-// keep NULL: no dropout (the kernel never sees a NULL pointer's argument)
+template <int DH, bool DROP>
+static int bert_attention_bwd_bias_launch_as(const float* qkv, const float* rel_bias, const float* dctx,
+                                             const uint8_t* keep, float keep_scale, int32_t B, int32_t T, int32_t heads,
+                                             float* dqkv, float* sq, hipStream_t stream) {
+  const int threads = GNNRAG_BERT_ATT_BWD_THREADS;
+  const size_t lds = bert_att_bwd_lds_bytes(T, DH, threads, true);
+  if (lds > 64 * 1024) {
+    static DeviceMask raised{0};
+    GNNRAG_RC(raise_lds_cap(k_bert_attention_bwd_bias<DH, DROP>, raised));
+  }
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bert_attention_bwd_bias<DH, DROP>), dim3((unsigned)((int64_t)B * heads)),
+                     dim3(threads), lds, stream, qkv, rel_bias, dctx, T, heads, keep, keep_scale, dqkv, sq);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// keep NULL: no dropout (the kernel never sees a NULL pointer's argument); rel_bias NULL: the kernels without a bias
 static int bert_attention_bwd_launch(const float* qkv, const float* dctx, const uint8_t* keep, float keep_scale, int32_t B,
-                                     int32_t T, int32_t heads, int32_t dh, float* dqkv, float* sq, hipStream_t stream) {
+                                     int32_t T, int32_t heads, int32_t dh, float* dqkv, float* sq, hipStream_t stream,
+                                     const float* rel_bias = nullptr) {
+  if (rel_bias) {
+    if (dh == 32)
+      return keep ? bert_attention_bwd_bias_launch_as<32, true>(qkv, rel_bias, dctx, keep, keep_scale, B, T, heads, dqkv, sq,
+                                                                stream)
+                  : bert_attention_bwd_bias_launch_as<32, false>(qkv, rel_bias, dctx, nullptr, 0.f, B, T, heads, dqkv, sq,
+                                                                 stream);
+    return keep ? bert_attention_bwd_bias_launch_as<64, true>(qkv, rel_bias, dctx, keep, keep_scale, B, T, heads, dqkv, sq,
+                                                              stream)
+                : bert_attention_bwd_bias_launch_as<64, false>(qkv, rel_bias, dctx, nullptr, 0.f, B, T, heads, dqkv, sq,
+                                                               stream);
+  }
   if (dh == 32)
     return keep ? bert_attention_bwd_launch_as<32, true>(qkv, dctx, keep, keep_scale, B, T, heads, dqkv, sq, stream)
                 : bert_attention_bwd_launch_as<32, false>(qkv, dctx, nullptr, 0.f, B, T, heads, dqkv, sq, stream);
@@ -367,6 +385,48 @@ static inline BertBwdWs bert_bwd_ws(int64_t B, int32_t T, int32_t H, int32_t hea
   return w;
 }
 
+static int bert_rel_bias_reduce_launch(const float* sq, int32_t B, int32_t T, int32_t heads, bool add, float* d_bias,
+                                       hipStream_t stream) {
+  const int n = heads * (2 * T - 1);
+  hipLaunchKernelGGL(k_bert_rel_bias_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, sq, B, T, heads,
+                     add ? 1 : 0, d_bias);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+// the workspace of gnnrag_bert_embed_backward, each block on a 256-byte boundary: dz, summ, dy [M, H]
+struct BertEmbedBwdWs {
+  size_t dz, summ, dy, total;
+};
+
+static inline BertEmbedBwdWs bert_embed_bwd_ws(int64_t M, int32_t H) {
+  BertEmbedBwdWs w;
+  const size_t mh = (size_t)M * H * sizeof(float);
+  Carve cv;
+  w.dz = cv.take(mh);
+  w.summ = cv.take(mh);
+  w.dy = cv.take(mh);
+  w.total = cv.off;
+  return w;
+}
+
+// the fill of the two tables (a NULL one is not wanted) and k_bert_embed_scatter on them
+static int bert_embed_scatter_launch(const int64_t* ids, const int32_t* pos, const float* dz, int64_t M, int32_t H,
+                                     int32_t vocab, int32_t max_pos, int32_t word_pad, int32_t pos_pad, float* d_word,
+                                     float* d_pos, hipStream_t st) {
+  if (d_word) GNNRAG_HIP(hipMemsetAsync(d_word, 0, (size_t)vocab * H * sizeof(float), st));
+  if (d_pos) GNNRAG_HIP(hipMemsetAsync(d_pos, 0, (size_t)max_pos * H * sizeof(float), st));
+  if (!d_word && !d_pos) return 0;
+  hipLaunchKernelGGL(k_bert_embed_scatter, dim3((unsigned)((M + kBertLnRows - 1) / kBertLnRows), 2), dim3(64 * kBertLnRows),
+                     0, st, ids, pos, dz, (int)M, H / 4, vocab, max_pos, word_pad, pos_pad, d_word, d_pos);
+  GNNRAG_LAUNCH_CHECK();
+  return 0;
+}
+
+static inline bool bert_embed_bwd_shape_ok(int32_t B, int32_t T, int32_t H) {
+  return !(H & 3) && (int64_t)B * T <= kBertEmbedBwdMaxRows;
+}
+
 static inline bool bert_bwd_shape_ok(int32_t B, int32_t T, int32_t H, int32_t heads, int32_t I) {
   if (H % heads != 0 || (H & 3) || (I & 3) || (int64_t)3 * H > INT32_MAX) return false;
   return bert_att_shape_ok(B, T, heads, H / heads) && (int64_t)B * T < ((int64_t)1 << 31);
@@ -381,15 +441,91 @@ extern "C" size_t gnnrag_bert_attention_backward_workspace_bytes(int32_t B, int3
   return bert_att_bwd_scratch_bytes(B, T, heads);
 }
 
-extern "C" int gnnrag_bert_attention_backward(const float* qkv, const float* d_ctx, int32_t B, int32_t T, int32_t heads,
-                                              int32_t dh, const uint8_t* keep, float scale, float* d_qkv, void* ws,
-                                              size_t ws_bytes, gnnrag_stream_t stream) {
+extern "C" int gnnrag_bert_attention_backward_bias(const float* qkv, const float* d_ctx, int32_t B, int32_t T,
+                                                   int32_t heads, int32_t dh, const float* rel_bias, const uint8_t* keep,
+                                                   float scale, float* d_qkv, void* ws, size_t ws_bytes,
+                                                   gnnrag_stream_t stream) {
   if (B <= 0 || T <= 0 || heads <= 0 || dh <= 0) return GNNRAG_E_BADARG;
   if (!bert_att_shape_ok(B, T, heads, dh)) return GNNRAG_E_UNSUPPORTED;
   if (!qkv || !d_ctx || !d_qkv || !ws || !bert_scale_ok(keep, scale)) return GNNRAG_E_BADARG;
-  if (!aligned16(qkv, d_ctx, d_qkv, ws)) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(qkv, d_ctx, d_qkv, ws, rel_bias)) return GNNRAG_E_UNSUPPORTED;
   if (ws_bytes < bert_att_bwd_scratch_bytes(B, T, heads)) return GNNRAG_E_WORKSPACE;
-  return bert_attention_bwd_launch(qkv, d_ctx, keep, scale, B, T, heads, dh, d_qkv, (float*)ws, (hipStream_t)stream);
+  return bert_attention_bwd_launch(qkv, d_ctx, keep, scale, B, T, heads, dh, d_qkv, (float*)ws, (hipStream_t)stream,
+                                   rel_bias);
+}
+
+extern "C" int gnnrag_bert_attention_backward(const float* qkv, const float* d_ctx, int32_t B, int32_t T, int32_t heads,
+                                              int32_t dh, const uint8_t* keep, float scale, float* d_qkv, void* ws,
+                                              size_t ws_bytes, gnnrag_stream_t stream) {
+  return gnnrag_bert_attention_backward_bias(qkv, d_ctx, B, T, heads, dh, nullptr, keep, scale, d_qkv, ws, ws_bytes, stream);
+}
+
+extern "C" int gnnrag_bert_rel_bias_reduce(const float* sq, int32_t B, int32_t T, int32_t heads, float* d_bias,
+                                           gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || heads <= 0) return GNNRAG_E_BADARG;
+  if (!bert_att_shape_ok(B, T, heads, 32)) return GNNRAG_E_UNSUPPORTED;
+  if (!sq || !d_bias) return GNNRAG_E_BADARG;
+  if (!aligned16(sq, d_bias)) return GNNRAG_E_UNSUPPORTED;
+  return bert_rel_bias_reduce_launch(sq, B, T, heads, false, d_bias, (hipStream_t)stream);
+}
+
+extern "C" size_t gnnrag_bert_embed_backward_workspace_bytes(int32_t B, int32_t T, int32_t H) {
+  if (B <= 0 || T <= 0 || H <= 0 || !bert_embed_bwd_shape_ok(B, T, H)) return 0;
+  return bert_embed_bwd_ws((int64_t)B * T, H).total;
+}
+
+// Backward of gnnrag_bert_embed_forward_save: dy = g_x0 m (k_bert_mask_mul; keep NULL: g_x0 itself), the LayerNorm
+// backward on the saved rows (k_bert_ln_bwd without a mask: the dropout sits behind this LayerNorm), the column sums,
+// then the tables: one fill and k_bert_embed_scatter for d_word / d_pos, the column sum of dz for row 0 of d_type.
+extern "C" int gnnrag_bert_embed_backward(const float* g_x0, const int64_t* ids, const void* reserve, size_t reserve_bytes,
+                                          int32_t B, int32_t T, int32_t H, int32_t vocab, int32_t max_pos, int32_t n_type,
+                                          int32_t word_pad, int32_t pos_pad, const uint8_t* keep, float scale,
+                                          const float* ln_g, float ln_eps, float* d_word, float* d_pos, float* d_type,
+                                          float* d_ln_g, float* d_ln_b, void* ws, size_t ws_bytes,
+                                          gnnrag_stream_t stream) {
+  if (B <= 0 || T <= 0 || H <= 0 || vocab <= 0 || max_pos <= 0 || (d_type && n_type <= 0)) return GNNRAG_E_BADARG;
+  if (!bert_embed_bwd_shape_ok(B, T, H)) return GNNRAG_E_UNSUPPORTED;
+  if (!g_x0 || !ids || !reserve || !ln_g || !ws || !bert_scale_ok(keep, scale)) return GNNRAG_E_BADARG;
+  if (!aligned16(g_x0, reserve, ln_g, d_word, d_pos, d_type, d_ln_g, d_ln_b, ws) || ((uintptr_t)ids & 7) ||
+      ((uintptr_t)keep & 3))
+    return GNNRAG_E_UNSUPPORTED;
+  const int64_t M = (int64_t)B * T;
+  const BertEmbedReserve r = bert_embed_reserve(M, H);
+  const BertEmbedBwdWs w = bert_embed_bwd_ws(M, H);
+  if (reserve_bytes < r.total || ws_bytes < w.total) return GNNRAG_E_WORKSPACE;
+
+  hipStream_t st = (hipStream_t)stream;
+  const float* sum0 = (const float*)((const char*)reserve + r.sum0);
+  const int32_t* pos = (const int32_t*)((const char*)reserve + r.pos);
+  float* dz = (float*)((char*)ws + w.dz);
+  float* summ = (float*)((char*)ws + w.summ);
+  const float* dy = g_x0;
+  if (keep) {
+    float* dyb = (float*)((char*)ws + w.dy);
+    const size_t n4 = (size_t)M * H / 4, blocks = (n4 + 255) / 256;
+    hipLaunchKernelGGL(k_bert_mask_mul, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(256), 0, st, g_x0, keep,
+                       scale, n4, dyb);
+    GNNRAG_LAUNCH_CHECK();
+    dy = dyb;
+  }
+  GNNRAG_RC(bert_ln_bwd_launch(dy, sum0, nullptr, 0.f, nullptr, ln_g, ln_eps, M, H, dz, nullptr, summ, st));
+  GNNRAG_RC(bert_colsum2(summ, d_ln_g, dy, d_ln_b, M, H, H, st));
+  if (d_type) {
+    GNNRAG_RC(bert_colsum2(dz, d_type, nullptr, nullptr, M, H, H, st));
+    if (n_type > 1) GNNRAG_HIP(hipMemsetAsync(d_type + H, 0, (size_t)(n_type - 1) * H * sizeof(float), st));
+  }
+  return bert_embed_scatter_launch(ids, pos, dz, M, H, vocab, max_pos, word_pad, pos_pad, d_word, d_pos, st);
+}
+
+extern "C" int gnnrag_bert_embed_scatter(const float* dz, const int64_t* ids, const int32_t* pos, int64_t M, int32_t H,
+                                         int32_t vocab, int32_t max_pos, int32_t word_pad, int32_t pos_pad, float* d_word,
+                                         float* d_pos, gnnrag_stream_t stream) {
+  if (M <= 0 || H <= 0 || vocab <= 0 || max_pos <= 0) return GNNRAG_E_BADARG;
+  if ((H & 3) || M > kBertEmbedBwdMaxRows) return GNNRAG_E_UNSUPPORTED;
+  if (!dz || !ids || !pos) return GNNRAG_E_BADARG;
+  if (!aligned16(dz, d_word, d_pos) || ((uintptr_t)ids & 7) || ((uintptr_t)pos & 3)) return GNNRAG_E_UNSUPPORTED;
+  return bert_embed_scatter_launch(ids, pos, dz, M, H, vocab, max_pos, word_pad, pos_pad, d_word, d_pos,
+                                   (hipStream_t)stream);
 }
 
 extern "C" int gnnrag_bert_ln_backward(const float* dy, const float* d, const uint8_t* keep, float scale, const float* res,
@@ -422,11 +558,25 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
                                            float scale_att, const void* reserve, size_t reserve_bytes, float* g_x0,
                                            const gnnrag_bert_layer_grads* grads, void* ws, size_t ws_bytes,
                                            gnnrag_stream_t stream_) {
+  return gnnrag_bert_layers_backward_ex(g_out, L, layers, nullptr, ln_eps, B, T, H, heads, I, keep_hidden, scale_hidden,
+                                        keep_att, scale_att, reserve, reserve_bytes, g_x0, grads, nullptr, ws, ws_bytes,
+                                        stream_);
+}
+
+// rel_bias NULL: the launches of gnnrag_bert_layers_backward.  With it the attention step is k_bert_attention_bwd_bias and,
+// d_rel_bias given, k_bert_rel_bias_reduce follows it on the same squares: layer L-1 writes the table, the others add.
+extern "C" int gnnrag_bert_layers_backward_ex(const float* g_out, int32_t L, const gnnrag_bert_layer* layers,
+                                              const float* rel_bias, float ln_eps, int32_t B, int32_t T, int32_t H,
+                                              int32_t heads, int32_t I, const uint8_t* keep_hidden, float scale_hidden,
+                                              const uint8_t* keep_att, float scale_att, const void* reserve,
+                                              size_t reserve_bytes, float* g_x0, const gnnrag_bert_layer_grads* grads,
+                                              float* d_rel_bias, void* ws, size_t ws_bytes, gnnrag_stream_t stream_) {
   if (B <= 0 || T <= 0 || H <= 0 || heads <= 0 || I <= 0 || L <= 0) return GNNRAG_E_BADARG;
   if (!bert_bwd_shape_ok(B, T, H, heads, I)) return GNNRAG_E_UNSUPPORTED;
-  if (!g_out || !layers || !reserve || !ws) return GNNRAG_E_BADARG;
+  if (!g_out || !layers || !reserve || !ws || (d_rel_bias && !rel_bias)) return GNNRAG_E_BADARG;
   if (!bert_scale_ok(keep_hidden, scale_hidden) || !bert_scale_ok(keep_att, scale_att)) return GNNRAG_E_BADARG;
-  if (!aligned16(g_out, reserve, g_x0, ws) || ((uintptr_t)keep_hidden & 3)) return GNNRAG_E_UNSUPPORTED;
+  if (!aligned16(g_out, reserve, g_x0, ws, rel_bias, d_rel_bias) || ((uintptr_t)keep_hidden & 3))
+    return GNNRAG_E_UNSUPPORTED;
   for (int l = 0; l < L; ++l) {
     GNNRAG_RC(bert_layer_ptrs_check(layers[l], kBertFieldsBwd));      // the biases are not read: NULL is legal
     if (grads) {
@@ -491,7 +641,8 @@ extern "C" int gnnrag_bert_layers_backward(const float* g_out, int32_t L, const 
     GNNRAG_RC(bert_colsum2(dY, o.db_o, nullptr, nullptr, M, H, H, st));
     GNNRAG_RC(transpose_launch(p.W_o, wt, H, H, st));
     GNNRAG_RC(gnnrag_linear(dY, M, H, wt, nullptr, nullptr, 0, 0, dctx, H, GNNRAG_MATH_FP32, stream_));
-    GNNRAG_RC(bert_attention_bwd_launch(qkv, dctx, keep.probs(l), scale_att, B, T, heads, dh, dqkv, att, st));
+    GNNRAG_RC(bert_attention_bwd_launch(qkv, dctx, keep.probs(l), scale_att, B, T, heads, dh, dqkv, att, st, rel_bias));
+    if (d_rel_bias) GNNRAG_RC(bert_rel_bias_reduce_launch(att, B, T, heads, l != L - 1, d_rel_bias, st));
     if (o.dW_qkv) GNNRAG_RC(gnnrag_gemm_tn(dqkv, xin, M, 3 * H, H, o.dW_qkv, tn, w.tn_bytes, stream_));
     if (o.db_qkv) {
       // the query and value thirds; the key third is exactly +0

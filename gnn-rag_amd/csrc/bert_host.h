@@ -12,6 +12,8 @@ namespace gnnrag {
 
 constexpr int kBertMaxT = 128;       // keys per question: two per lane
 constexpr int kBertLnRows = 4;       // rows (waves) per workgroup of the LayerNorm kernels
+// rows B T of gnnrag_bert_embed_backward: its scatter compares every row's id with every other's (M M / 64 ballots)
+constexpr int64_t kBertEmbedBwdMaxRows = 65536;
 
 // the shapes the attention kernels (forward and backward) take
 static inline bool bert_att_shape_ok(int64_t B, int32_t T, int32_t heads, int32_t dh) {

@@ -34,4 +34,20 @@ static inline BertReserve bert_reserve(int64_t M, int64_t H, int64_t I) {
   return r;
 }
 
+// The embedding reserve (gnnrag_bert_embed_forward_save, read by gnnrag_bert_embed_backward), without padding:
+//   sum0 [M, H]   the row in front of the embedding LayerNorm: word + type + position
+//   pos  [M]      int32: the position row of each token; -1 for a token whose id or position lies outside its table
+// (H + 1) 4 bytes per row.
+struct BertEmbedReserve {
+  size_t sum0, pos, total;
+};
+
+static inline BertEmbedReserve bert_embed_reserve(int64_t M, int64_t H) {
+  BertEmbedReserve r;
+  r.sum0 = 0;
+  r.pos = (size_t)M * H * sizeof(float);
+  r.total = r.pos + (size_t)M * sizeof(int32_t);
+  return r;
+}
+
 }  // namespace gnnrag

@@ -59,6 +59,17 @@ dropout, its position rule, its lookup backward - and the layers run on ``autogr
 encodes followed by one backward each read their own.  ``hip_finetune_calls`` counts these calls beside ``hip_calls``.  With
 the switch off or unset every call behaves as without it.
 
+``GNNRAG_HIP_LM_FINETUNE_FULL=1`` (read at every call; unset, empty or ``0`` is off, the default; it has a meaning only
+together with ``GNNRAG_HIP_LM_FINETUNE=1``): the whole encoder on the library.  ``x0`` then comes from
+``autograd.BertEmbedFn`` (``gnnrag_bert_embed_forward_save`` / ``gnnrag_bert_embed_backward``: the lookups, the positions, the
+LayerNorm and keep plane 0 of :func:`draw_keep` in one launch; the three table gradients dense and without atomics, the
+``padding_idx`` rows zero as transformers leaves them), and an ``MPNetModel`` is taken as well: its bias table is built
+differentiably per call as ``relative_attention_bias.weight[bucket].t()`` and the layers run on
+``autograd.BertLayersBiasFn``, which returns the table's gradient; torch autograd carries it to the weight.  One more
+refusal: "more rows than the embedding backward takes" (``ops.bert_embed_backward_supported``).
+``hip_finetune_full_calls`` counts these calls beside ``hip_finetune_calls``.  With the switch off every call behaves as
+without it, bit for bit.
+
 An eligible call returns a ``BaseModelOutput`` whose ``[0]`` is ``last_hidden_state``; the pooler is not computed (the
 reference never reads it).  The packed query / key / value weight and bias of every layer are kept on the state object,
 keyed by ``(data_ptr, _version)`` of their six source tensors (as ``install.cache_rel_features`` keys its cache): an
@@ -81,6 +92,7 @@ DEFAULT = "1"        # GNNRAG_HIP_LM for BertModel when unset (DESIGN.md section
 DEFAULT_ON = ("BertModel",)
 TRAIN_DEFAULT = "0"  # GNNRAG_HIP_LM_TRAIN when unset: off (DESIGN.md section 8 f-6 has the rule for a later flip)
 FINETUNE_DEFAULT = "0"  # GNNRAG_HIP_LM_FINETUNE when unset: off (Fine-tuning: the rule for a flip)
+FINETUNE_FULL_DEFAULT = "0"  # GNNRAG_HIP_LM_FINETUNE_FULL when unset: off (Fine-tuning)
 SPLITK_DEFAULT = "0"  # GNNRAG_HIP_LM_SPLITK when unset: off (DESIGN.md section 8 f-6 keeps the measurement)
 # the largest B T at which an inference call with GNNRAG_HIP_LM_SPLITK set takes the split-K encode: the largest measured
 # shape, (8, 20), at which its stream time is not worse than the encode without the switch; at (64, 20) it is
@@ -115,6 +127,13 @@ def finetune_enabled() -> bool:
     """Whether a call that needs a gradient may run its layers on the library (``GNNRAG_HIP_LM_FINETUNE``, read at every
     call; unset, empty or ``0`` is off)."""
     return os.environ.get("GNNRAG_HIP_LM_FINETUNE", FINETUNE_DEFAULT) not in ("0", "")
+
+
+def finetune_full_enabled() -> bool:
+    """Whether a fine-tuning call also runs its embedding stage on the library, and an ``MPNetModel`` may be fine-tuned on it
+    (``GNNRAG_HIP_LM_FINETUNE_FULL``, read at every call; unset, empty or ``0`` is off).  It has a meaning only together
+    with ``GNNRAG_HIP_LM_FINETUNE``."""
+    return os.environ.get("GNNRAG_HIP_LM_FINETUNE_FULL", FINETUNE_FULL_DEFAULT) not in ("0", "")
 
 
 def splitk_enabled() -> bool:
@@ -179,6 +198,7 @@ class _LmPatch:
         self.hip_train_calls = 0                # those of them that ran the training-mode forward
         self.hip_splitk_calls = 0               # those of them that ran the split-K inference encode
         self.hip_finetune_calls = 0             # those of them that ran the layers under autograd (fine-tuning)
+        self.hip_finetune_full_calls = 0        # those of these that ran the embedding stage on the library as well
 
     # -- eligibility ----------------------------------------------------------------------------------------------
     def pad_id(self):
@@ -222,11 +242,14 @@ class _LmPatch:
         if finetune:
             if not finetune_enabled():
                 return "a gradient is needed"
-            if arch["rel_bias"]:
+            full = finetune_full_enabled()
+            if arch["rel_bias"] and not full:
                 return "a gradient is needed and the relative attention bias has no backward on the library"
             if len(enc.encoder.layer) < 1 or not ops.bert_layers_backward_supported(
                     int(ids.shape[1]), int(cfg.hidden_size), int(cfg.num_attention_heads), int(cfg.intermediate_size)):
                 return "a shape the backward kernels do not take"
+            if full and not ops.bert_embed_backward_supported(int(ids.numel()), int(cfg.hidden_size)):
+                return "more rows than the embedding backward takes"
         if self.dropout_active():
             if not finetune and not train_enabled():
                 return "dropout is active"
@@ -304,17 +327,44 @@ class _LmPatch:
         position rule), then the layers on ``autograd.BertLayersFn``."""
         from ... import autograd
         enc, cfg = self.enc, self.enc.config
-        x0 = enc.embeddings(input_ids=ids)
+        full = finetune_full_enabled()
+        if not full:
+            x0 = enc.embeddings(input_ids=ids)
         p_h, p_a, keep_h, keep_a = 0.0, 0.0, None, None
         if self.dropout_active():
-            p_h, p_a, keep_h, keep_a = self._draw(len(enc.encoder.layer), ids)      # plane 0 (the embedding's) is not read
+            # without GNNRAG_HIP_LM_FINETUNE_FULL plane 0 (the embedding's) is not read
+            p_h, p_a, keep_h, keep_a = self._draw(len(enc.encoder.layer), ids)
+        if full:
+            x0 = self._embed_full(ids, keep_h, p_h)
         params = []
         for layer in enc.encoder.layer:
             q, k, v, o, ln1, it, fo, ln2 = self._modules(layer)
             params += [q.weight, k.weight, v.weight, q.bias, k.bias, v.bias, o.weight, o.bias, ln1.weight, ln1.bias,
                        it.weight, it.bias, fo.weight, fo.bias, ln2.weight, ln2.bias]
+        if _ARCH[self.arch]["rel_bias"]:        # only with GNNRAG_HIP_LM_FINETUNE_FULL (refusal)
+            # the table as a function of the weight, per call: torch autograd carries its gradient back through the
+            # bucket gather (rel_bias_table detaches and caches: that one is for the frozen paths)
+            T = int(ids.shape[1])
+            w = enc.encoder.relative_attention_bias.weight
+            bucket = type(enc.encoder).relative_position_bucket(torch.arange(-(T - 1), T, dtype=torch.long),
+                                                                num_buckets=REL_BUCKETS)
+            table = w[bucket.to(w.device)].t()
+            return autograd.BertLayersBiasFn.apply(x0, table, keep_h, _scale(p_h), keep_a, _scale(p_a),
+                                                   int(cfg.num_attention_heads), float(cfg.layer_norm_eps), *params)
         return autograd.BertLayersFn.apply(x0, keep_h, _scale(p_h), keep_a, _scale(p_a), int(cfg.num_attention_heads),
                                            float(cfg.layer_norm_eps), *params)
+
+    def _embed_full(self, ids, keep_h, p_h):
+        """The embedding stage on ``autograd.BertEmbedFn``: keep plane 0 is read, the padding rows are transformers'
+        ``padding_idx`` of the two tables."""
+        from ... import autograd
+        emb, cfg = self.enc.embeddings, self.enc.config
+        type_emb = emb.token_type_embeddings.weight if _ARCH[self.arch]["token_type"] else None
+        return autograd.BertEmbedFn.apply(ids, None if keep_h is None else keep_h[0], _scale(p_h), self.pad_id(),
+                                          emb.word_embeddings.padding_idx, emb.position_embeddings.padding_idx,
+                                          float(cfg.layer_norm_eps), emb.word_embeddings.weight,
+                                          emb.position_embeddings.weight, type_emb, emb.LayerNorm.weight,
+                                          emb.LayerNorm.bias)
 
     # -- the wrapper ----------------------------------------------------------------------------------------------
     def forward(self, *args, **kwargs):
@@ -328,6 +378,7 @@ class _LmPatch:
             hidden = self._finetune(ids)
             self.hip_calls += 1
             self.hip_finetune_calls += 1
+            self.hip_finetune_full_calls += int(finetune_full_enabled())
             return BaseModelOutput(last_hidden_state=hidden)
         type_emb = emb.token_type_embeddings.weight if _ARCH[self.arch]["token_type"] else None
         top = (ids, emb.word_embeddings.weight, emb.position_embeddings.weight, type_emb, emb.LayerNorm.weight,

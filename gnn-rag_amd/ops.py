@@ -2131,10 +2131,13 @@ def _bert_layers_args(x, layers, heads, keep_hidden, scale_hidden, keep_att, sca
 
 def bert_layers_forward_save(x0, layers, heads: int, eps: float, B: int, T: int, math: Optional[int] = None, *,
                              keep_hidden: Optional[torch.Tensor] = None, scale_hidden: float = 1.0,
-                             keep_att: Optional[torch.Tensor] = None, scale_att: float = 1.0):
+                             keep_att: Optional[torch.Tensor] = None, scale_att: float = 1.0,
+                             rel_bias: Optional[torch.Tensor] = None):
     """``gnnrag_bert_layers_forward_save``: the layers of ``bert_encode_train`` on ``x0`` [B*T, H] (or [B,T,H]) - the
     output of the embedding stage - with the same launches, so the bits of ``bert_encode_train`` for the same ``x0`` and
     masks.  ``keep_hidden`` has the (1 + 2L) planes of ``bert_keep_shapes`` (plane 0, the embedding's, is not read).
+    ``rel_bias`` [heads, 2T-1] (MPNet's table, every layer) goes through ``gnnrag_bert_layers_forward_save_ex``; without it
+    the call is the one it has always been.
     Returns ``(out, reserve)``: out of x0's shape and the reserve (uint8, ``gnnrag_bert_reserve_bytes``) that
     :func:`bert_layers_backward` reads; it is allocated per call and belongs to this forward."""
     lib = _lib.load()
@@ -2146,24 +2149,28 @@ def bert_layers_forward_save(x0, layers, heads: int, eps: float, B: int, T: int,
     out = _buf(tuple(x0.shape), torch.float32, dev, role + "out")
     reserve = _buf((max(int(lib.gnnrag_bert_reserve_bytes(L, B, T, H, I)), 1),), torch.uint8, dev, role + "reserve")
     ws = _buf((max(int(lib.gnnrag_bert_workspace_bytes(B, T, H, I)), 1),), torch.uint8, dev, role + "workspace")
+    args, entry = [x0.data_ptr(), L, arr], "gnnrag_bert_layers_forward_save"
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
+        args, entry = args + [rel_bias.data_ptr()], entry + "_ex"
+    args += [float(eps), B, T, H, heads, I, _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att, out.data_ptr(),
+             reserve.data_ptr(), reserve.numel(), ws.data_ptr(), ws.numel(), _math(math), _stream()]
     with torch.cuda.device(dev):
-        _lib.check(lib.gnnrag_bert_layers_forward_save(x0.data_ptr(), L, arr, float(eps), B, T, H, heads, I,
-                                                       _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att,
-                                                       out.data_ptr(), reserve.data_ptr(), reserve.numel(), ws.data_ptr(),
-                                                       ws.numel(), _math(math), _stream()),
-                   "gnnrag_bert_layers_forward_save")
+        _lib.check(getattr(lib, entry)(*args), entry)
     return out, reserve
 
 
 def bert_layers_backward(g_out, layers, heads: int, eps: float, B: int, T: int, reserve, *,
                          keep_hidden: Optional[torch.Tensor] = None, scale_hidden: float = 1.0,
                          keep_att: Optional[torch.Tensor] = None, scale_att: float = 1.0, need_x0: bool = True,
-                         need=None):
+                         need=None, rel_bias: Optional[torch.Tensor] = None, want_rel_bias_grad: bool = False):
     """Backward of :func:`bert_layers_forward_save` (``gnnrag_bert_layers_backward``): ``g_out`` the gradient of its output,
     the layers, masks and scales as given to it, ``reserve`` as it returned it.  ``need``: per layer a dict over
     ``BERT_GRAD_FIELDS`` of what is wanted (None: everything); an unwanted gradient is None and its product is not launched.
     Returns ``(g_x0, grads)``: g_x0 of g_out's shape (None without ``need_x0``) and a list of dicts over ``BERT_GRAD_FIELDS``
-    (dW_qkv [3H,H], db_qkv [3H] with the key third exactly 0, ...).  One fixed summation order: the same bits every time."""
+    (dW_qkv [3H,H], db_qkv [3H] with the key third exactly 0, ...).  One fixed summation order: the same bits every time.
+    ``rel_bias`` as given to the forward (``gnnrag_bert_layers_backward_ex``); with ``want_rel_bias_grad`` the return is
+    ``(g_x0, grads, d_rel_bias)``, d_rel_bias [heads, 2T-1] the table's gradient summed over the layers."""
     lib = _lib.load()
     g_out, H, I, L, keep_hidden, scale_hidden, keep_att, scale_att = _bert_layers_args(
         g_out, layers, heads, keep_hidden, scale_hidden, keep_att, scale_att, B, T, "g_out")
@@ -2182,21 +2189,35 @@ def bert_layers_backward(g_out, layers, heads: int, eps: float, B: int, T: int, 
             setattr(garr[l], name, _ptr(g[name]))
         grads.append(g)
     g_x0 = _buf(tuple(g_out.shape), torch.float32, dev, role + "g_x0") if need_x0 else None
+    if want_rel_bias_grad and rel_bias is None:
+        raise ValueError("bert_layers_backward: want_rel_bias_grad without rel_bias")
+    d_rel_bias = None
+    args, entry = [g_out.data_ptr(), L, arr], "gnnrag_bert_layers_backward"
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
+        if want_rel_bias_grad:
+            d_rel_bias = _buf((heads, 2 * T - 1), torch.float32, dev, role + "d_rel_bias")
+        args, entry = args + [rel_bias.data_ptr()], entry + "_ex"
     with torch.cuda.device(dev):
         # the size depends on the CURRENT device's CU count (gnnrag_gemm_tn inside): query it on g_out's device
         ws = _buf((max(int(lib.gnnrag_bert_layers_backward_workspace_bytes(B, T, H, heads, I)), 16),), torch.uint8, dev,
                   role + "workspace")
-        _lib.check(lib.gnnrag_bert_layers_backward(g_out.data_ptr(), L, arr, float(eps), B, T, H, heads, I,
-                                                   _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att,
-                                                   reserve.data_ptr(), reserve.numel(), _ptr(g_x0), garr, ws.data_ptr(),
-                                                   ws.numel(), _stream()), "gnnrag_bert_layers_backward")
-    return g_x0, grads
+        args += [float(eps), B, T, H, heads, I, _ptr(keep_hidden), scale_hidden, _ptr(keep_att), scale_att,
+                 reserve.data_ptr(), reserve.numel(), _ptr(g_x0), garr]
+        if rel_bias is not None:
+            args.append(_ptr(d_rel_bias))
+        args += [ws.data_ptr(), ws.numel(), _stream()]
+        _lib.check(getattr(lib, entry)(*args), entry)
+    return (g_x0, grads, d_rel_bias) if want_rel_bias_grad else (g_x0, grads)
 
 
 def bert_attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, T: int, heads: int, dh: int,
-                            keep: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
+                            keep: Optional[torch.Tensor] = None, scale: float = 1.0,
+                            rel_bias: Optional[torch.Tensor] = None, want_bias_grad: bool = False):
     """``gnnrag_bert_attention_backward``: d_qkv [B*T, 3*heads*dh] from qkv, d_ctx [B*T, heads*dh] and the keep bytes
-    [B, heads, T, T] of :func:`bert_attention_drop` (None: :func:`bert_attention`).  The probabilities are recomputed."""
+    [B, heads, T, T] of :func:`bert_attention_drop` (None: :func:`bert_attention`).  The probabilities are recomputed.
+    ``rel_bias`` [heads, 2T-1] as given to the forward (``gnnrag_bert_attention_backward_bias``); with ``want_bias_grad``
+    the return is ``(d_qkv, d_bias)``: :func:`bert_rel_bias_reduce` on the squares the kernel left in its workspace."""
     lib = _lib.load()
     H = heads * dh
     qkv = _chk(qkv, "qkv", shape=(B * T, 3 * H))
@@ -2208,11 +2229,133 @@ def bert_attention_backward(qkv: torch.Tensor, d_ctx: torch.Tensor, B: int, T: i
     d_qkv = _buf((B * T, 3 * H), torch.float32, qkv.device, role + "d_qkv")
     ws = _buf((max(int(lib.gnnrag_bert_attention_backward_workspace_bytes(B, T, heads)), 16),), torch.uint8, qkv.device,
               role + "workspace")
+    args, entry = [qkv.data_ptr(), d_ctx.data_ptr(), B, T, heads, dh], "gnnrag_bert_attention_backward"
+    if rel_bias is not None:
+        rel_bias = _chk(rel_bias.detach(), "rel_bias", shape=(heads, 2 * T - 1))
+        args, entry = args + [rel_bias.data_ptr()], entry + "_bias"
+    args += [_ptr(keep), float(scale), d_qkv.data_ptr(), ws.data_ptr(), ws.numel(), _stream()]
     with torch.cuda.device(qkv.device):
-        _lib.check(lib.gnnrag_bert_attention_backward(qkv.data_ptr(), d_ctx.data_ptr(), B, T, heads, dh, _ptr(keep),
-                                                      float(scale), d_qkv.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                      _stream()), "gnnrag_bert_attention_backward")
-    return d_qkv
+        _lib.check(getattr(lib, entry)(*args), entry)
+    if not want_bias_grad:
+        return d_qkv
+    sq = ws[: B * heads * 2 * T * T * 4].view(torch.float32).view(B * heads, 2, T, T)
+    return d_qkv, bert_rel_bias_reduce(sq, B, T, heads)
+
+
+def bert_rel_bias_reduce(sq: torch.Tensor, B: int, T: int, heads: int) -> torch.Tensor:
+    """``gnnrag_bert_rel_bias_reduce``: ``d_bias[h, d + T - 1]`` = the sum over the questions b and the entries
+    (i, j = i + d) of the dS squares ``sq[b * heads + h, 0]`` (``sq`` [B*heads, 2, T, T], the scratch layout of the
+    attention backward), b ascending, then i ascending."""
+    lib = _lib.load()
+    sq = _chk(sq, "sq", shape=(B * heads, 2, T, T))
+    d_bias = _buf((heads, 2 * T - 1), torch.float32, sq.device, "bert_rel_bias_reduce: d_bias")
+    with torch.cuda.device(sq.device):
+        _lib.check(lib.gnnrag_bert_rel_bias_reduce(sq.data_ptr(), B, T, heads, d_bias.data_ptr(), _stream()),
+                   "gnnrag_bert_rel_bias_reduce")
+    return d_bias
+
+
+BERT_EMBED_BWD_MAX_ROWS = 65536                 # rows B T of gnnrag_bert_embed_backward (include/gnnrag.h)
+BERT_EMBED_GRADS = ("d_word", "d_pos", "d_type", "d_ln_g", "d_ln_b")
+
+
+def bert_embed_backward_supported(M: int, H: int) -> bool:
+    """Whether ``gnnrag_bert_embed_backward`` takes ``M = B T`` rows of width ``H`` (the header's rules)."""
+    return 0 < M <= BERT_EMBED_BWD_MAX_ROWS and H > 0 and H % 4 == 0
+
+
+def bert_embed_scatter(dz, ids, pos, vocab: int, max_pos: int, word_pad: Optional[int] = None,
+                       pos_pad: Optional[int] = None):
+    """``gnnrag_bert_embed_scatter``, the table step of :func:`bert_embed_backward` alone: ``(d_word [vocab,H], d_pos
+    [max_pos,H])`` from ``dz`` [M,H], ``ids`` [M] int64 and ``pos`` [M] int32 - row k the sum of the dz rows that name it in
+    ascending row order, +0 where none does and at the pad rows."""
+    lib = _lib.load()
+    dz = _chk(dz, "dz")
+    M, H = dz.shape
+    ids, pos = _chk(ids, "ids", dtype=torch.int64, shape=(M,)), _chk(pos, "pos", dtype=torch.int32, shape=(M,))
+    role = "bert_embed_scatter: "
+    d_word = _buf((vocab, H), torch.float32, dz.device, role + "d_word")
+    d_pos = _buf((max_pos, H), torch.float32, dz.device, role + "d_pos")
+    with torch.cuda.device(dz.device):
+        _lib.check(lib.gnnrag_bert_embed_scatter(dz.data_ptr(), ids.data_ptr(), pos.data_ptr(), M, H, int(vocab), int(max_pos),
+                                                 -1 if word_pad is None else int(word_pad),
+                                                 -1 if pos_pad is None else int(pos_pad), d_word.data_ptr(),
+                                                 d_pos.data_ptr(), _stream()), "gnnrag_bert_embed_scatter")
+    return d_word, d_pos
+
+
+def _bert_embed_args(ids, H, keep, scale):
+    ids = _chk(ids, "ids", dtype=torch.int64)
+    if ids.dim() != 2:
+        raise ValueError("ids must be [B,T]")
+    B, T = ids.shape
+    if keep is not None:
+        keep = _chk(keep, "keep", dtype=torch.uint8, shape=(B * T, H))
+        scale = _keep_scale(scale, "scale")
+    return ids, int(B), int(T), keep, float(scale)
+
+
+def bert_embed_forward_save(ids, word_emb, pos_emb, type_emb, ln_g, ln_b, eps: float, *, pad_id: Optional[int] = None,
+                            keep: Optional[torch.Tensor] = None, scale: float = 1.0):
+    """``gnnrag_bert_embed_forward_save``: the embedding stage of ``bert_encode_train`` - ids [B,T] -> ``x0`` [B,T,H] with
+    that call's bits for the same tables and ``keep`` (plane 0 of its ``keep_hidden``: uint8 [B*T,H], or None) - and the
+    reserve (uint8, ``gnnrag_bert_embed_reserve_bytes``) that :func:`bert_embed_backward` reads.  ``type_emb`` / ``pad_id``
+    as in ``bert_encode``.  Returns ``(x0, reserve)``."""
+    lib = _lib.load()
+    word_emb = _chk(word_emb.detach(), "word_emb")
+    vocab, H = word_emb.shape
+    ids, B, T, keep, scale = _bert_embed_args(ids, H, keep, scale)
+    pos_emb = _chk(pos_emb.detach(), "pos_emb")
+    if pos_emb.dim() != 2 or pos_emb.shape[1] != H:
+        raise ValueError("pos_emb must be [max_pos,H]")
+    if type_emb is not None:
+        type_emb = _chk(type_emb.detach(), "type_emb")
+        if type_emb.dim() != 2 or type_emb.shape[1] != H or type_emb.shape[0] < 1:
+            raise ValueError("type_emb must be [>=1,H]")
+    ln_g, ln_b = _chk(ln_g.detach(), "ln_g", shape=(H,)), _chk(ln_b.detach(), "ln_b", shape=(H,))
+    dev, role = ids.device, "bert_embed_forward_save: "
+    out = _buf((B, T, H), torch.float32, dev, role + "out")
+    reserve = _buf((max(int(lib.gnnrag_bert_embed_reserve_bytes(B, T, H)), 16),), torch.uint8, dev, role + "reserve")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_embed_forward_save(ids.data_ptr(), word_emb.data_ptr(), vocab, pos_emb.data_ptr(),
+                                                      pos_emb.shape[0], _ptr(type_emb), _bert_pad_id(pad_id),
+                                                      ln_g.data_ptr(), ln_b.data_ptr(), float(eps), B, T, H, _ptr(keep),
+                                                      scale, out.data_ptr(), reserve.data_ptr(), reserve.numel(),
+                                                      _stream()), "gnnrag_bert_embed_forward_save")
+    return out, reserve
+
+
+def bert_embed_backward(g_x0, ids, reserve, ln_g, eps: float, vocab: int, max_pos: int, n_type: int = 0, *,
+                        word_pad: Optional[int] = None, pos_pad: Optional[int] = None,
+                        keep: Optional[torch.Tensor] = None, scale: float = 1.0, need=None):
+    """Backward of :func:`bert_embed_forward_save` (``gnnrag_bert_embed_backward``): ``g_x0`` [B,T,H] (or [B*T,H]) the
+    gradient of its output, ``ids``, ``keep`` and ``scale`` as given to it, ``reserve`` as it returned it.  ``word_pad`` /
+    ``pos_pad``: the table row whose gradient stays zero (transformers' ``padding_idx``; None: no such row).  ``n_type``: the
+    rows of the token-type table (0: the encoder has none).  ``need``: a dict over ``BERT_EMBED_GRADS`` of what is wanted
+    (None: everything the encoder has); an unwanted gradient is None and is not computed.  Returns a dict over
+    ``BERT_EMBED_GRADS``: d_word [vocab,H], d_pos [max_pos,H], d_type [n_type,H], d_ln_g, d_ln_b [H], every one fully
+    written - a row no token names is +0 - in one fixed summation order: the same bits every time."""
+    lib = _lib.load()
+    H = int(g_x0.shape[-1])
+    ids, B, T, keep, scale = _bert_embed_args(ids, H, keep, scale)
+    g_x0 = _chk(g_x0, "g_x0", shape=(B * T, H) if g_x0.dim() == 2 else (B, T, H))
+    reserve = _chk(reserve, "reserve", dtype=torch.uint8)
+    ln_g = _chk(ln_g.detach(), "ln_g", shape=(H,))
+    dev, role = g_x0.device, "bert_embed_backward: "
+    shapes = {"d_word": (vocab, H), "d_pos": (max_pos, H), "d_type": (n_type, H), "d_ln_g": (H,), "d_ln_b": (H,)}
+    out = {}
+    for name in BERT_EMBED_GRADS:
+        wanted = (bool(need.get(name, False)) if need is not None else True) and (name != "d_type" or n_type > 0)
+        out[name] = _buf(shapes[name], torch.float32, dev, role + name) if wanted else None
+    ws = _buf((max(int(lib.gnnrag_bert_embed_backward_workspace_bytes(B, T, H)), 16),), torch.uint8, dev, role + "workspace")
+    with torch.cuda.device(dev):
+        _lib.check(lib.gnnrag_bert_embed_backward(g_x0.data_ptr(), ids.data_ptr(), reserve.data_ptr(), reserve.numel(), B, T,
+                                                  H, int(vocab), int(max_pos), int(n_type),
+                                                  -1 if word_pad is None else int(word_pad),
+                                                  -1 if pos_pad is None else int(pos_pad), _ptr(keep), scale,
+                                                  ln_g.data_ptr(), float(eps), *[_ptr(out[n]) for n in BERT_EMBED_GRADS],
+                                                  ws.data_ptr(), ws.numel(), _stream()), "gnnrag_bert_embed_backward")
+    return out
 
 
 def bert_ln_backward(dy: torch.Tensor, d: torch.Tensor, g: torch.Tensor, eps: float,

@@ -986,9 +986,10 @@ int gnnrag_bert_encode_train(const int64_t* ids, const float* word_emb, int32_t 
                              size_t ws_bytes, int32_t math, gnnrag_stream_t stream);
 
 /* ---- Fine-tuning the encoder: the layers under autograd (additive to ABI 16; DESIGN.md section 8 f-6, Fine-tuning) --------
- * The reference's --lm_frozen 0 trains the LM with the GNN.  The embedding stage stays with the caller (its output x0
- * [B T, H] comes in, its gradient g_x0 goes out); BertModel / RobertaModel layers only (no rel_bias: MPNet's table would
- * need a gradient of its own).
+ * The reference's --lm_frozen 0 trains the LM with the GNN.  These two entries are the layers: the embedding stage's output
+ * x0 [B T, H] comes in, its gradient g_x0 goes out (the stage itself: gnnrag_bert_embed_forward_save / _backward in the
+ * next block, or the caller's own); BertModel / RobertaModel layers (no rel_bias; MPNet's table and its gradient: the
+ * _ex forms of the next block).
  *
  * gnnrag_bert_layers_forward_save: the L layers of gnnrag_bert_encode_train on x0 - the same launches on the same values in
  * the same order, so `out` [B T, H] has the bits gnnrag_bert_encode_train gives for the same x0 and masks (keep_hidden: the
@@ -1053,6 +1054,88 @@ int gnnrag_bert_ln_backward(const float* dy, const float* d, const uint8_t* keep
                             float* dY /* or NULL */, float* summ, float* dgamma /* or NULL */, float* dbeta /* or NULL */,
                             gnnrag_stream_t stream);
 int gnnrag_bert_gelu_backward(const float* pre, const float* d_act, int64_t n, float* d_pre, float* act /* or NULL */,
+                              gnnrag_stream_t stream);
+
+/* ---- Fine-tuning the whole encoder: the embedding stage and MPNet's relative bias (additive to ABI 16) ----
+ * With these the three classes run from the ids to last_hidden_state and back to every parameter on the library.
+ *
+ * gnnrag_bert_embed_forward_save: the embedding launch of gnnrag_bert_encode_train on the same arguments (pad_id >= 0:
+ * positions from the ids; type_emb NULL: no token-type term; keep: plane 0 of keep_hidden, [M,H] bytes, or NULL), so `out`
+ * [M,H] has that call's bits, M = B T.  A second launch leaves in `reserve` (gnnrag_bert_embed_reserve_bytes(B, T, H) =
+ * M (H + 1) 4 bytes; 0 for a size <= 0 or H % 4 != 0), without padding: sum0 [M,H], the row in front of the LayerNorm, then
+ * pos [M] int32, the position row of every token; -1 for a token whose id or position lies outside its table (the forward
+ * makes that row NaN, and its sum0 row NaN).
+ *
+ * gnnrag_bert_embed_backward: from g_x0 [M,H], the reserve, the ids, the keep bytes and scale of the forward and the
+ * LayerNorm weight.  The dropout sits BEHIND this LayerNorm: dy = g_x0 m, then the LayerNorm backward on sum0 gives dz
+ * [M,H], d_ln_g = colsum(dy xhat), d_ln_b = colsum(dy) (8-slice column sums).  The tables are dense, fully written outputs:
+ *   d_word [vocab,H], d_pos [max_pos,H]: row k is the sum of the dz rows of the tokens that name it, in ascending row order;
+ *     a row no token names is exactly +0, and so is row word_pad / pos_pad (transformers' padding_idx; -1: none).  A token
+ *     with pos = -1, a pos >= max_pos or an id outside [0, vocab) adds to neither table and indexes nothing.
+ *   d_type [n_type,H]: row 0 is the column sum of dz (every token has type 0), the other rows +0.
+ * No sort and no atomics: a wave per (token, table) compares its key with the keys of all rows, 64 per ballot; the first
+ * row of a key owns the table row.  That is M M / 64 ballots per table: M <= 65536 rows, more is GNNRAG_E_UNSUPPORTED.
+ * Any of the five outputs may be NULL: not wanted, not computed.  Workspace: gnnrag_bert_embed_backward_workspace_bytes(B,
+ * T, H) = three [M,H] blocks on 256-byte boundaries (0 for a size <= 0 or a shape outside the rules).
+ * Rules of both calls, in this order before anything is launched: a size <= 0 (n_type with d_type given included) is
+ * GNNRAG_E_BADARG; then the shape rules whatever the pointers are - H % 4 != 0, M too large, and for the forward T > 128,
+ * T > max_pos, T + pad_id > max_pos - 1 - are GNNRAG_E_UNSUPPORTED; then a NULL among the required pointers or a scale of a
+ * given mask that is not finite and > 0 is GNNRAG_E_BADARG; then a pointer that is not 16-byte aligned (ids: 8, keep: 4) is
+ * GNNRAG_E_UNSUPPORTED; then a reserve or workspace below the stated size is GNNRAG_E_WORKSPACE.
+ *
+ * gnnrag_bert_layers_forward_save_ex / gnnrag_bert_layers_backward_ex: the two entries of the block above plus rel_bias
+ * [heads, 2T-1] or NULL (MPNet: rel_bias[h][j - i + T - 1] is added to the scaled score of query i and key j of every
+ * layer, as gnnrag_bert_encode_train adds it) and, backward, d_rel_bias [heads, 2T-1] or NULL.  With rel_bias NULL they
+ * enqueue what the entries above enqueue, which are these calls with NULL.  The attention backward recomputes the
+ * probabilities with the bias; an all-zero table gives the bits of the call without one.  d_rel_bias[h][d + T - 1] =
+ * sum_b sum_{i, j = i + d} dS[b,h,i,j], read from the dS squares the attention backward leaves in its scratch: one owner
+ * per entry, b ascending, then i ascending; the layers share the table, their sums are added in the order L-1 .. 0 and the
+ * output is fully written.  The key third of db_qkv stays +0: the rows of dS still sum to zero.  d_rel_bias without
+ * rel_bias is GNNRAG_E_BADARG; both pointers are 16-byte aligned; every other rule, the reserve and the workspaces are
+ * those of the block above.
+ *
+ * The two kernels alone (tests): gnnrag_bert_attention_backward_bias (gnnrag_bert_attention_backward plus rel_bias or NULL;
+ * ws receives [B heads, 2, T, T]: the dS and the dropped-probability square of every (question, head)) and
+ * gnnrag_bert_rel_bias_reduce (d_bias [heads, 2T-1], fully written, from such a scratch); and the table step of the
+ * embedding backward alone, gnnrag_bert_embed_scatter: d_word / d_pos (either may be NULL) from a given dz [M,H], ids [M] and
+ * pos [M] int32, with that call's rules for M, H, the two pads and the tokens that name no row. */
+size_t gnnrag_bert_embed_reserve_bytes(int32_t B, int32_t T, int32_t H);
+int gnnrag_bert_embed_forward_save(const int64_t* ids, const float* word_emb, int32_t vocab, const float* pos_emb,
+                                   int32_t max_pos, const float* type_emb /* or NULL */, int32_t pad_id /* -1: 0..T-1 */,
+                                   const float* ln_g, const float* ln_b, float ln_eps, int32_t B, int32_t T, int32_t H,
+                                   const uint8_t* keep /* [B T,H] or NULL */, float scale, float* out /* [B T,H] */,
+                                   void* reserve, size_t reserve_bytes, gnnrag_stream_t stream);
+size_t gnnrag_bert_embed_backward_workspace_bytes(int32_t B, int32_t T, int32_t H);
+int gnnrag_bert_embed_backward(const float* g_x0 /* [B T,H] */, const int64_t* ids, const void* reserve,
+                               size_t reserve_bytes, int32_t B, int32_t T, int32_t H, int32_t vocab, int32_t max_pos,
+                               int32_t n_type, int32_t word_pad /* or -1 */, int32_t pos_pad /* or -1 */,
+                               const uint8_t* keep /* [B T,H] or NULL */, float scale, const float* ln_g, float ln_eps,
+                               float* d_word /* [vocab,H] or NULL */, float* d_pos /* [max_pos,H] or NULL */,
+                               float* d_type /* [n_type,H] or NULL */, float* d_ln_g /* [H] or NULL */,
+                               float* d_ln_b /* [H] or NULL */, void* ws, size_t ws_bytes, gnnrag_stream_t stream);
+int gnnrag_bert_layers_forward_save_ex(const float* x0 /* [B T,H] */, int32_t L, const gnnrag_bert_layer* layers,
+                                       const float* rel_bias /* [heads,2T-1] or NULL */, float ln_eps, int32_t B, int32_t T,
+                                       int32_t H, int32_t heads, int32_t I, const uint8_t* keep_hidden /* or NULL */,
+                                       float scale_hidden, const uint8_t* keep_att /* or NULL */, float scale_att,
+                                       float* out /* [B T,H] */, void* reserve, size_t reserve_bytes, void* ws,
+                                       size_t ws_bytes, int32_t math, gnnrag_stream_t stream);
+int gnnrag_bert_layers_backward_ex(const float* g_out /* [B T,H] */, int32_t L, const gnnrag_bert_layer* layers,
+                                   const float* rel_bias /* [heads,2T-1] or NULL */, float ln_eps, int32_t B, int32_t T,
+                                   int32_t H, int32_t heads, int32_t I, const uint8_t* keep_hidden /* or NULL */,
+                                   float scale_hidden, const uint8_t* keep_att /* or NULL */, float scale_att,
+                                   const void* reserve, size_t reserve_bytes, float* g_x0 /* [B T,H] or NULL */,
+                                   const gnnrag_bert_layer_grads* grads /* or NULL */,
+                                   float* d_rel_bias /* [heads,2T-1] or NULL */, void* ws, size_t ws_bytes,
+                                   gnnrag_stream_t stream);
+int gnnrag_bert_attention_backward_bias(const float* qkv, const float* d_ctx, int32_t B, int32_t T, int32_t heads,
+                                        int32_t dh, const float* rel_bias /* [heads,2T-1] or NULL */,
+                                        const uint8_t* keep /* [B,heads,T,T] or NULL */, float scale, float* d_qkv,
+                                        void* ws, size_t ws_bytes, gnnrag_stream_t stream);
+int gnnrag_bert_rel_bias_reduce(const float* sq /* [B heads,2,T,T] */, int32_t B, int32_t T, int32_t heads,
+                                float* d_bias /* [heads,2T-1] */, gnnrag_stream_t stream);
+int gnnrag_bert_embed_scatter(const float* dz /* [M,H] */, const int64_t* ids, const int32_t* pos, int64_t M, int32_t H,
+                              int32_t vocab, int32_t max_pos, int32_t word_pad /* or -1 */, int32_t pos_pad /* or -1 */,
+                              float* d_word /* [vocab,H] or NULL */, float* d_pos /* [max_pos,H] or NULL */,
                               gnnrag_stream_t stream);
 
 /* ---- Split-K linear for few rows, and the inference encoder on it (additive to ABI 16) ------------

@@ -10,6 +10,8 @@
                                       [--out profiles/bert_encoder_splitk_time.jsonl]
     python tools/time_bert_encoder.py --finetune [--arch bert|roberta]
                                       [--out profiles/bert_encoder_finetune_time.jsonl]
+    python tools/time_bert_encoder.py --finetune --full [--arch bert|roberta|mpnet]
+                                      [--out profiles/bert_encoder_finetune_full_time.jsonl]
 
 * the encode: a MiniLM-shaped ``BertModel`` (hidden 384, 12 heads, intermediate 1536, 6 layers; random weights from
   tests/bert_oracle.py - the real all-MiniLM-L6-v2 weights are not needed for a timing) in eval mode, ``enc(ids)[0]`` on a
@@ -44,6 +46,10 @@ transformers' dropout 0.1: ``out = enc(ids)[0]; out.backward(g)`` with every par
 cleared before each iteration, ``GNNRAG_HIP_LM=1`` in both legs and ``GNNRAG_HIP_LM_FINETUNE`` off (transformers and torch
 autograd) and on (transformers' embedding stage, the layers on ``gnnrag_bert_layers_forward_save`` /
 ``gnnrag_bert_layers_backward``), each in a process of its own; the same shapes, host enqueue and stream time of the pair.
+``--finetune --full`` (``--arch bert|roberta|mpnet``): ``GNNRAG_HIP_LM_FINETUNE=1`` in both legs and
+``GNNRAG_HIP_LM_FINETUNE_FULL`` off (the path above; for MPNet transformers' own forward and backward) and on (the embedding
+stage on ``gnnrag_bert_embed_forward_save`` / ``_backward`` as well, MPNet's layers with its relative bias), written to
+``profiles/bert_encoder_finetune_full_time.jsonl``.
 
 ``--kernel``: ``gnnrag_bert_attention`` alone, 20 calls per graph, per library given in ``--libs`` as ``label=path``
 (``GNNRAG_LIB``; empty path = the built library): how the workgroup size (``-DGNNRAG_BERT_ATT_THREADS``,
@@ -206,8 +212,8 @@ def child_encode(a):
 def child_finetune(a):
     torch, bo, dev = _setup()
     import numpy as np
-    from gnnrag_amd.modules.question_encoding.lm_encoder import finetune_enabled, patch_lm_encoder
-    on = finetune_enabled()
+    from gnnrag_amd.modules.question_encoding.lm_encoder import finetune_enabled, finetune_full_enabled, patch_lm_encoder
+    on, full = finetune_enabled(), finetune_full_enabled()
     if a.arch == "bert":
         shape, n_layers, vocab = bo.MINILM, L, VOCAB
         enc = bo.make_model(bo.config(L=L, vocab=VOCAB, max_pos=MAX_POS, **bo.MINILM), seed=1)[0]
@@ -224,7 +230,7 @@ def child_finetune(a):
             ids0[1::2, T // 2:] = 1             # every second question padded from the middle (pad id 1)
         ids0 = torch.from_numpy(ids0).long().to(dev)
         g = torch.randn(B, T, shape["H"], device=dev)
-        before = patch.hip_finetune_calls
+        before, before_full = patch.hip_finetune_calls, patch.hip_finetune_full_calls
         host, ev = [], []
         for it in range(a.warm + a.iters):
             x = ids0.clone()
@@ -244,6 +250,8 @@ def child_finetune(a):
                "H": shape["H"], "I": shape["I"], "host_ms": _median(host), "event_ms": _median(ev), "host_ms_min": min(host),
                "event_ms_min": min(ev), "iters": a.iters, "warm": a.warm, "dropout": float(enc.config.hidden_dropout_prob),
                "hip_finetune_calls_per_encode": (patch.hip_finetune_calls - before) / (a.warm + a.iters),
+               "full": "on" if full else "off",
+               "hip_finetune_full_calls_per_encode": (patch.hip_finetune_full_calls - before_full) / (a.warm + a.iters),
                "device": torch.cuda.get_device_name(0)}
         print(TAG + json.dumps(rec), flush=True)
 
@@ -335,6 +343,8 @@ def main():
     ap.add_argument("--splitk", action="store_true", help="inference: GNNRAG_HIP_LM_SPLITK off / on; with --kernel the products")
     ap.add_argument("--finetune", action="store_true",
                     help="unfrozen, training mode, forward + backward: GNNRAG_HIP_LM_FINETUNE off / on")
+    ap.add_argument("--full", action="store_true",
+                    help="with --finetune: GNNRAG_HIP_LM_FINETUNE on in both legs, GNNRAG_HIP_LM_FINETUNE_FULL off / on")
     ap.add_argument("--libs", default="256=")
     ap.add_argument("--limit", type=int, default=240, help="seconds one child process may take")
     ap.add_argument("--out", default=None)
@@ -344,10 +354,12 @@ def main():
     if a.child:
         return {"encode": child_encode, "kernel": child_kernel, "splitk_kernel": child_splitk_kernel,
                 "finetune": child_finetune}[a.child](a)
-    if a.finetune and a.arch == "mpnet":
-        raise SystemExit("--finetune: MPNetModel keeps transformers' forward in both legs, there is nothing to compare")
+    if a.finetune and a.arch == "mpnet" and not a.full:
+        raise SystemExit("--finetune: MPNetModel keeps transformers' forward in both legs, there is nothing to compare "
+                         "(--finetune --full compares it)")
     if a.out is None:
-        a.out = os.path.join(REPO, "profiles", "bert_encoder_finetune_time.jsonl" if a.finetune else
+        a.out = os.path.join(REPO, "profiles", "bert_encoder_finetune_full_time.jsonl" if a.finetune and a.full else
+                             "bert_encoder_finetune_time.jsonl" if a.finetune else
                              "bert_encoder_splitk_time.jsonl" if a.splitk else "bert_encoder_time.jsonl")
     common = (["--iters", str(a.iters), "--warm", str(a.warm), "--arch", a.arch] + (["--train"] if a.train else []) +
               (["--splitk"] if a.splitk else []))
@@ -356,8 +368,10 @@ def main():
         for rnd in range(a.rounds):
             for switch in ("0", "1"):
                 before = len(lines)
-                _spawn(["--child", "finetune"] + common, {"GNNRAG_HIP_LM": "1", "GNNRAG_HIP_LM_FINETUNE": switch}, lines,
-                       a.limit)
+                env = {"GNNRAG_HIP_LM": "1", "GNNRAG_HIP_LM_FINETUNE": switch, "GNNRAG_HIP_LM_FINETUNE_FULL": "0"}
+                if a.full:      # GNNRAG_HIP_LM_FINETUNE on in both legs: the off leg is the path without the new switch
+                    env.update({"GNNRAG_HIP_LM_FINETUNE": "1", "GNNRAG_HIP_LM_FINETUNE_FULL": switch})
+                _spawn(["--child", "finetune"] + common, env, lines, a.limit)
                 for rec in lines[before:]:
                     rec["round"] = rnd
     elif a.splitk and a.kernel:
